@@ -1,6 +1,7 @@
 """Benchmark: PGM iterations/sec over batched blends (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W [--config cfg3|cfg1|cfg4|cfg5] [--weak]
+                    [--full] [--dump-outputs DIR]
 
 A step = one proximal-gradient iteration (render -> FFT convolution -> weighted
 residual/loss -> adjoint convolution -> gradient gather -> AMSGrad -> prox chain)
@@ -29,7 +30,19 @@ Workloads (BASELINE.json configs):
 (``torch.distributed.run``, one per GPU; when the box has fewer GPUs than N the ranks
 share GPUs over gloo -- a functional check, flagged in ``config``).
 
-Output: ONE JSON line on rank 0 with the contract's fields plus
+A plain run sets up, warms up (clock ramp + W iterations), times the K iterations, writes
+the outputs with ``--dump-outputs DIR`` and prints ONE JSON line on rank 0 with the
+contract's fields and the workload's description (``config``, ``comm``).
+
+``--dump-outputs DIR`` (one GPU): what the timed path leaves a caller after its last
+iteration, as DIR/<name>.npy -- every component's SED (float32), the morphologies of a fixed,
+seeded sample of blends (float32, flattened, with the sample's blend indices), the free
+centres (float64) and every blend's loss at the last iteration (float64).  The inputs are
+seeded, so two builds can be compared file by file.
+
+``--full`` adds what the headline figure does not need (the cold window before the clock ramp,
+everything else after the timed region):
+  cold_window  config.cold_window_value: the same K iterations timed before the clock ramp
   roofline     dominant kernel: algorithmic bytes per launch / mean launch duration
                (HIP events on the batch stream over the same K iterations, replayed
                in one range of blends), at the FFT shape the kernel runs; `traffic`,
@@ -155,6 +168,31 @@ def oracle_check(scenes, picks, loss, K, e_rel):
         raise AssertionError("device fit differs from the oracle: %.3g (first 12 iterations), "
                              "%.3g (all)" % (worst_early, worst))
     return worst_early, worst
+
+
+def dump_outputs(batch, loss, out_dir, morph_budget=48 << 20):
+    """``--dump-outputs``: the parameters after the last timed iteration and the loss of that
+    iteration, as float32 / float64 .npy files (64 MB at most).  The morphologies of all blends
+    can exceed that, so they are written for a fixed, seeded sample of blends."""
+    os.makedirs(out_dir, exist_ok=True)
+    sed, morphs = batch.parameters()
+    first = np.concatenate([[0], np.cumsum(batch.n_comp_per_blend)])
+    per_blend = max(4 * sum(morphs[k].size for k in range(first[b], first[b + 1]))
+                    for b in range(batch.n_blends))
+    n_pick = min(batch.n_blends, 256, max(1, morph_budget // max(per_blend, 1)))
+    pick = np.sort(np.random.default_rng(0).choice(batch.n_blends, n_pick, replace=False))
+    out = {
+        "sed": sed.astype(np.float32),
+        "morph_sample": np.concatenate([morphs[k].ravel() for b in pick
+                                        for k in range(first[b], first[b + 1])]).astype(np.float32),
+        "morph_sample_blends": pick.astype(np.float64),
+        "center": batch.centers()["center"].astype(np.float64),
+        "loss_last": np.array([l[-1] if len(l) else np.nan for l in loss], dtype=np.float64),
+    }
+    total = sum(a.nbytes for a in out.values())
+    assert total <= 64 << 20, "outputs of %d bytes exceed 64 MB" % total
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def usable_cores():
@@ -486,7 +524,7 @@ def live_hbm_counters(nb, timeout=90):
             cmd = [prof, "--kernel-trace", "--pmc", *group, "-d", d, "-o", "run",
                    "--output-format", "csv", "--", sys.executable, os.path.abspath(__file__),
                    "--steps", "6", "--warmup", "2", "--no-cpu", "--sub-ranges", "1",
-                   "--blends", str(nb), "--no-counters"]
+                   "--blends", str(nb), "--no-counters", "--full"]
             env = dict(os.environ, TMPDIR="/tmp", GPU_MAX_HW_QUEUES="8")
             res = subprocess.run(cmd, cwd="/tmp", env=env, timeout=timeout,
                                  stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
@@ -527,6 +565,171 @@ def live_hbm_counters(nb, timeout=90):
     return out or None
 
 
+def roofline_object(args, data, comps, kernel, nb, n_total, world, K, it0, ms_iter, phases,
+                    fft_shape, conv_path, ranges_timed):
+    """``--full``: the `roofline` object of the line -- the dominant kernel of the roofline pass
+    (`phases`: mean ms per phase) against HBM bandwidth, the whole iteration against the speed of
+    light, and the HBM counters, measured in this run where possible."""
+    lite = args.loop != "blend"
+    C, H, W = data.shape[1:]
+    boxes = [c.morph.size for c in comps[0]]
+    kb = 0 if args.null_renderer else kernel.shape[-3]
+    Fy, Fx = fft_shape if not args.null_renderer else (0, 0)
+    by = algorithmic_bytes(C, H, W, boxes, Fy, Fx, kb)
+    by_survey = algorithmic_bytes(C, H, W, boxes, 180, 180, kb) if args.config == "cfg3" else by
+    bytes_per = by["null"] if args.null_renderer else by["whole"]
+    fused = conv_path == "fused"
+    k_name, k_bytes, k_ms = dominant_kernel(phases, conv_path, by)
+    # `frac` / `achieved` price the bytes the dominant kernel must move at its fusion
+    # boundary (<= 1 by construction); the SURVEY 8d byte model, whose transform passes
+    # stay in LDS here, is reported beside it as frac_survey_model
+    k_boundary = (by["conv_boundary"] if k_name == "fused_conv_kernel" else
+                  by["update_boundary"] if k_name.startswith("update") else k_bytes)
+    achieved = k_boundary * nb / (k_ms * 1e-3) / 1e9
+    achieved_model = k_bytes * nb / (k_ms * 1e-3) / 1e9
+    cnt = counters(k_name) if args.config == "cfg3" and nb == 1024 else {}
+    # HBM bytes by the PMC counters, measured in this run where that is possible (N = 1,
+    # the benchmark's own workload, the fused path); the committed summary otherwise
+    live = None
+    if (args.config == "cfg3" and world == 1 and conv_path == "fused" and not lite
+            and not args.steady and not args.no_counters):
+        live = live_hbm_counters(nb)
+    live_name = "update_kernel_reg" if k_name.startswith("update") else k_name
+    live_util = False
+    if live and live_name in live:
+        cnt = dict(cnt, **live[live_name])
+        live_util = "valu_busy" in live[live_name]
+        if live_util:
+            # the rule of tools/hbm_counters.py, on this run's own counters
+            k_ms_now = dominant_kernel(phases, conv_path, by)[2]
+            hbm_now = live[live_name]["bytes_per_blend"] * nb / (k_ms_now * 1e-3) / 1e9 / HBM_PEAK_GBS
+            cnt["bound"] = ("hbm" if hbm_now > 0.6 else
+                            "valu-issue" if cnt.get("issue_busy", 0) > 0.85 else "latency-l2-lds")
+    traffic = cnt["bytes_per_blend"] * nb if "bytes_per_blend" in cnt else None
+    # Speed of light of one iteration of this rank's shard: what cannot be avoided is the
+    # compulsory traffic B0 (data and weights once, parameters and moments once each way)
+    # at 8 TB/s, and the butterflies of the four transforms at the f32 vector peak.
+    counted = (args.config == "cfg3" and nb == 1024 and not args.null_renderer
+               and os.path.exists(os.path.join(ROOT, "profiles", "hbm_traffic.json")))
+    # every kernel of the iteration that the counter passes saw (no render_kernel since
+    # the convolution kernel renders its own model rows)
+    all_cnt = {k: counters(k) for k in ("fused_conv_kernel", "update_kernel_reg",
+                                        "render_kernel") if counters(k)} if counted else {}
+    if live:
+        all_cnt = {k: dict(v) for k, v in live.items()
+                   if k in ("fused_conv_kernel", "update_kernel_reg", "render_kernel")}
+    hbm_ms = by["null"] * nb / (HBM_PEAK_GBS * 1e9) * 1e3
+    flop_ms = (fft_flops(C, Fy, Fx) * nb / (F32_VECTOR_PEAK_TFLOPS * 1e12) * 1e3
+               if not args.null_renderer else 0.0)
+    sol_ms = max(hbm_ms, flop_ms)
+    measured_iter = (sum(c["bytes_per_blend"] for c in all_cnt.values())
+                     if all_cnt and all("bytes_per_blend" in c for c in all_cnt.values()) else None)
+    sol_frac = round(sol_ms / ms_iter, 4)
+    hbm_whole = (round(measured_iter * nb / (ms_iter * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+                 if measured_iter else None)
+    frac = round(achieved / HBM_PEAK_GBS, 5)
+    frac_model = round(achieved_model / HBM_PEAK_GBS, 5)
+    return {
+        # the roofline `achieved` / `peak` are priced against (HBM bandwidth; no MFMA work
+        # on this path), and what the PMC counters say limits the dominant kernel
+        # ("unknown" without a counter summary for this workload)
+        "bound": "hbm",
+        "limiter": cnt.get("bound") or "unknown",
+        # READ THESE FIRST.  frac_physical: share of the chip's physical limit the whole
+        # iteration reaches (speed_of_light.sol_frac); hbm_frac_whole_iteration: HBM bytes
+        # of the whole iteration by the PMC counters over ms_per_step against 8 TB/s (null
+        # without a counter summary for this workload).  `frac` further down prices SURVEY
+        # 8d's byte model for the dominant kernel and saturates (frac_note).
+        "frac_physical": sol_frac,
+        "hbm_frac_whole_iteration": hbm_whole,
+        "speed_of_light": {
+            "compulsory_bytes_per_blend_iteration": by["null"],
+            "hbm_ms": round(hbm_ms, 4),
+            "butterfly_flops_per_blend_iteration": (round(fft_flops(C, Fy, Fx))
+                                                    if not args.null_renderer else 0),
+            "valu_ms": round(flop_ms, 4),
+            "sol_ms": round(sol_ms, 4),
+            "sol_frac": sol_frac,
+            "note": "sol_ms = max(compulsory bytes / 8 TB/s, butterfly flops / 157.3 TFLOP/s) "
+                    "for this rank's %d blends; sol_frac = sol_ms / ms_per_step: the share of "
+                    "the chip's physical limit the iteration reaches.  `frac` below prices the "
+                    "SURVEY 8d byte model, most of whose bytes this design keeps in LDS." % nb,
+        },
+        "measured_hbm": {
+            "bytes_per_blend_iteration": measured_iter,
+            "over_compulsory": (round(measured_iter / by["null"], 3) if measured_iter else None),
+            "frac_of_peak": hbm_whole,
+            "per_kernel": {k: c.get("bytes_per_blend") for k, c in all_cnt.items()} or None,
+            "source": ("this run: bench.py re-run under rocprofv3 --kernel-trace --pmc FETCH_SIZE / "
+                       "WRITE_SIZE (separate passes, 6 iterations, one range of %d blends; KiB, "
+                       "FETCH_SIZE doubled for gfx950)" % nb if live else
+                       "profiles/hbm_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
+                       "passes of tools/collect_profiles.sh on 1024-blend launches "
+                       "(committed constants, not measured in this run)" if all_cnt else None),
+        },
+        "counter_fields": {
+            "fields": ([] if live_util else ["limiter", "valu_busy"] if live else
+                       ["limiter", "traffic", "hbm_frac_measured", "valu_busy", "measured_hbm"]),
+            "source": ("none: every field of this line is measured in this run (traffic, "
+                       "hbm_frac_measured, measured_hbm, valu_busy, issue_busy and the limiter by "
+                       "its own rocprofv3 --pmc passes)" if live_util else
+                       "profiles/hbm_traffic.json (committed PMC summary); every other field is "
+                       "measured in this run" + (" -- traffic, hbm_frac_measured and measured_hbm "
+                                                 "by counter passes of this run" if live else "")),
+        },
+        "achieved": round(achieved, 2),
+        "peak": HBM_PEAK_GBS,
+        "unit": "GB/s",
+        "frac": frac,
+        "frac_note": "bytes the dominant kernel must move through HBM at its fusion boundary "
+                     "(data + weights + parameters in, gradient image out for the convolution; "
+                     "parameters, moments and the gather of the gradient image for the update) "
+                     "/ launch time / 8 TB/s; the SURVEY 8d byte model is frac_survey_model",
+        # SURVEY 8d prices four FFT passes through HBM; the fused convolution keeps them
+        # in LDS and moves ~1.1 MB of the 5.05 MB per blend, so this figure sits at or
+        # above 1: it prices the survey's picture of the path, not the chip
+        "frac_survey_model": frac_model,
+        "achieved_survey_model": round(achieved_model, 2),
+        "traffic": traffic,
+        "kernel": k_name,
+        "algorithmic_bytes_per_launch": k_boundary * nb,
+        "algorithmic_bytes_per_blend": k_boundary,
+        "survey_model_bytes_per_blend": k_bytes,
+        "fft_shape_priced": [Fy, Fx],
+        "ms_per_launch": round(k_ms, 4),
+        "hbm_frac_measured": (round(traffic / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
+                              if traffic else None),
+        "valu_busy": cnt.get("valu_busy"),
+        "issue_busy": cnt.get("issue_busy"),
+        "flops_frac": (round(fft_flops(C, Fy, Fx) * nb / (k_ms * 1e-3) / 1e12
+                             / F32_VECTOR_PEAK_TFLOPS, 5)
+                       if k_name == "fused_conv_kernel" else None),
+        "measured": "HIP events on the batch stream, iterations %d..%d replayed in one "
+                    "range of %d blends per launch (the timed region runs %d range(s) "
+                    "concurrently)" % (it0 + (K if args.steady else 0),
+                                       it0 + (K if args.steady else 0) + K - 1, nb,
+                                       ranges_timed),
+        "kernels": {
+            "fused_conv_kernel": {
+                "ms": phases["conv"], "algorithmic_bytes_per_blend": by["conv"],
+                "frac": round(by["conv"] * nb / (phases["conv"] * 1e-3) / 8e12, 5)
+                if fused else None},
+            "update_kernel_reg": {
+                "ms": phases["update"], "algorithmic_bytes_per_blend": by["update"],
+                "frac": round(by["update"] * nb / (phases["update"] * 1e-3) / 8e12, 5)},
+        },
+        "whole_iteration": {
+            "algorithmic_bytes_per_blend_iteration": bytes_per,
+            "ms": round(ms_iter, 4),
+            "achieved": round(bytes_per * n_total / world / (ms_iter * 1e-3) / 1e9, 2),
+            "frac": round(bytes_per * n_total / world / (ms_iter * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+            "frac_survey_F180": round(by_survey["whole"] * n_total / world
+                                      / (ms_iter * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+        },
+        "phases_ms": phases,
+    }
+
+
 def self_launch(args):
     """`python bench.py --gpus N` outside torchrun: start N ranks of this script."""
     import torch
@@ -553,9 +756,10 @@ def main():
     ap.add_argument("--null-renderer", action="store_true", help="ablation: no PSF convolution")
     ap.add_argument("--fft", type=int, nargs=2, default=None, help="override FFT shape")
     ap.add_argument("--conv-path", default="auto", choices=["auto", "rocfft", "fused"])
-    ap.add_argument("--cpu-blends", type=int, default=12)
-    ap.add_argument("--cpu-iters", type=int, default=0, help="0 = --steps")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--cpu-blends", type=int, default=12, help="--full: CPU baseline blends")
+    ap.add_argument("--cpu-iters", type=int, default=0, help="--full: CPU baseline iterations "
+                                                              "(0 = --steps)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--steady", action="store_true",
                     help="round-1 window: time iterations W .. W+K-1 of the warmed-up fit")
     ap.add_argument("--sub-ranges", type=int, default=0,
@@ -567,13 +771,21 @@ def main():
                     help="milliseconds of untimed iterations before the warm-up (GPU clocks up "
                          "after the idle set-up; 0: none)")
     ap.add_argument("--no-counters", action="store_true",
-                    help="do not re-run under rocprofv3 for the HBM byte counters (roofline.traffic "
-                         "then comes from the committed profiles/hbm_traffic.json)")
+                    help="--full: do not re-run under rocprofv3 for the HBM byte counters "
+                         "(roofline.traffic then comes from the committed "
+                         "profiles/hbm_traffic.json)")
     ap.add_argument("--facade", action="store_true",
                     help="time scarlet_amd.fit_blends on Blend objects built from the cfg3 "
                          "scenes (resizing on) instead of the C-ABI batch")
     ap.add_argument("--profile", action="store_true", help="--facade: cProfile of the call")
+    ap.add_argument("--full", action="store_true",
+                    help="also the cold window, the oracle parity check, the roofline pass with "
+                         "its counter passes and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed iteration to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and (args.facade or args.config == "cfg5" or args.gpus != 1):
+        ap.error("--dump-outputs: the C-ABI batch (cfg3, cfg1, cfg4) on one GPU")
 
     # before the HIP runtime starts (scarlet_amd._lib explains): eight hardware queues, so that
     # a small shard can step four ranges of blends side by side
@@ -663,19 +875,20 @@ def main():
     # warm-up iterations, then the state of iteration 0 again
     cold = None
     if args.ramp_ms > 0 and not args.steady:
-        # the same protocol without the ramp first (rounds 1-5 measured this window): reported
-        # beside `value` as config.cold_window_value, never as `value`
         run(0, Wm)
         torch.cuda.synchronize()
         fresh()
-        torch.cuda.synchronize()
-        sdist.barrier()
-        t0 = time.perf_counter()
-        run(0, K)
-        torch.cuda.synchronize()
-        sdist.barrier()
-        cold = n_total * K / sdist.max_over_ranks(time.perf_counter() - t0)
-        fresh()
+        if args.full:
+            # the same protocol without the ramp first (rounds 1-5 measured this window):
+            # reported beside `value` as config.cold_window_value, never as `value`
+            torch.cuda.synchronize()
+            sdist.barrier()
+            t0 = time.perf_counter()
+            run(0, K)
+            torch.cuda.synchronize()
+            sdist.barrier()
+            cold = n_total * K / sdist.max_over_ranks(time.perf_counter() - t0)
+            fresh()
     ramp(args.ramp_ms)
     run(0, Wm)
     torch.cuda.synchronize()
@@ -701,10 +914,13 @@ def main():
     rec = sdist.gather_records(sdist.pack_records(loss, batch.states(), K))
     comm = sdist.comm_info()  # backend / world size / devices of the live process group
     assert len(rec) == n_total and np.all(rec["n_iter"] == K)
+    if args.dump_outputs:
+        dump_outputs(batch, loss, args.dump_outputs)
     # parity at the benchmark's own size: first and last blend of every rank's shard against
     # the oracle, same K iterations (checker only, after the clock has stopped)
     parity = None
-    if scenes is not None and not lite and not args.steady and not args.null_renderer:
+    if (args.full and scenes is not None and not lite and not args.steady
+            and not args.null_renderer):
         # (every rank enters the gather, a rank with an empty shard with an empty record)
         picks = sorted({0, nb - 1}) if nb else []
         early, late = oracle_check(scenes, picks, loss, K, e_rel) if picks else (0.0, 0.0)
@@ -718,178 +934,22 @@ def main():
     # streams of their own and their kernels share the chip, so the duration of a single
     # launch there says nothing about the kernel; `value` is not affected by this pass.
     ranges_timed = batch.sub_ranges()
-    if not args.steady:
-        ramp(args.ramp_ms)  # (the oracle check above left the GPU idle)
-        fresh()
-    batch.set_sub_ranges(1)
-    batch.enable_timing(True)  # HIP events around every phase, on the batch stream
-    run(it0 + (K if args.steady else 0), K)
-    torch.cuda.synchronize()
-    phases = {k: round(v, 4) for k, v in batch.timing().items()}  # mean ms over the K steps
-    batch.enable_timing(False)
+    if args.full:
+        if not args.steady:
+            ramp(args.ramp_ms)  # (the oracle check above left the GPU idle)
+            fresh()
+        batch.set_sub_ranges(1)
+        batch.enable_timing(True)  # HIP events around every phase, on the batch stream
+        run(it0 + (K if args.steady else 0), K)
+        torch.cuda.synchronize()
+        phases = {k: round(v, 4) for k, v in batch.timing().items()}  # mean ms over the K steps
+        batch.enable_timing(False)
     fft_shape = batch.fft_shape
     conv_path = batch.conv_path  # "none" | "rocfft" | "fused": what the library runs
 
     if rank == 0:
         value = n_total * K / elapsed
-        C, H, W = data.shape[1:]
-        boxes = [c.morph.size for c in comps[0]]
-        kb = 0 if args.null_renderer else kernel.shape[-3]
-        Fy, Fx = fft_shape if not args.null_renderer else (0, 0)
-        by = algorithmic_bytes(C, H, W, boxes, Fy, Fx, kb)
-        by_survey = algorithmic_bytes(C, H, W, boxes, 180, 180, kb) if args.config == "cfg3" else by
-        bytes_per = by["null"] if args.null_renderer else by["whole"]
         ms_iter = elapsed / K * 1e3
-        fused = conv_path == "fused"
-        k_name, k_bytes, k_ms = dominant_kernel(phases, conv_path, by)
-        # `frac` / `achieved` price the bytes the dominant kernel must move at its fusion
-        # boundary (<= 1 by construction); the SURVEY 8d byte model, whose transform passes
-        # stay in LDS here, is reported beside it as frac_survey_model
-        k_boundary = (by["conv_boundary"] if k_name == "fused_conv_kernel" else
-                      by["update_boundary"] if k_name.startswith("update") else k_bytes)
-        achieved = k_boundary * nb / (k_ms * 1e-3) / 1e9
-        achieved_model = k_bytes * nb / (k_ms * 1e-3) / 1e9
-        cnt = counters(k_name) if args.config == "cfg3" and nb == 1024 else {}
-        # HBM bytes by the PMC counters, measured in this run where that is possible (N = 1,
-        # the benchmark's own workload, the fused path); the committed summary otherwise
-        live = None
-        if (args.config == "cfg3" and world == 1 and conv_path == "fused" and not lite
-                and not args.steady and not args.no_counters):
-            live = live_hbm_counters(nb)
-        live_name = "update_kernel_reg" if k_name.startswith("update") else k_name
-        live_util = False
-        if live and live_name in live:
-            cnt = dict(cnt, **live[live_name])
-            live_util = "valu_busy" in live[live_name]
-            if live_util:
-                # the rule of tools/hbm_counters.py, on this run's own counters
-                k_ms_now = dominant_kernel(phases, conv_path, by)[2]
-                hbm_now = live[live_name]["bytes_per_blend"] * nb / (k_ms_now * 1e-3) / 1e9 / HBM_PEAK_GBS
-                cnt["bound"] = ("hbm" if hbm_now > 0.6 else
-                                "valu-issue" if cnt.get("issue_busy", 0) > 0.85 else "latency-l2-lds")
-        traffic = cnt["bytes_per_blend"] * nb if "bytes_per_blend" in cnt else None
-        # Speed of light of one iteration of this rank's shard: what cannot be avoided is the
-        # compulsory traffic B0 (data and weights once, parameters and moments once each way)
-        # at 8 TB/s, and the butterflies of the four transforms at the f32 vector peak.
-        counted = (args.config == "cfg3" and nb == 1024 and not args.null_renderer
-                   and os.path.exists(os.path.join(ROOT, "profiles", "hbm_traffic.json")))
-        # every kernel of the iteration that the counter passes saw (no render_kernel since
-        # the convolution kernel renders its own model rows)
-        all_cnt = {k: counters(k) for k in ("fused_conv_kernel", "update_kernel_reg",
-                                            "render_kernel") if counters(k)} if counted else {}
-        if live:
-            all_cnt = {k: dict(v) for k, v in live.items()
-                       if k in ("fused_conv_kernel", "update_kernel_reg", "render_kernel")}
-        hbm_ms = by["null"] * nb / (HBM_PEAK_GBS * 1e9) * 1e3
-        flop_ms = (fft_flops(C, Fy, Fx) * nb / (F32_VECTOR_PEAK_TFLOPS * 1e12) * 1e3
-                   if not args.null_renderer else 0.0)
-        sol_ms = max(hbm_ms, flop_ms)
-        measured_iter = (sum(c["bytes_per_blend"] for c in all_cnt.values())
-                         if all_cnt and all("bytes_per_blend" in c for c in all_cnt.values()) else None)
-        sol_frac = round(sol_ms / ms_iter, 4)
-        hbm_whole = (round(measured_iter * nb / (ms_iter * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-                     if measured_iter else None)
-        frac = round(achieved / HBM_PEAK_GBS, 5)
-        frac_model = round(achieved_model / HBM_PEAK_GBS, 5)
-        roofline = {
-            # the roofline `achieved` / `peak` are priced against (HBM bandwidth; no MFMA work
-            # on this path), and what the PMC counters say limits the dominant kernel
-            # ("unknown" without a counter summary for this workload)
-            "bound": "hbm",
-            "limiter": cnt.get("bound") or "unknown",
-            # READ THESE FIRST.  frac_physical: share of the chip's physical limit the whole
-            # iteration reaches (speed_of_light.sol_frac); hbm_frac_whole_iteration: HBM bytes
-            # of the whole iteration by the PMC counters over ms_per_step against 8 TB/s (null
-            # without a counter summary for this workload).  `frac` further down prices SURVEY
-            # 8d's byte model for the dominant kernel and saturates (frac_note).
-            "frac_physical": sol_frac,
-            "hbm_frac_whole_iteration": hbm_whole,
-            "speed_of_light": {
-                "compulsory_bytes_per_blend_iteration": by["null"],
-                "hbm_ms": round(hbm_ms, 4),
-                "butterfly_flops_per_blend_iteration": (round(fft_flops(C, Fy, Fx))
-                                                        if not args.null_renderer else 0),
-                "valu_ms": round(flop_ms, 4),
-                "sol_ms": round(sol_ms, 4),
-                "sol_frac": sol_frac,
-                "note": "sol_ms = max(compulsory bytes / 8 TB/s, butterfly flops / 157.3 TFLOP/s) "
-                        "for this rank's %d blends; sol_frac = sol_ms / ms_per_step: the share of "
-                        "the chip's physical limit the iteration reaches.  `frac` below prices the "
-                        "SURVEY 8d byte model, most of whose bytes this design keeps in LDS." % nb,
-            },
-            "measured_hbm": {
-                "bytes_per_blend_iteration": measured_iter,
-                "over_compulsory": (round(measured_iter / by["null"], 3) if measured_iter else None),
-                "frac_of_peak": hbm_whole,
-                "per_kernel": {k: c.get("bytes_per_blend") for k, c in all_cnt.items()} or None,
-                "source": ("this run: bench.py re-run under rocprofv3 --kernel-trace --pmc FETCH_SIZE / "
-                           "WRITE_SIZE (separate passes, 6 iterations, one range of %d blends; KiB, "
-                           "FETCH_SIZE doubled for gfx950)" % nb if live else
-                           "profiles/hbm_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
-                           "passes of tools/collect_profiles.sh on 1024-blend launches "
-                           "(committed constants, not measured in this run)" if all_cnt else None),
-            },
-            "counter_fields": {
-                "fields": ([] if live_util else ["limiter", "valu_busy"] if live else
-                           ["limiter", "traffic", "hbm_frac_measured", "valu_busy", "measured_hbm"]),
-                "source": ("none: every field of this line is measured in this run (traffic, "
-                           "hbm_frac_measured, measured_hbm, valu_busy, issue_busy and the limiter by "
-                           "its own rocprofv3 --pmc passes)" if live_util else
-                           "profiles/hbm_traffic.json (committed PMC summary); every other field is "
-                           "measured in this run" + (" -- traffic, hbm_frac_measured and measured_hbm "
-                                                     "by counter passes of this run" if live else "")),
-            },
-            "achieved": round(achieved, 2),
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": frac,
-            "frac_note": "bytes the dominant kernel must move through HBM at its fusion boundary "
-                         "(data + weights + parameters in, gradient image out for the convolution; "
-                         "parameters, moments and the gather of the gradient image for the update) "
-                         "/ launch time / 8 TB/s; the SURVEY 8d byte model is frac_survey_model",
-            # SURVEY 8d prices four FFT passes through HBM; the fused convolution keeps them
-            # in LDS and moves ~1.1 MB of the 5.05 MB per blend, so this figure sits at or
-            # above 1: it prices the survey's picture of the path, not the chip
-            "frac_survey_model": frac_model,
-            "achieved_survey_model": round(achieved_model, 2),
-            "traffic": traffic,
-            "kernel": k_name,
-            "algorithmic_bytes_per_launch": k_boundary * nb,
-            "algorithmic_bytes_per_blend": k_boundary,
-            "survey_model_bytes_per_blend": k_bytes,
-            "fft_shape_priced": [Fy, Fx],
-            "ms_per_launch": round(k_ms, 4),
-            "hbm_frac_measured": (round(traffic / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
-                                  if traffic else None),
-            "valu_busy": cnt.get("valu_busy"),
-            "issue_busy": cnt.get("issue_busy"),
-            "flops_frac": (round(fft_flops(C, Fy, Fx) * nb / (k_ms * 1e-3) / 1e12
-                                 / F32_VECTOR_PEAK_TFLOPS, 5)
-                           if k_name == "fused_conv_kernel" else None),
-            "measured": "HIP events on the batch stream, iterations %d..%d replayed in one "
-                        "range of %d blends per launch (the timed region runs %d range(s) "
-                        "concurrently)" % (it0 + (K if args.steady else 0),
-                                           it0 + (K if args.steady else 0) + K - 1, nb,
-                                           ranges_timed),
-            "kernels": {
-                "fused_conv_kernel": {
-                    "ms": phases["conv"], "algorithmic_bytes_per_blend": by["conv"],
-                    "frac": round(by["conv"] * nb / (phases["conv"] * 1e-3) / 8e12, 5)
-                    if fused else None},
-                "update_kernel_reg": {
-                    "ms": phases["update"], "algorithmic_bytes_per_blend": by["update"],
-                    "frac": round(by["update"] * nb / (phases["update"] * 1e-3) / 8e12, 5)},
-            },
-            "whole_iteration": {
-                "algorithmic_bytes_per_blend_iteration": bytes_per,
-                "ms": round(ms_iter, 4),
-                "achieved": round(bytes_per * n_total / world / (ms_iter * 1e-3) / 1e9, 2),
-                "frac": round(bytes_per * n_total / world / (ms_iter * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                "frac_survey_F180": round(by_survey["whole"] * n_total / world
-                                          / (ms_iter * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-            },
-            "phases_ms": phases,
-        }
         if args.config == "cfg1":
             what = ("configs[0] scene (hsc_cosmos_35: 5x58x48, 10 components, boxes 21^2..61^2, "
                     "per-band 43x43 kernel) replicated: %d blends in total" % n_total)
@@ -938,17 +998,22 @@ def main():
                                    "blend-it/s); --ramp-ms 0 measures the cold window",
                 "mean_logL": float(np.mean(rec["logL"])),
             },
-            "roofline": roofline,
-            "comm": comm,
-            "parity": ({"checked_blends": [b for p in parity for b in p["blends"]],
-                        "worst_rel_chi2_first_12_iterations": max(p["first_12"] for p in parity),
-                        "worst_rel_chi2_all_iterations": max(p["all"] for p in parity),
-                        "tolerance": [2e-5, 5e-4],
-                        "against": "CPU oracle (oracle/pgm.py), same scenes, iterations 0..%d; "
-                                   "checker only, after the timed region" % (K - 1)}
-                       if parity else None),
         }
-        if not args.no_cpu and not lite and world == 1:  # reported at N = 1 only
+        if args.full:
+            line["roofline"] = roofline_object(args, data, comps, kernel, nb, n_total, world, K,
+                                               it0, ms_iter, phases, fft_shape, conv_path,
+                                               ranges_timed)
+        line["comm"] = comm
+        if args.full:
+            line["parity"] = (
+                {"checked_blends": [b for p in parity for b in p["blends"]],
+                 "worst_rel_chi2_first_12_iterations": max(p["first_12"] for p in parity),
+                 "worst_rel_chi2_all_iterations": max(p["all"] for p in parity),
+                 "tolerance": [2e-5, 5e-4],
+                 "against": "CPU oracle (oracle/pgm.py), same scenes, iterations 0..%d; "
+                            "checker only, after the timed region" % (K - 1)}
+                if parity else None)
+        if args.full and not args.no_cpu and not lite and world == 1:  # reported at N = 1 only
             line["cpu_baseline"] = cpu_baseline(args.config, args.cpu_blends,
                                                 args.cpu_iters or K, e_rel)
             ref = os.path.join(ROOT, "profiles", "r03_reference_forward.json")

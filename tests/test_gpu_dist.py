@@ -98,6 +98,32 @@ def test_bench_starts_its_own_ranks(tmp_path):
     assert one["config"]["blends_per_gpu"] == [16]
 
 
+def test_plain_bench_run_and_its_outputs(tmp_path):
+    """`bench.py` without --full: the contract's fields for exactly --steps timed iterations,
+    none of the --full measurements, and with --dump-outputs the .npy files of the last step
+    (the loss of every blend equals the one the line's mean_logL summarises)."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+                          "--steps", "4", "--warmup", "1", "--blends", "16",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True,
+                         timeout=600)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    rows = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(rows) == 1, out.stdout
+    line = rows[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["steps"] == 4 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert not {"roofline", "parity", "cpu_baseline"} & set(line)
+    assert line["config"]["cold_window_value"] is None
+    loss = np.load(tmp_path / "loss_last.npy")
+    assert loss.dtype == np.float64 and loss.shape == (16,)
+    assert np.isclose(-loss.mean(), line["config"]["mean_logL"], rtol=1e-12)
+    sed = np.load(tmp_path / "sed.npy")
+    assert sed.dtype == np.float32 and sed.shape == (160, 5) and np.all(np.isfinite(sed))
+    morph = np.load(tmp_path / "morph_sample.npy")
+    assert morph.dtype == np.float32 and morph.size == 160 * 41 * 41
+
+
 def test_the_drivers_eight_rank_command_runs(tmp_path):
     """The command the driver uses for the scaling record -- torchrun with 8 ranks and
     ``bench.py --gpus 8`` -- on this one-GPU box: the ranks share the GPU over gloo (flagged in
@@ -105,7 +131,7 @@ def test_the_drivers_eight_rank_command_runs(tmp_path):
     job whose fit equals the single-rank run's."""
     from scarlet_amd import dist
 
-    args = ["--steps", "3", "--warmup", "1", "--blends", "64", "--no-cpu"]
+    args = ["--steps", "3", "--warmup", "1", "--blends", "64", "--no-cpu", "--full"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
            "--master-addr", "127.0.0.1", "--master-port", str(dist.free_port()),
@@ -185,8 +211,8 @@ def test_bench_measures_its_own_hbm_counters():
     if not (shutil.which("rocprofv3") or os.path.exists("/opt/rocm/bin/rocprofv3")):
         pytest.skip("no rocprofv3 on this box")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--blends", "96", "--steps",
-                          "6", "--warmup", "2", "--no-cpu"], capture_output=True, text=True,
-                         timeout=900)
+                          "6", "--warmup", "2", "--no-cpu", "--full"], capture_output=True,
+                         text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     hbm = line["roofline"]["measured_hbm"]

@@ -813,3 +813,46 @@ def test_lazy_std_survives_views_and_old_pickles():
     r.__setstate__(base[2][:-1] + (legacy,))
     assert np.allclose(r.std, 0.5)
     assert np.allclose(pickle.loads(pickle.dumps(p)).std, 0.5)
+
+
+def test_bench_dumps_the_outputs_of_its_last_step(tmp_path):
+    """``bench.py --dump-outputs``: float32 / float64 .npy files of what the timed path leaves a
+    caller (SEDs, a fixed sample of the morphologies, centres, the last loss), the morphology
+    sample the same from run to run and the whole at most 64 MB for the benchmark's batch."""
+    import importlib.util
+    import os
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class Batch:  # the BlendBatch methods dump_outputs reads, 1024 blends of 10 41^2 boxes
+        n_blends, n_comp_per_blend = 1024, [10] * 1024
+
+        def parameters(self):
+            n = sum(self.n_comp_per_blend)
+            return (np.arange(5 * n, dtype=np.float32).reshape(n, 5),
+                    [np.full((41, 41), k, dtype=np.float32) for k in range(n)])
+
+        def centers(self):
+            return {"center": np.zeros((sum(self.n_comp_per_blend), 2))}
+
+    loss = [np.arange(3.0) + b for b in range(1024)]
+    for d in ("a", "b"):
+        bench.dump_outputs(Batch(), loss, str(tmp_path / d))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["center.npy", "loss_last.npy", "morph_sample.npy",
+                     "morph_sample_blends.npy", "sed.npy"]
+    total = 0
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64)
+        assert_array_equal(a, b)
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert_array_equal(np.load(tmp_path / "a" / "loss_last.npy"), np.arange(1024) + 2.0)
+    pick = np.load(tmp_path / "a" / "morph_sample_blends.npy").astype(int)
+    assert len(pick) == 256 and np.all(np.diff(pick) > 0)
+    morph = np.load(tmp_path / "a" / "morph_sample.npy").reshape(len(pick), 10, 41 * 41)
+    assert_array_equal(morph[:, :, 0], 10 * pick[:, None] + np.arange(10))

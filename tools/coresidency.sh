@@ -13,7 +13,7 @@ run() {  # label, env..., -- bench args
     local envs=()
     while [ "$1" != "--" ]; do envs+=("$1"); shift; done
     shift
-    env "${envs[@]}" python "$R/bench.py" --no-cpu "$@" 2>/dev/null | python -c "
+    env "${envs[@]}" python "$R/bench.py" --full --no-cpu "$@" 2>/dev/null | python -c "
 import json, sys
 for l in sys.stdin:
     if l.startswith('{'):
