@@ -585,6 +585,63 @@ int smi_batch_attach_lowres(smi_batch *b, smi_resampler *r, const int32_t *chann
  * gradient / step call */
 int smi_batch_get_lowres_rendered(smi_batch *b, int32_t index, float *out);
 
+/* ------------------------------------------------------------------------- *
+ * Detection: starlet wavelets (scarlet/wavelet.py) and footprints
+ * (scarlet/detect_pybind11.cc) for scarlet/detect.py.
+ * ------------------------------------------------------------------------- */
+
+/* starlet_transform (wavelet.py:220-266) of n images [n][H][W] at once: coefficients
+ * d_coeffs[scales+1][n][H][W] in float64 whatever the input type, generation 1 or 2, bit for
+ * bit the reference's.  d_work: n*H*W doubles of scratch.  Device pointers; the work is
+ * enqueued on `stream` (hipStream_t, NULL = default stream) and not waited for. */
+int smi_starlet_transform_f32(const float *d_images, int32_t n, int32_t H, int32_t W,
+                              int32_t scales, int32_t generation, double *d_coeffs,
+                              double *d_work, void *stream);
+int smi_starlet_transform_f64(const double *d_images, int32_t n, int32_t H, int32_t W,
+                              int32_t scales, int32_t generation, double *d_coeffs,
+                              double *d_work, void *stream);
+/* starlet_reconstruction (wavelet.py:284-311) of n images: d_coeffs[scales+1][n][H][W] ->
+ * d_image[n][H][W]; d_work as above (generation 2 only). */
+int smi_starlet_reconstruction_f64(const double *d_coeffs, int32_t n, int32_t H, int32_t W,
+                                   int32_t scales, int32_t generation, double *d_image,
+                                   double *d_work, void *stream);
+/* get_multiresolution_support, "ground" branch (wavelet.py:381-407), for n independent
+ * images of `planes` coefficient planes each: plane k of image b starts at
+ * d_coeffs + k*plane_stride + b*image_stride (elements) and holds H*W pixels.  Host arrays
+ * [n][planes]: sigma0 = the initial sigma_j, thresh0 = K*sigma_j of the first iteration (both
+ * as the caller's dtype rounded them).  Later iterations use K*sigma_j, sigma_j = the standard
+ * deviation of w*(|w| <= K sigma_j) over the plane, until every non-zero sigma_j moved by less
+ * than epsilon (relative) or after max_iter iterations.  Outputs in the layout of d_coeffs
+ * (either may be NULL): d_support = M (0/1), d_masked = M*w; iterations[n] (host, may be
+ * NULL) = iterations run.  Returns when the outputs are complete. */
+int smi_multiresolution_support_f64(const double *d_coeffs, int32_t n, int32_t planes,
+                                    int32_t H, int32_t W, int64_t plane_stride,
+                                    int64_t image_stride, const double *sigma0,
+                                    const double *thresh0, double K, double epsilon,
+                                    int32_t max_iter, int32_t *d_support, double *d_masked,
+                                    int32_t *iterations, void *stream);
+/* np.sum(images, axis=0) of bands [bands][H][W] -> d_out[H][W], summed in band order in the
+ * images' own type (get_detect_wavelets, detect.py:386). */
+int smi_coadd_f32(const float *d_images, int32_t bands, int32_t H, int32_t W, float *d_out,
+                  void *stream);
+int smi_coadd_f64(const double *d_images, int32_t bands, int32_t H, int32_t W, double *d_out,
+                  void *stream);
+
+/* get_footprints (detect_pybind11.cc) on the host, in two calls.  The first finds the
+ * footprints of image[H][W] -- 4-connected pixels > thresh, seeds in raster order, kept when
+ * the box has more than min_area pixels and the footprint at least min_area -- with their
+ * peaks, keeps them for the calling thread and returns counts[3] = (footprints, mask bytes,
+ * peaks).  smi_footprints_fetch then copies them out and forgets them: bounds[n][4] =
+ * (y0, y1, x0, x1) inclusive, masks = the footprints' (y1-y0+1) x (x1-x0+1) byte masks one
+ * after another, peak_start[n+1] = first peak of every footprint, peak_yx[peaks][2] and
+ * peak_flux[peaks], brightest first (ties in raster order).  No GPU needed. */
+int smi_get_footprints_f32(const float *image, int32_t H, int32_t W, double min_separation,
+                           int32_t min_area, int32_t thresh, int32_t *counts);
+int smi_get_footprints_f64(const double *image, int32_t H, int32_t W, double min_separation,
+                           int32_t min_area, int32_t thresh, int32_t *counts);
+int smi_footprints_fetch(int32_t *bounds, uint8_t *masks, int32_t *peak_start, int32_t *peak_yx,
+                         double *peak_flux);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,7 +58,8 @@ from .source import (  # noqa: F401
     PointSource,
 )
 from .model import Model, UpdateException  # noqa: F401
-from . import fft, initialization, measure, operator, synthetic  # noqa: F401
+from .wavelet import Starlet  # noqa: F401
+from . import detect, fft, initialization, measure, operator, synthetic, wavelet  # noqa: F401
 from ._lib import configure  # noqa: F401
 
 __version__ = "0.1.0"

@@ -218,6 +218,48 @@ SYMBOLS = {
     "smi_batch_set_round": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p]),
     "smi_batch_get_round": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p]),
     "smi_batch_get_progress": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p]),
+    "smi_starlet_transform_f32": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "smi_starlet_transform_f64": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "smi_starlet_reconstruction_f64": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "smi_multiresolution_support_f64": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_int64, ctypes.c_int64, c_f64p, c_f64p, ctypes.c_double, ctypes.c_double,
+         ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, c_i32p, ctypes.c_void_p],
+    ),
+    "smi_coadd_f32": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+         ctypes.c_void_p],
+    ),
+    "smi_coadd_f64": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+         ctypes.c_void_p],
+    ),
+    "smi_get_footprints_f32": (
+        ctypes.c_int,
+        [c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
+         ctypes.c_int32, c_i32p],
+    ),
+    "smi_get_footprints_f64": (
+        ctypes.c_int,
+        [c_f64p, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
+         ctypes.c_int32, c_i32p],
+    ),
+    "smi_footprints_fetch": (ctypes.c_int, [c_i32p, c_u8p, c_i32p, c_i32p, c_f64p]),
 }
 
 _lib = None

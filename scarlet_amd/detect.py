@@ -1,0 +1,222 @@
+"""Source detection on starlet coefficients (reference scarlet/detect.py).
+
+The wavelet stages -- the coadd of the bands, the starlet transform and the multiresolution
+support -- run on the GPU in one device-resident chain; footprints and peaks are found on the
+host (``detect_pybind11``), and the structures that connect them across scales are plain
+Python over ``Box``es, as in the reference.  ``QuadTreeRegion.query`` returns a ``set`` as the
+reference does, so the order in which ``get_peaks`` lists the peaks is the reference's.
+Display helpers (``draw_*``, matplotlib) are not part of this package.
+"""
+
+import numpy as np
+
+from .bbox import Box, overlapped_slices
+from .detect_pybind11 import get_footprints
+from . import wavelet
+
+
+def bounds_to_bbox(bounds):
+    """Box of the inclusive bounds ``(bottom, top, left, right)`` of a footprint."""
+    return Box((bounds[1] + 1 - bounds[0], bounds[3] + 1 - bounds[2]),
+               origin=(bounds[0], bounds[2]))
+
+
+def box_intersect(box1, box2):
+    """True when the two boxes overlap."""
+    overlap = box1 & box2
+    return overlap.shape[0] != 0 and overlap.shape[1] != 0
+
+
+def footprint_intersect(footprint1, box1, footprint2, box2):
+    """True when the two footprint masks (in boxes ``box1``, ``box2``) share a pixel."""
+    if not box_intersect(box1, box2):
+        return False
+    s1, s2 = overlapped_slices(box1, box2)
+    return np.sum(footprint1[s1] * footprint2[s2]) > 0
+
+
+class QuadTreeRegion:
+    """A quad tree of boxes: a region holds up to ``capacity - 1`` boxes, then splits into
+    four sub-regions, each receiving every box that overlaps it."""
+
+    def __init__(self, bbox, capacity=5, sub_regions=None, boxes=None, depth=0, detect=None):
+        self.bbox = bbox
+        self.sub_regions = sub_regions
+        self.boxes = [] if boxes is None else boxes
+        self.capacity = capacity
+        self.depth = depth
+        self.detect = detect
+
+    def footprint_image(self, bbox=None):
+        """Sum of the masks of all footprints in the tree, in ``bbox`` (default: the union of
+        their boxes)."""
+        boxes = self.query(self.bbox)
+        if bbox is None:
+            bbox = Box((0, 0))
+            for box in boxes:
+                bbox = bbox | box
+        image = np.zeros(bbox.shape)
+        for box in boxes:
+            full, local = overlapped_slices(bbox, box)
+            image[full] += box.footprint.footprint[local]
+        return image
+
+    @property
+    def peaks(self):
+        """All peaks of the footprints in the tree."""
+        for box in self.query(self.bbox):
+            yield from box.footprint.peaks
+
+    def add(self, other_box):
+        """Insert a box (it goes to every sub-region it overlaps)."""
+        if not box_intersect(self.bbox, other_box):
+            return
+        if self.sub_regions is not None:
+            self._add_to_sub_regions(other_box)
+            return
+        if self.boxes is None:
+            self.boxes = []
+        if len(self.boxes) < self.capacity - 1:
+            self.boxes.append(other_box)
+        else:
+            self.split()
+            self.boxes = None
+            self._add_to_sub_regions(other_box)
+
+    def add_footprints(self, footprints):
+        """Insert the bounding box of each footprint (the box carries it as ``.footprint``)."""
+        for fp in footprints:
+            box = bounds_to_bbox(fp.bounds)
+            box.footprint = fp
+            self.add(box)
+        return self
+
+    def split(self):
+        """Divide the region into four: top-left, bottom-left, top-right, bottom-right."""
+        height, width = self.bbox.shape
+        h2, w2 = height // 2, width // 2
+        y, x = self.bbox.origin
+        quads = (((h2, w2), (y, x)), ((height - h2, w2), (y + h2, x)),
+                 ((h2, width - w2), (y, x + w2)), ((height - h2, width - w2), (y + h2, x + w2)))
+        self.sub_regions = [QuadTreeRegion(Box(shape, origin), capacity=self.capacity,
+                                           depth=self.depth + 1) for shape, origin in quads]
+        for box in self.boxes:
+            self._add_to_sub_regions(box)
+
+    def _add_to_sub_regions(self, other_box):
+        for region in self.sub_regions:
+            region.add(other_box)
+
+    def query(self, other_box=None):
+        """The ``set`` of boxes in the tree that overlap ``other_box`` (default: the region)."""
+        if other_box is None:
+            other_box = self.bbox
+        if self.boxes is not None:
+            return set(box for box in self.boxes if box_intersect(box, other_box))
+        found = set()
+        if self.sub_regions is not None:
+            for region in self.sub_regions:
+                if box_intersect(region.bbox, other_box):
+                    found |= region.query(other_box)
+        return found
+
+
+class SingleScaleStructure:
+    """A footprint at one wavelet scale and the peaks, per scale, of the footprints at other
+    scales that overlap its box."""
+
+    def __init__(self, scale, footprint):
+        self.scale = scale
+        self.footprint = footprint
+        self.bbox = bounds_to_bbox(footprint.bounds)
+        self.peaks = {scale: footprint.peaks}
+        self._all_peaks = None
+
+    def add_footprint(self, scale, footprint):
+        """Add the peaks of ``footprint`` at ``scale``."""
+        self.peaks[scale] = self.peaks.get(scale, []) + list(footprint.peaks)
+        self._all_peaks = None
+
+    def add_scale_tree(self, scale, tree):
+        """Add every footprint of ``tree`` (at ``scale``) whose box overlaps this one."""
+        for box in tree.query(self.bbox):
+            self.add_footprint(scale, box.footprint)
+        return self
+
+    @property
+    def all_peaks(self):
+        """``set`` of ``(x, y)`` of the peaks at all scales."""
+        if self._all_peaks is None:
+            self._all_peaks = set((p.x, p.y) for peaks in self.peaks.values() for p in peaks)
+        return self._all_peaks
+
+
+def get_wavelets(images, variance, scales=3):
+    """Significant starlet coefficients ``M * w`` of every band, shape
+    ``(bands, scales+1, Ny, Nx)`` (as the reference's code returns them; its docstring names
+    the axes the other way round).  Band ``b`` uses ``sigma = median(sqrt(variance[b]))``.
+    All bands are transformed in one batch and their supports found together on the
+    device."""
+    images = np.asarray(images)
+    sigma = np.median(np.sqrt(variance), axis=(1, 2))
+    scales = wavelet.get_scales(images.shape, scales)
+    d_coeffs = wavelet.transform_device(wavelet._upload(images), scales)
+    P = scales + 1
+    s0, t0 = zip(*(wavelet.initial_sigma(images[b].dtype, P, sigma[b], 3)
+                   for b in range(len(images))))
+    _, Mw, _ = wavelet.support_device(d_coeffs, np.stack(s0), np.stack(t0), 3, 1e-1, 20)
+    return Mw.transpose(0, 1).contiguous().cpu().numpy()
+
+
+def get_detect_wavelets(images, variance, scales=3):
+    """Significant starlet coefficients ``(scales+1, Ny, Nx)`` of the coadd
+    ``np.sum(images, axis=0)``, with ``sigma = median(sqrt(variance))``: coadd, transform and
+    support on the device, one copy of the result to the host."""
+    images = np.asarray(images)
+    sigma = np.median(np.sqrt(variance))
+    detect = wavelet.coadd_device(wavelet._upload(images))
+    scales = wavelet.get_scales(detect.shape, scales)
+    d_coeffs = wavelet.transform_device(detect[None], scales)
+    dtype = np.float32 if images.dtype == np.float32 else np.float64
+    s0, t0 = wavelet.initial_sigma(dtype, scales + 1, sigma, 3)
+    _, Mw, _ = wavelet.support_device(d_coeffs, s0[None], t0[None], 3, 1e-1, 20)
+    return Mw[:, 0].cpu().numpy()
+
+
+def _scale_footprints(detect):
+    return [get_footprints(plane, min_separation=0, min_area=4, thresh=0) for plane in detect[:-1]]
+
+
+def get_blend_trees(detect):
+    """Quad tree and footprints of every wavelet scale but the last of ``detect``
+    ``(scales+1, Ny, Nx)``.  Returns ``(trees, all_footprints)``."""
+    all_footprints = _scale_footprints(detect)
+    trees = [QuadTreeRegion(Box(detect.shape[-2:]), capacity=10).add_footprints(fps)
+             for fps in all_footprints]
+    return trees, all_footprints
+
+
+def get_blend_structures(detect):
+    """Structures of the third wavelet scale, each with the overlapping footprints of the first
+    two scales, and the quad tree of the second scale.  Returns
+    ``(high_structures, middle_tree)`` (the reference's effective definition)."""
+    all_footprints = _scale_footprints(detect)
+    low, middle = all_footprints[:2]
+    low_tree = QuadTreeRegion(Box(detect.shape[-2:]), capacity=10).add_footprints(low)
+    middle_tree = QuadTreeRegion(Box(detect.shape[-2:]), capacity=10).add_footprints(middle)
+    structures = [SingleScaleStructure(2, fp).add_scale_tree(0, low_tree)
+                  .add_scale_tree(1, middle_tree) for fp in all_footprints[2]]
+    return structures, middle_tree
+
+
+def get_peaks(detect=None, images=None, variance=None, bbox=None, scales=3):
+    """``(y, x)`` of the peaks of the second wavelet scale, in the order of the middle tree's
+    query.  Without ``detect``, ``images``, ``variance`` and ``bbox`` are needed and the
+    detection coefficients come from ``get_detect_wavelets(images, variance, scales=3)``."""
+    if detect is None:
+        if images is None or variance is None or bbox is None:
+            raise ValueError("Must pass either 'detect' or 'images' and 'variance' and 'bbox'")
+        detect = get_detect_wavelets(images, variance, scales=3)
+    bbox = Box(detect.shape[1:]) if bbox is None else bbox[1:]
+    _, tree = get_blend_structures(detect)
+    return [(peak.y, peak.x) for box in tree.query(bbox) for peak in box.footprint.peaks]

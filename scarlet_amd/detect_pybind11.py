@@ -1,0 +1,146 @@
+"""Footprints and peaks: drop-in for the reference's compiled ``scarlet.detect_pybind11``.
+
+``get_footprints`` runs in the library (``csrc/detect.cpp``, host code: a labelling pass
+with a branch at every pixel); ``get_connected_pixels`` and ``get_peaks`` are the
+single-footprint helpers of the same module, here in NumPy.
+
+Where the reference's behaviour is undefined, this module defines it: equal-flux peaks keep
+raster order (a stable sort), ``min_separation > 0`` keeps peaks brightest first and drops
+every later one closer than that to a kept peak, a footprint without a strict maximum keeps an
+empty peak list (the reference asserts), and large footprints do not overflow a stack (the
+reference's fill is recursive).
+"""
+
+import ctypes
+
+import numpy as np
+
+from . import _lib
+
+
+class Peak:
+    """A local maximum of a footprint: pixel ``(y, x)`` in the full image and its flux."""
+
+    def __init__(self, y, x, flux):
+        self._y, self._x, self._flux = int(y), int(x), float(flux)
+
+    @property
+    def y(self):
+        return self._y
+
+    @property
+    def x(self):
+        return self._x
+
+    @property
+    def flux(self):
+        return self._flux
+
+    def __repr__(self):
+        return "Peak(y={}, x={}, flux={!r})".format(self._y, self._x, self._flux)
+
+
+class Footprint:
+    """A connected set of pixels: ``footprint`` (bool mask of its bounding box), ``peaks``
+    (brightest first) and ``bounds`` = ``(y0, y1, x0, x1)``, inclusive."""
+
+    def __init__(self, footprint, peaks, bounds):
+        self._footprint = np.asarray(footprint, dtype=bool)
+        self.peaks = list(peaks)
+        self._bounds = np.asarray(bounds, dtype=np.int32)
+
+    @property
+    def footprint(self):
+        return self._footprint
+
+    @property
+    def bounds(self):
+        return self._bounds
+
+
+def get_footprints(image, min_separation, min_area, thresh):
+    """All footprints of the 2-D ``image``: 4-connected pixels ``> int(thresh)`` (the
+    reference's threshold is an ``int``), seeds in raster order, kept when the bounding box
+    has more than ``min_area`` pixels and the footprint at least ``min_area``; peaks as in
+    :func:`get_peaks` on the box with the pixels outside the footprint set to 0."""
+    image = np.asarray(image)
+    if image.ndim != 2:
+        raise ValueError("get_footprints: a 2-D image is needed, got shape %s" % (image.shape,))
+    lib = _lib.load()
+    if image.dtype == np.float32:
+        img, fn, ct = np.ascontiguousarray(image), lib.smi_get_footprints_f32, ctypes.c_float
+    else:
+        img = np.ascontiguousarray(image, dtype=np.float64)
+        fn, ct = lib.smi_get_footprints_f64, ctypes.c_double
+    counts = np.zeros(3, dtype=np.int32)
+    _lib.check(fn(_lib.ptr(img, ct), img.shape[0], img.shape[1], float(min_separation),
+                  int(min_area), int(thresh), _lib.ptr(counts, ctypes.c_int32)))
+    n, n_mask, n_peaks = (int(v) for v in counts)
+    bounds = np.zeros((n, 4), dtype=np.int32)
+    masks = np.zeros(n_mask, dtype=np.uint8)
+    start = np.zeros(n + 1, dtype=np.int32)
+    yx = np.zeros((n_peaks, 2), dtype=np.int32)
+    flux = np.zeros(n_peaks, dtype=np.float64)
+    _lib.check(lib.smi_footprints_fetch(
+        _lib.ptr(bounds, ctypes.c_int32), _lib.ptr(masks, ctypes.c_uint8),
+        _lib.ptr(start, ctypes.c_int32), _lib.ptr(yx, ctypes.c_int32),
+        _lib.ptr(flux, ctypes.c_double)))
+    footprints = []
+    offset = 0
+    for f in range(n):
+        y0, y1, x0, x1 = (int(v) for v in bounds[f])
+        h, w = y1 - y0 + 1, x1 - x0 + 1
+        mask = masks[offset:offset + h * w].reshape(h, w).astype(bool)
+        offset += h * w
+        peaks = [Peak(yx[k, 0], yx[k, 1], flux[k]) for k in range(start[f], start[f + 1])]
+        footprints.append(Footprint(mask, peaks, bounds[f]))
+    return footprints
+
+
+def get_connected_pixels(i, j, image, unchecked, footprint, bounds, thresh=0):
+    """Mark in ``footprint`` the pixels 4-connected to ``(i, j)`` with ``image > thresh`` and
+    grow ``bounds`` = ``[y0, y1, x0, x1]`` over them.  ``unchecked`` (bool) is cleared for
+    every pixel visited, as in the reference; all three arrays are updated in place."""
+    height, width = image.shape
+    stack = [(i, j)]
+    while stack:
+        y, x = stack.pop()
+        if not unchecked[y, x]:
+            continue
+        unchecked[y, x] = False
+        if not image[y, x] > thresh:
+            continue
+        footprint[y, x] = True
+        bounds[0] = min(bounds[0], y)
+        bounds[1] = max(bounds[1], y)
+        bounds[2] = min(bounds[2], x)
+        bounds[3] = max(bounds[3], x)
+        for a, b in ((y - 1, x), (y + 1, x), (y, x - 1), (y, x + 1)):
+            if 0 <= a < height and 0 <= b < width and unchecked[a, b]:
+                stack.append((a, b))
+
+
+def get_peaks(image, min_separation, y0, x0):
+    """Strict local maxima of ``image`` over their existing 8 neighbours, as ``Peak``s at
+    ``(y + y0, x + x0)``, brightest first (ties in raster order); with
+    ``min_separation > 0`` a peak closer than that to a brighter kept peak is dropped."""
+    image = np.asarray(image)
+    h, w = image.shape
+    pad = np.full((h + 2, w + 2), -np.inf)
+    pad[1:-1, 1:-1] = image
+    is_peak = np.ones((h, w), dtype=bool)
+    for dy in (-1, 0, 1):
+        for dx in (-1, 0, 1):
+            if dy or dx:
+                is_peak &= image > pad[1 + dy:1 + dy + h, 1 + dx:1 + dx + w]
+    ys, xs = np.nonzero(is_peak)
+    flux = image[ys, xs].astype(np.float64)
+    order = np.argsort(-flux, kind="stable")
+    kept = []
+    min2 = float(min_separation) ** 2
+    for k in order:
+        y, x = int(ys[k]) + y0, int(xs[k]) + x0
+        if min_separation > 0 and any((p.y - y) ** 2 + (p.x - x) ** 2 < min2 for p in kept):
+            continue
+        kept.append(Peak(y, x, flux[k]))
+    return kept

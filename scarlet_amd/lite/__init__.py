@@ -5,11 +5,14 @@ from .initialization import (  # noqa: F401
     get_min_psf,
     init_adaprox_component,
     init_all_sources_main,
+    init_all_sources_wavelets,
     init_fista_component,
     init_main_parameters,
     init_monotonic_morph,
+    init_wavelet_source,
     multifit_seds,
     parameterize_sources,
+    WaveletInitParameters,
 )
 from .measure import calculate_snr, weight_sources  # noqa: F401
 from .models import (  # noqa: F401

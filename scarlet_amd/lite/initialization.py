@@ -3,8 +3,8 @@
 
 ``init_all_sources_main`` (lite/initialization.py:321-419) is provided with both
 monotonicity variants (weighted sweep, or ``use_mask=True``: the monotonic mask operators);
-the wavelet initialisation (``init_all_sources_wavelets``) needs the starlet transform and
-is not part of this package.
+``init_all_sources_wavelets`` (lite/initialization.py:422-605) starts from the detection
+coefficients of ``scarlet_amd.detect.get_detect_wavelets`` (starlet transform on the GPU).
 """
 
 from functools import partial
@@ -12,6 +12,7 @@ from functools import partial
 import numpy as np
 
 from ..bbox import Box, overlapped_slices
+from ..detect import get_detect_wavelets
 from ..initialization import trim_morphology
 from ..operator import prox_monotonic_mask, prox_uncentered_symmetry, prox_weighted_monotonic
 from ..parameter import relative_step
@@ -175,6 +176,97 @@ def init_fista_component(center, bbox, sed, morph, observation, bg_thresh=None):
     return LiteFactorizedComponent(FistaParameter(sed, step=step), FistaParameter(morph, step=step),
                                    center, bbox, observation.bbox, observation.noise_rms,
                                    bg_thresh=bg_thresh)
+
+
+class WaveletInitParameters:
+    """What every source of one wavelet initialisation shares: the positive detection
+    coefficients summed over all scales but the last (``detectlets``), over ``bulge_slice``
+    and over ``disk_slice``, the observation convolved with ``detectlets`` and the spectrum of
+    the model PSF.  See ``init_all_sources_wavelets`` for the parameters."""
+
+    def __init__(self, observation, bulge_slice=slice(None, 2), disk_slice=slice(2, -1),
+                 bulge_grow=5, disk_grow=5, use_psf=True, scales=5, wavelets=None):
+        if wavelets is None:
+            wavelets = get_detect_wavelets(observation.images, observation.variance,
+                                           scales=scales)
+        wavelets[wavelets < 0] = 0
+        self.detectlets = np.sum(wavelets[:-1], axis=0)
+        self.bulgelets = np.sum(wavelets[bulge_slice], axis=0)
+        self.disklets = np.sum(wavelets[disk_slice], axis=0)
+        bands = observation.shape[0]
+        model_psf = observation.model_psf[0]
+        self.convolved = observation.convolve(np.repeat(self.detectlets[None], bands, axis=0),
+                                              mode="real")
+        self.py = observation.model_psf.shape[1] // 2
+        self.px = observation.model_psf.shape[2] // 2
+        self.psf_sed = observation.convolve(np.repeat(model_psf[None], bands, axis=0),
+                                            mode="real")[:, self.py, self.px]
+        self.observation = observation
+        self.images = observation.images
+        self.bulge_grow = bulge_grow
+        self.disk_grow = disk_grow
+        self.use_psf = use_psf
+
+
+def init_wavelet_source(center, nbr_components, init):
+    """One ``LiteSource`` at ``center`` from the wavelet coefficients in ``init``
+    (``WaveletInitParameters``): the model PSF when ``nbr_components < 1`` (and
+    ``init.use_psf``) or when nothing is detected at the centre; one monotonic component for
+    ``nbr_components < 2``; otherwise a bulge and a disk component, falling back to one
+    component if either is empty.  As in the reference, the result is an empty source when the
+    single component vanishes and None when neither bulge nor disk is found."""
+    obs = init.observation
+    spec_box = obs.bbox[0]
+    at_center = (slice(None), center[0], center[1])
+    if (nbr_components < 1 and init.use_psf) or init.detectlets[center[0], center[1]] <= 0:
+        model_psf = obs.model_psf[0]
+        sed = init.images[at_center] / init.psf_sed
+        sed[sed < 0] = 0
+        bbox = Box(model_psf.shape, origin=(center[0] - init.py, center[1] - init.px))
+        return LiteSource([LiteComponent(center, spec_box @ bbox, sed,
+                                         model_psf / np.max(model_psf))], obs.dtype)
+    if nbr_components < 2:
+        bbox, morph = init_monotonic_morph(init.detectlets, center, obs.bbox[1:],
+                                           init.disk_grow)
+        if morph is None or np.max(morph) <= 0:
+            return LiteSource([], obs.dtype)
+        sed = init.images[at_center] / init.convolved[at_center]
+        sed[sed < 0] = 0
+        return LiteSource([LiteComponent(center, spec_box @ bbox, sed, morph / np.max(morph))],
+                          obs.dtype)
+    bulge_box, bulge = init_monotonic_morph(init.bulgelets, center, obs.bbox[1:],
+                                            init.bulge_grow)
+    disk_box, disk = init_monotonic_morph(init.disklets, center, obs.bbox[1:], init.disk_grow)
+    if bulge is None and disk is None:
+        return None
+    if bulge is None or disk is None:
+        return init_wavelet_source(center, 1, init)
+    bulge_sed, disk_sed = multifit_seds(obs, [bulge, disk], [bulge_box, disk_box])
+    comps = []
+    # (the reference tests the bulge by its count of non-zero entries, the disk by its sum)
+    if np.count_nonzero(bulge_sed):
+        comps.append(LiteComponent(center, spec_box @ bulge_box, bulge_sed, bulge))
+    if np.sum(disk_sed) != 0:
+        comps.append(LiteComponent(center, spec_box @ disk_box, disk_sed, disk))
+    return LiteSource(comps, obs.dtype)
+
+
+def init_all_sources_wavelets(observation, centers, min_snr=50, bulge_grow=5, disk_grow=5,
+                              use_psf=True, bulge_slice=slice(None, 2), disk_slice=slice(2, -1),
+                              scales=5, wavelets=None):
+    """One source per centre from wavelet detection images (lite/initialization.py:568-605):
+    the number of components is ``floor(SNR) / min_snr`` (PSF below 1, one component below 2,
+    bulge and disk above).  ``wavelets``: detection coefficients ``(scales+1, Ny, Nx)``,
+    default ``get_detect_wavelets(images, variance, scales)``.  Wrap the result with
+    ``parameterize_sources`` before fitting."""
+    init = WaveletInitParameters(observation, bulge_slice, disk_slice, bulge_grow, disk_grow,
+                                 use_psf, scales, wavelets)
+    sources = []
+    for center in centers:
+        snr = np.floor(calculate_snr(observation.images, observation.variance, observation.psfs,
+                                     center))
+        sources.append(init_wavelet_source(center, snr / min_snr, init))
+    return sources
 
 
 def parameterize_sources(sources, observation, parameterization):
