@@ -542,6 +542,25 @@ int64_t smi_observation_uploads(void);
  * 0 none (NullRenderer, no difference kernel), 1 rocFFT pipeline, 2 fused_conv_kernel. */
 int smi_batch_conv_path_used(smi_batch *b, int32_t *path);
 
+/* Ragged frames: blend b's frame is the corner [0, h[b]) x [0, w[b]) of its [C][H][W] plane
+ * (1 <= h[b] <= H, 1 <= w[b] <= W); component origins stay relative to that corner.  Every
+ * kernel clips components to the blend's own extent instead of H x W: nothing is rendered
+ * beyond it, and no gradient flows back from beyond it (lite/models.py:206-216).  The caller
+ * pads data and weights beyond the extent (weights 0, data finite).  h = w = NULL gives every
+ * blend the full frame again.  Not combined with shifting components, point sources,
+ * smi_batch_set_kernel_shift, smi_batch_attach_lowres, smi_batch_add_observation or
+ * smi_batch_resize_test: those calls, and this one after them, return an error. */
+int smi_batch_set_frame_extents(smi_batch *b, const int32_t *h, const int32_t *w);
+
+/* The FFT shape smi_batch_create picks for a desc with fft_h = fft_w = 0 and these sizes
+ * (host only, no GPU): the fused kernel's shape (fused_conv_choose) or, on the rocFFT path, the
+ * reference rule fft.py:116-167; (H, W) for kernel_h = kernel_w = 0.  conv_path as in
+ * smi_batch_desc (2: an error if the fused kernel cannot take the frame).  A rocFFT batch created
+ * while a batch of the transposed complex shape is alive on its device steps aside to a larger
+ * Fy (see smi_batch_create); this query does not know about live batches. */
+int smi_fft_shape_for(int32_t H, int32_t W, int32_t kernel_h, int32_t kernel_w, int32_t conv_path,
+                      int32_t *Fy, int32_t *Fx);
+
 /* ---------------------------------------------------------------------------------
  * Multi-resolution rendering: the per-call part of ResolutionRenderer
  * (renderer.py:478-545) for unrotated pixel grids.  The host builds the two linear

@@ -82,6 +82,20 @@ class PointSourceSpec(ComponentSpec):
                          prox_flags=_lib.COMPONENT_POINT_SOURCE)
 
 
+def fft_shape_for(H, W, kernel_shape, conv_path="auto"):
+    """The FFT shape ``(Fy, Fx)`` a ``BlendBatch`` of frame ``(H, W)`` and difference-kernel
+    stamp ``kernel_shape`` (``(p, q)``, or ``None`` for the NullRenderer) gets without an
+    explicit ``fft_shape`` (``smi_fft_shape_for``; no GPU needed).  ``conv_path`` as for
+    ``BlendBatch``; "fused" raises if the fused kernel cannot take the frame."""
+    lib = _lib.load()
+    kh, kw = (0, 0) if kernel_shape is None else (int(kernel_shape[-2]), int(kernel_shape[-1]))
+    fy, fx = ctypes.c_int32(), ctypes.c_int32()
+    _lib.check(lib.smi_fft_shape_for(int(H), int(W), kh, kw,
+                                     {"auto": 0, "rocfft": 1, "fused": 2}[conv_path],
+                                     ctypes.byref(fy), ctypes.byref(fx)))
+    return fy.value, fx.value
+
+
 class BlendBatch:
     """A batch of blends sharing the frame shape ``(C, H, W)``.
 
@@ -103,10 +117,15 @@ class BlendBatch:
         needs ``fista_step``)
     log_norm: include the normalisation term of ``Observation.log_norm`` in the loss
         (False = scarlet.lite's loss, lite/models.py:541)
+    frame_shapes: ``None`` or one ``(h, w)`` per blend: blend b's frame is the corner
+        ``[:h, :w]`` of its ``(H, W)`` plane and its components are clipped to it (ragged
+        frames in one batch; ``smi_batch_set_frame_extents``).  Pad data and weights beyond
+        it with finite values and weight 0.
     """
 
     def __init__(self, data, weights, components, kernel=None, max_iter=200,
-                 fft_shape=None, device=0, conv_path="auto", scheme="amsgrad", log_norm=True):
+                 fft_shape=None, device=0, conv_path="auto", scheme="amsgrad", log_norm=True,
+                 frame_shapes=None):
         lib = _lib.load()
         self._lib = lib
         self._h = ctypes.c_void_p()
@@ -154,6 +173,22 @@ class BlendBatch:
         self._kernel_shape = None if kernel is None else kernel.shape
         if kernel is not None:
             _lib.check(lib.smi_batch_set_kernel(self._h, _lib.ptr(kernel, ctypes.c_float)))
+        self.frame_shapes = None
+        if frame_shapes is not None:
+            self.set_frame_extents(frame_shapes)
+
+    def set_frame_extents(self, frame_shapes):
+        """One ``(h, w)`` per blend with ``1 <= h <= H``, ``1 <= w <= W``, or ``None`` for
+        the full frame everywhere (``smi_batch_set_frame_extents``)."""
+        if frame_shapes is None:
+            _lib.check(self._lib.smi_batch_set_frame_extents(self._h, None, None))
+            self.frame_shapes = None
+            return
+        hw = np.asarray(frame_shapes, dtype=np.int32).reshape(self.n_blends, 2)
+        h, w = _lib.i32(hw[:, 0]), _lib.i32(hw[:, 1])
+        _lib.check(self._lib.smi_batch_set_frame_extents(
+            self._h, _lib.ptr(h, ctypes.c_int32), _lib.ptr(w, ctypes.c_int32)))
+        self.frame_shapes = [tuple(int(x) for x in r) for r in hw]
 
     # -- component tables ---------------------------------------------------
     def _pack_components(self, flat, values=True, rows=None):

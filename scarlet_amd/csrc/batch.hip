@@ -275,6 +275,7 @@ struct smi_batch {
     // per blend
     int32_t *state = nullptr, *zero_state = nullptr, *n_loss = nullptr, *status_out = nullptr;
     int32_t *it_base = nullptr;  // BatchView::it_base (smi_batch_set_iteration_base)
+    int32_t *frame_hw = nullptr;  // BatchView::frame_hw (smi_batch_set_frame_extents)
     int32_t *pause_at = nullptr, *conv_flag = nullptr;  // smi_batch_set_pause_at
     std::vector<char> plan_shared;  // plans[i] belongs to the plan cache (smi_batch_add_sweep_plan)
     int32_t *h_round = nullptr;  // pinned staging of smi_batch_set_round / get_round, 3 x n_blends
@@ -331,6 +332,7 @@ void refresh_view(smi_batch *b) {
     v.weights = b->weights;
     v.dw = b->dw;
     v.it_base = b->it_base;
+    v.frame_hw = b->frame_hw;
     v.pause_at = b->pause_at;
     v.conv_flag = b->conv_flag;
     v.log_norm = b->log_norm;
@@ -678,6 +680,7 @@ int smi_batch_attach_lowres(smi_batch *b, smi_resampler *r, const int32_t *chann
                             const float *data, const float *weights, double log_norm) {
     SMI_REQUIRE(b && r && channels && data && weights, "null argument");
     SMI_REQUIRE(b->d.n_blends == 1, "a low-resolution observation needs a batch of one blend");
+    SMI_REQUIRE(!b->frame_hw, "a low-resolution observation does not support frame extents");
     SMI_REQUIRE(r->impl, "resampler already destroyed");
     SMI_REQUIRE((int)b->lowres.size() < kMaxLowRes, "too many low-resolution observations");
     SMI_HIP(hipSetDevice(b->device));
@@ -901,7 +904,7 @@ int smi_batch_destroy(smi_batch *b) {
                     b->morph, b->mom[0], b->mom[1], b->mom[2], b->mom[3], b->mom[4], b->mom[5],
                     b->g_sed, b->g_morph, b->xp_tmp, b->pt, b->g_center, b->c_sigma, b->c_beta, b->morph_param,
                     b->c_shift_step, b->c_shift_rel, b->c_shift_fft, b->c_center_floor, b->c_sym_strength, b->c_chain_repeat, b->c_pos_floor, b->c_bg_level,
-                    b->c_fista_step, b->fista_t, b->have_prev, b->scratch, b->state, b->zero_state, b->n_loss, b->status_out, b->it_base, b->pause_at, b->conv_flag, b->shift_scratch,
+                    b->c_fista_step, b->fista_t, b->have_prev, b->scratch, b->state, b->zero_state, b->n_loss, b->status_out, b->it_base, b->frame_hw, b->pause_at, b->conv_flag, b->shift_scratch,
                     b->loss_hist, b->last_loss, b->loss_partial, b->d_plans, b->work_items};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
@@ -1261,6 +1264,7 @@ int smi_batch_set_kernel_shift(smi_batch *b, const float *kernel, int32_t h0, in
                                const double *moments, double step) {
     SMI_REQUIRE(b && kernel && fft_shape && shift, "null argument");
     SMI_REQUIRE(b->fused, "a free kernel shift needs the fused convolution path");
+    SMI_REQUIRE(!b->frame_hw, "a free kernel shift does not support frame extents");
     SMI_REQUIRE(b->have_components && b->have_obs, "set the observation and the components first");
     // (further observations on the model's grid keep their fixed kernels: the free shift belongs
     // to the first observation's)
@@ -1438,6 +1442,7 @@ int smi_batch_add_observation(smi_batch *b, const float *data, const float *weig
                               const float *kernel) {
     SMI_REQUIRE(b && data && weights && kernel, "null argument");
     SMI_REQUIRE(b->have_obs && b->have_kernel, "add the first observation and its kernel first");
+    SMI_REQUIRE(!b->frame_hw, "further observations do not support frame extents");
     SMI_REQUIRE(b->fused, "further observations need the fused convolution path");
     // (a free kernel shift stays with the first observation: smi_batch_set_kernel_shift)
     SMI_HIP(hipSetDevice(b->device));
@@ -1514,6 +1519,10 @@ static int set_components_impl(smi_batch *b, const smi_components *c, const int3
     SMI_REQUIRE(c->blend && c->origin_y && c->origin_x && c->box_h && c->box_w &&
                     (keep || (c->sed && c->morph)) && c->sed_min_step && c->morph_step && c->prox_flags,
                 "missing component array");
+    if (b->frame_hw)
+        for (int k = 0; k < b->d.n_components; ++k)
+            SMI_REQUIRE(!(c->prox_flags[k] & (SMI_COMPONENT_POINT_SOURCE | SMI_COMPONENT_SHIFTING)),
+                        "frame extents: point sources and shifting components are not supported");
     SMI_HIP(hipSetDevice(b->device));
     SMI_HIP(hipStreamSynchronize(b->stream));  // pending steps may still read the old arrays
     const int n = b->d.n_components, nb = b->d.n_blends, C = b->d.C;
@@ -1864,6 +1873,7 @@ int smi_batch_update_components(smi_batch *b, const smi_components *c, const int
 
 int smi_batch_resize_test(smi_batch *b, int32_t *margin, double *edge_pull) {
     SMI_REQUIRE(b && b->have_components && margin && edge_pull, "components not set / null argument");
+    SMI_REQUIRE(!b->frame_hw, "smi_batch_resize_test does not support frame extents");
     SMI_HIP(hipSetDevice(b->device));
     const int n = b->d.n_components;
     int32_t *d_margin = nullptr;
@@ -1923,6 +1933,36 @@ int smi_batch_set_iteration_base(smi_batch *b, const int32_t *base) {
         if (!b->it_base) SMI_HIP(dev_alloc(&b->it_base, (size_t)b->d.n_blends));
         SMI_HIP(hipMemcpy(b->it_base, base, b->d.n_blends * sizeof(int32_t), hipMemcpyHostToDevice));
     }
+    refresh_view(b);
+    return SMI_OK;
+}
+
+int smi_batch_set_frame_extents(smi_batch *b, const int32_t *h, const int32_t *w) {
+    SMI_REQUIRE(b != nullptr, "null batch");
+    SMI_REQUIRE((h == nullptr) == (w == nullptr), "smi_batch_set_frame_extents: h and w must both be set or both NULL");
+    SMI_HIP(hipSetDevice(b->device));
+    SMI_HIP(hipStreamSynchronize(b->stream));  // pending steps may still read the old extents
+    if (!h) {
+        if (b->frame_hw) (void)hipFree(b->frame_hw);
+        b->frame_hw = nullptr;
+        refresh_view(b);
+        return SMI_OK;
+    }
+    SMI_REQUIRE(b->n_point == 0 && b->n_shift == 0,
+                "frame extents: point sources and shifting components are not supported");
+    SMI_REQUIRE(!b->ks.stamp, "frame extents: a shifting difference kernel is not supported");
+    SMI_REQUIRE(b->lowres.empty() && b->layers.empty(),
+                "frame extents: further observations are not supported");
+    const int nb = b->d.n_blends;
+    std::vector<int32_t> hw(2 * (size_t)nb);
+    for (int i = 0; i < nb; ++i) {
+        SMI_REQUIRE(h[i] >= 1 && h[i] <= b->d.H && w[i] >= 1 && w[i] <= b->d.W,
+                    "frame extents must satisfy 1 <= h <= H and 1 <= w <= W");
+        hw[2 * i] = h[i];
+        hw[2 * i + 1] = w[i];
+    }
+    if (!b->frame_hw) SMI_HIP(dev_alloc(&b->frame_hw, hw.size()));
+    SMI_HIP(hipMemcpy(b->frame_hw, hw.data(), hw.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     refresh_view(b);
     return SMI_OK;
 }
@@ -2740,6 +2780,31 @@ int smi_batch_fft_shape(smi_batch *b, int32_t *fft_h, int32_t *fft_w) {
     SMI_REQUIRE(b, "null batch");
     if (fft_h) *fft_h = b->Fy;
     if (fft_w) *fft_w = b->Fx;
+    return SMI_OK;
+}
+
+int smi_fft_shape_for(int32_t H, int32_t W, int32_t kernel_h, int32_t kernel_w, int32_t conv_path,
+                      int32_t *Fy, int32_t *Fx) {
+    SMI_REQUIRE(Fy && Fx, "null argument");
+    SMI_REQUIRE(H > 0 && W > 0 && kernel_h >= 0 && kernel_w >= 0, "bad sizes");
+    SMI_REQUIRE((kernel_h == 0) == (kernel_w == 0), "kernel_h/kernel_w mismatch");
+    SMI_REQUIRE(conv_path >= 0 && conv_path <= 2, "conv_path must be 0, 1 or 2");
+    if (kernel_h == 0) {  // NullRenderer
+        *Fy = H;
+        *Fx = W;
+        return SMI_OK;
+    }
+    // the rule of batch_create_impl for fft_h = fft_w = 0
+    int fy = 0, fx = 0;
+    if (conv_path != 1 && fused_conv_choose(H + kernel_h / 2, W + kernel_w / 2, &fy, &fx)) {
+        *Fy = fy;
+        *Fx = fx;
+        return SMI_OK;
+    }
+    SMI_REQUIRE(conv_path != 2, "fused convolution not available for this shape");
+    reference_fft_shape(H, W, kernel_h, kernel_w, &fy, &fx);
+    *Fy = fy;
+    *Fx = fx;
     return SMI_OK;
 }
 

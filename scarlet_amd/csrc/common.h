@@ -311,9 +311,15 @@ struct BatchView {
     const int32_t *pause_at = nullptr;
     int32_t *conv_flag = nullptr;
     const int32_t *it_base = nullptr;
+    // smi_batch_set_frame_extents: per blend (h, w), the corner of its H x W plane that is its
+    // frame; components are clipped to it (nullptr: every blend has the full H x W frame).
+    // Indexed by a wave-uniform blend, so the reads are scalar loads.
+    const int32_t *frame_hw = nullptr;
     __device__ __forceinline__ int local_it(int b, int it) const {
         return it_base ? it - it_base[b] : it;
     }
+    __device__ __forceinline__ int frame_h(int b) const { return frame_hw ? frame_hw[2 * b] : H; }
+    __device__ __forceinline__ int frame_w(int b) const { return frame_hw ? frame_hw[2 * b + 1] : W; }
 };
 
 void launch_render(const BatchView &v, float *P, hipStream_t s);

@@ -578,7 +578,7 @@ template <int FX1, int NX1, int M>
 struct ModelGather {
     static constexpr uint32_t kNone = 0x40000000u;  // rowbase + column stays out of range
     const BatchView &v;
-    int band_c, H, W, y, n2, ylo;
+    int band_c, H, W, y, n2, ylo;  // (H, W: the blend's frame, BatchView::frame_hw)
     // metadata of 64 components, one per lane (all that `open` needs comes from here by
     // v_readlane: no scalar address arithmetic, no load per component)
     struct Lanes {
@@ -669,7 +669,8 @@ extern __shared__ __attribute__((aligned(16))) float2 lds_conv[];
 // model: the model cube [nb][C][H][W] (render_kernel)
 // mode 0: full (writes the gradient image G[nb][C][H][W] and the loss partial)
 // mode 1: forward only (writes the rendered cube instead and the loss partial)
-template <int FY1, int FX1, int ZB>
+// EXT: the batch has frame extents (smi_batch_set_frame_extents)
+template <int FY1, int FX1, int ZB, bool EXT>
 __global__ __launch_bounds__(kThreads) void fused_conv_kernel(BatchView v, const float *model,
                                                               const float2 *Kt, int k_bands,
                                                               int k_per_blend, float *out,
@@ -685,6 +686,8 @@ __global__ __launch_bounds__(kThreads) void fused_conv_kernel(BatchView v, const
     if (v.state[b] >= 2) return;
     const int tid = threadIdx.x;
     const int H = v.H, W = v.W;
+    // ModelGather clips components to the blend's own frame (smi_batch_set_frame_extents)
+    const int Hb = EXT ? v.frame_h(b) : H, Wb = EXT ? v.frame_w(b) : W;
 
     Conv<FY1, FX1, ZB> cv;
     cv.T = lds_conv;
@@ -715,10 +718,10 @@ __global__ __launch_bounds__(kThreads) void fused_conv_kernel(BatchView v, const
         // the four row pairs of this wavefront start at pair (item / 64) * 4
         const int j0 = __builtin_amdgcn_readfirstlane(s.j - ((tid & 63) >> 4));
         if (v.render_slots <= 4) {
-            const ModelGather<FX1, NX1, 4> g{v, c, H, W, 2 * s.j, s.n2, 2 * j0};
+            const ModelGather<FX1, NX1, 4> g{v, c, Hb, Wb, 2 * s.j, s.n2, 2 * j0};
             g.run(b, tid & 63, mrow);
         } else {
-            const ModelGather<FX1, NX1, (FX1 < 6 ? FX1 : 6)> g{v, c, H, W, 2 * s.j, s.n2, 2 * j0};
+            const ModelGather<FX1, NX1, (FX1 < 6 ? FX1 : 6)> g{v, c, Hb, Wb, 2 * s.j, s.n2, 2 * j0};
             g.run(b, tid & 63, mrow);
         }
     };
@@ -946,17 +949,26 @@ __global__ void stamp_dft_y(const double2 *A, float2 *Kt, int ph, int NKX, doubl
 
 #endif  // SMI_CONV_SHORT_ROWS
 
-template <int FY1, int FX1, int ZB>
-int launch_zb(const BatchView &v, const float *model, const float2 *Kt, int k_bands,
-              int k_per_blend, float *out, int mode, long long *dbg, hipStream_t s) {
+template <int FY1, int FX1, int ZB, bool EXT>
+int launch_ext(const BatchView &v, const float *model, const float2 *Kt, int k_bands,
+               int k_per_blend, float *out, int mode, long long *dbg, hipStream_t s) {
     using C = Cfg<FY1, FX1, ZB>;
-    auto kern = fused_conv_kernel<FY1, FX1, ZB>;
+    auto kern = fused_conv_kernel<FY1, FX1, ZB, EXT>;
     static size_t configured[kMaxDevices] = {};
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), C::lds_bytes, configured))
         return rc;
     hipLaunchKernelGGL(kern, dim3(v.nb * v.C), dim3(kThreads), C::lds_bytes, s, v, model, Kt,
                        k_bands, k_per_blend, out, mode, dbg);
     return SMI_OK;
+}
+
+// (the kernels without frame extents are those of a batch that never had them)
+template <int FY1, int FX1, int ZB>
+int launch_zb(const BatchView &v, const float *model, const float2 *Kt, int k_bands,
+              int k_per_blend, float *out, int mode, long long *dbg, hipStream_t s) {
+    if (v.frame_hw)
+        return launch_ext<FY1, FX1, ZB, true>(v, model, Kt, k_bands, k_per_blend, out, mode, dbg, s);
+    return launch_ext<FY1, FX1, ZB, false>(v, model, Kt, k_bands, k_per_blend, out, mode, dbg, s);
 }
 
 // the kernel variant for the frame: as many all-padding blocks (of both axes) as it has, up to 2

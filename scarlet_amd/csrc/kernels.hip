@@ -91,9 +91,11 @@ __global__ __launch_bounds__(64 * kRenderWaves) void render_kernel(BatchView v, 
     if (y0 >= v.H) return;
     const int cs = v.comp_start[b], ce = v.comp_start[b + 1];
     const int H = v.H, W = v.W;
-    const int y1 = min(y0 + kRenderRows, H);
+    // components are clipped to the blend's own frame (smi_batch_set_frame_extents); the rest
+    // of the plane is written as zeros
+    const int y1 = min(y0 + kRenderRows, v.frame_h(b)), Wb = v.frame_w(b);
     for (int x0 = 0; x0 < W; x0 += 128) {
-        const int x1 = min(x0 + 128, W);
+        const int x1 = min(x0 + 128, Wb);
         for (int c0 = 0; c0 < v.C; c0 += NB) {
             const int nc = min(NB, v.C - c0);
             float acc[kRenderRows][2][NB];
@@ -452,11 +454,11 @@ __device__ __forceinline__ CompCtx comp_ctx(const BatchView &v) {
     return c;
 }
 
-// slice G into the box (zero outside the frame, blend.py:30-46); us[i] = sum_c sed G,
-// return (in lane c) sum_yx G[c] morph  (lite/models.py:206-216)
+// slice G into the box (zero outside the frame [0, Hb) x [0, Wb), blend.py:30-46); us[i] =
+// sum_c sed G, return (in lane c) sum_yx G[c] morph  (lite/models.py:206-216)
 template <int T>
 __device__ __forceinline__ float gather_gradient(const BatchView &v, const CompCtx &c,
-                                                 const float *G, float *us) {
+                                                 const float *G, float *us, int Hb, int Wb) {
     float g_sed = 0.f;
     if (c.pre) {
         for (int i = c.lane; i < c.N; i += T) us[i] = v.g_morph_buf[c.moff + i];
@@ -486,7 +488,7 @@ __device__ __forceinline__ float gather_gradient(const BatchView &v, const CompC
                 const int fy = y + c.oy, fx = x + c.ox;
                 in_box[u] = i < c.N;
                 const bool ok =
-                    in_box[u] && (unsigned)fy < (unsigned)v.H && (unsigned)fx < (unsigned)v.W;
+                    in_box[u] && (unsigned)fy < (unsigned)Hb && (unsigned)fx < (unsigned)Wb;
                 mv[u] = ok ? c.morph[i] : 0.f;
                 const float *g = G + (((int64_t)c.b * c.C + c0) * v.Fy + fy) * v.Fx + fx;
 #pragma unroll
@@ -750,7 +752,7 @@ __global__ __launch_bounds__(T) void update_kernel(BatchView v, const float *G, 
     float *ws = reinterpret_cast<float *>(lvl + ((v.max_levels + 2 + 3) & ~3));
     uint8_t *fl = reinterpret_cast<uint8_t *>(ws + npad);
 
-    float g_sed = gather_gradient<T>(v, c, G, us);
+    float g_sed = gather_gradient<T>(v, c, G, us, v.frame_h(c.b), v.frame_w(c.b));
     __syncthreads();
     if (grad_only) {
         if (lane < c.C) g_sed_out[(int64_t)c.k * c.C + lane] = g_sed;
@@ -997,7 +999,8 @@ __global__ __launch_bounds__(64) void point_source_kernel(BatchView v, const flo
     };
 
     if (mode != 2) {
-        const float g_sed = gather_gradient<64>(v, c, G, us);
+        // (point sources and frame extents exclude each other: smi_batch_set_frame_extents)
+        const float g_sed = gather_gradient<64>(v, c, G, us, v.H, v.W);
         __syncthreads();
         double gy = 0.0, gx = 0.0;
         if (moffat) {
@@ -1573,8 +1576,8 @@ struct UpdFull {
 };
 
 // gradient gather, spectrum update, AMSGrad (or FISTA) step of the image, set-up of the
-// proximal sub-iterations
-template <int NPL, int MODE, int T>
+// proximal sub-iterations.  EXT: the batch has frame extents (smi_batch_set_frame_extents)
+template <int NPL, int MODE, int T, bool EXT>
 __device__ __forceinline__ void upd_step(const BatchView &v, const float *G, int it, float e2,
                                          int prox_max_iter, UpdState<NPL, update_xp(T)> &S) {
     constexpr bool LITE = MODE != 0;
@@ -1618,6 +1621,7 @@ __device__ __forceinline__ void upd_step(const BatchView &v, const float *G, int
         // range), parked in the LDS image, which is not needed before the prox loop
         uint32_t *goff = reinterpret_cast<uint32_t *>(us);
         const float inv_w = 1.0f / (float)c.w;
+        const int Hb = EXT ? v.frame_h(c.b) : v.H, Wb = EXT ? v.frame_w(c.b) : v.W;  // its frame
 #pragma unroll
         for (int j = 0; j < NPL; ++j) {
             const int i = lane + T * j;
@@ -1625,8 +1629,8 @@ __device__ __forceinline__ void upd_step(const BatchView &v, const float *G, int
             const int y = (int)(((float)i + 0.5f) * inv_w);
             const int x = i - y * c.w;
             const int fy = y + c.oy, fx = x + c.ox;
-            const bool ok = (j < kFull || i < N) && (unsigned)fy < (unsigned)v.H &&
-                            (unsigned)fx < (unsigned)v.W;
+            const bool ok = (j < kFull || i < N) && (unsigned)fy < (unsigned)Hb &&
+                            (unsigned)fx < (unsigned)Wb;
             goff[i] = ok ? (uint32_t)(fy * v.Fx + fx) * 4u : kOutOfRange;
             xs[j] = 0.f;
         }
@@ -1946,7 +1950,7 @@ __device__ __forceinline__ void upd_store(const BatchView &v, UpdState<NPL, upda
 }
 
 // kGlobalRing: components without a staged plan read the ring stream out of L2 (update_kernel_mixed)
-template <int NPL, int MODE, int T = 64, bool kGlobalRing = false>
+template <int NPL, int MODE, int T = 64, bool kGlobalRing = false, bool EXT = false>
 __device__ __forceinline__ void update_component(const BatchView &v, const float *G, int it,
                                                  float e_rel, int prox_max_iter, int k,
                                                  float *us, float *sed_new,
@@ -1964,7 +1968,7 @@ __device__ __forceinline__ void update_component(const BatchView &v, const float
     S.sed_new = sed_new;
     const float e2 = e_rel * e_rel;
     if (fista) prox_max_iter = 1;  // FistaParameter applies the prox once
-    upd_step<NPL, MODE, T>(v, G, it, e2, prox_max_iter, S);
+    upd_step<NPL, MODE, T, EXT>(v, G, it, e2, prox_max_iter, S);
     team_fence<T>();  // the offsets parked in `us` have been consumed
     for (int tau = 0; tau < prox_max_iter; ++tau) {
         upd_prox_begin<NPL, T>(v, S);
@@ -2024,7 +2028,7 @@ constexpr int update_pack_max(int npl, int team) {
 // it (a counter in LDS) until it is used up -- a workgroup that holds 150 KB of LDS must not
 // idle behind its slowest component.  (One global counter per XCD, measured: 10 240 atomic
 // additions on eight addresses take 0.25 ms, longer than the updates themselves.)
-template <int NPL, int MODE, int T>
+template <int NPL, int MODE, int T, bool EXT>
 __global__ __launch_bounds__(T * update_pack_max(NPL, T)) SMI_WAVES void update_kernel_reg(
     BatchView v, const float *G, int it, float e_rel, int prox_max_iter, int n_items,
     int n_finalize, int min_iter, int check, int stage_plan, int persistent) {
@@ -2079,7 +2083,7 @@ __global__ __launch_bounds__(T * update_pack_max(NPL, T)) SMI_WAVES void update_
         // from it must not be hoisted out of this loop and live across all of them)
         int tid = (int)threadIdx.x;
         asm volatile("" : "+v"(tid));
-        update_component<NPL, MODE, T>(v, G, it, e_rel, prox_max_iter, v.work[lo + k + v.work0],
+        update_component<NPL, MODE, T, false, EXT>(v, G, it, e_rel, prox_max_iter, v.work[lo + k + v.work0],
                                        us, sed_new[wave], staged, plan_lds, tid);
         if (!loop) break;
     }
@@ -2101,7 +2105,7 @@ __global__ __launch_bounds__(T * update_pack_max(NPL, T)) SMI_WAVES void update_
 // Quickstart Blend.fit(100, 1e-4) 18.5 -> 17.2 ms, 16 quickstart blends 124 k -> 135 k
 // blend-it/s, 128 blends 765 k -> 782 k; 256 blends 1 224 k -> 1 040 k: a batch of more than
 // ~1 000 components needs the second wavefront per SIMD (launch_update picks).
-template <int MODE, int WAVES>
+template <int MODE, int WAVES, bool EXT>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) void update_kernel_mixed(
     BatchView v, const float *G, int it, float e_rel, int prox_max_iter, int n_finalize,
     int min_iter, int check) {
@@ -2115,15 +2119,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) voi
     const int n = v.c_h[k] * v.c_w[k];  // uniform over the wavefront
     float *us = lds_dyn + 4;  // (spare cell of the sweep in front)
     if (n <= 64 * kUpdateNpl[0])
-        update_component<kUpdateNpl[0], MODE, 64, true>(v, G, it, e_rel, prox_max_iter, k, us, sed_new);
+        update_component<kUpdateNpl[0], MODE, 64, true, EXT>(v, G, it, e_rel, prox_max_iter, k, us, sed_new);
     else if (n <= 64 * kUpdateNpl[1])
-        update_component<kUpdateNpl[1], MODE, 64, true>(v, G, it, e_rel, prox_max_iter, k, us, sed_new);
+        update_component<kUpdateNpl[1], MODE, 64, true, EXT>(v, G, it, e_rel, prox_max_iter, k, us, sed_new);
     else if (n <= 64 * kUpdateNpl[2])
-        update_component<kUpdateNpl[2], MODE, 64, true>(v, G, it, e_rel, prox_max_iter, k, us, sed_new);
+        update_component<kUpdateNpl[2], MODE, 64, true, EXT>(v, G, it, e_rel, prox_max_iter, k, us, sed_new);
     else if (n <= 64 * kUpdateNpl[3])
-        update_component<kUpdateNpl[3], MODE, 64, true>(v, G, it, e_rel, prox_max_iter, k, us, sed_new);
+        update_component<kUpdateNpl[3], MODE, 64, true, EXT>(v, G, it, e_rel, prox_max_iter, k, us, sed_new);
     else
-        update_component<kUpdateNpl[4], MODE, 64, true>(v, G, it, e_rel, prox_max_iter, k, us, sed_new);
+        update_component<kUpdateNpl[4], MODE, 64, true, EXT>(v, G, it, e_rel, prox_max_iter, k, us, sed_new);
 }
 
 // development aid: shader clocks of `n_rep` sweeps of one plan per wavefront, every wavefront
@@ -2676,20 +2680,25 @@ static int launch_update_reg(const BatchView &v, const float *G, int32_t it, flo
         }
     }
     const dim3 grid(n_blocks + n_fin), block(T * pack);
-#define SMI_LAUNCH(MODE)                                                                        \
+#define SMI_LAUNCH_EXT(MODE, EXT)                                                               \
     {                                                                                           \
         static size_t configured[kMaxDevices] = {};                                             \
-        auto kern = update_kernel_reg<NPL, MODE, T>;                                            \
+        auto kern = update_kernel_reg<NPL, MODE, T, EXT>;                                       \
         if (lds > 48 * 1024)                                                                    \
             if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds, configured)) \
                 return rc;                                                                      \
         hipLaunchKernelGGL(kern, grid, block, lds, s, vi, G, it, e_rel, prox_max_iter, n_items, \
                            n_fin, fin.min_iter, fin.check, stage, persistent);                         \
     }
+    // (the kernels without frame extents are those of a batch that never had them)
+#define SMI_LAUNCH(MODE)                                                                        \
+    if (v.frame_hw) SMI_LAUNCH_EXT(MODE, true)                                                  \
+    else SMI_LAUNCH_EXT(MODE, false)
     if (v.scheme == SMI_SCHEME_FISTA) SMI_LAUNCH(2)
     else if (v.lite) SMI_LAUNCH(1)
     else SMI_LAUNCH(0)
 #undef SMI_LAUNCH
+#undef SMI_LAUNCH_EXT
     return SMI_OK;
 }
 
@@ -2750,13 +2759,19 @@ int launch_update(const BatchView &v_in, const float *G, int32_t it, float e_rel
                 return e ? atoi(e) : 1024;
             }();
             const bool lone = v.n_comp_total <= one_wave_limit;  // (one wavefront per SIMD suffices)
-#define SMI_MIXED(MODE)                                                                          \
+#define SMI_MIXED_EXT(MODE, EXT)                                                                 \
     if (lone)                                                                                    \
-        hipLaunchKernelGGL((update_kernel_mixed<MODE, 1>), grid, dim3(64), lds, s, v, G, it,     \
+        hipLaunchKernelGGL((update_kernel_mixed<MODE, 1, EXT>), grid, dim3(64), lds, s, v, G, it, \
                            e_rel, prox_max_iter, n_fin, fin.min_iter, fin.check);                \
     else                                                                                         \
-        hipLaunchKernelGGL((update_kernel_mixed<MODE, 2>), grid, dim3(64), lds, s, v, G, it,     \
+        hipLaunchKernelGGL((update_kernel_mixed<MODE, 2, EXT>), grid, dim3(64), lds, s, v, G, it, \
                            e_rel, prox_max_iter, n_fin, fin.min_iter, fin.check)
+#define SMI_MIXED(MODE)                                                                          \
+    if (v.frame_hw) {                                                                            \
+        SMI_MIXED_EXT(MODE, true);                                                               \
+    } else {                                                                                     \
+        SMI_MIXED_EXT(MODE, false);                                                              \
+    }
             if (v.scheme == SMI_SCHEME_FISTA) {
                 SMI_MIXED(2);
             } else if (v.lite) {
@@ -2765,6 +2780,7 @@ int launch_update(const BatchView &v_in, const float *G, int32_t it, float e_rel
                 SMI_MIXED(0);
             }
 #undef SMI_MIXED
+#undef SMI_MIXED_EXT
             return SMI_OK;
         }
         // one launch per size class that has components in this range of blends, the
