@@ -161,6 +161,38 @@ def _step_rule(step, what):
     return float(step), 0.0, 0
 
 
+# -- the rules of the adaprox round loop (blend.py:276-302), for every fit that runs one
+def _next_round(local, budget):
+    """Iterations until the resize hook after local iterations 10, 20, ... has to run (once
+    11, 21, ... iterations of this adaprox call are done), capped by ``budget``."""
+    n_hook = (11 if local == 0 else ((local - 1) // 10 + 1) * 10 + 1) - local
+    return min(n_hook, budget)
+
+
+def _at_hook(done):
+    """Whether an adaprox call that has run ``done`` iterations (an int or an array) ends
+    on a resize hook."""
+    return (done > 1) & ((done - 1) % 10 == 0)
+
+
+def _update_sources(sources):
+    """``update()`` of every source (blend.py:284-292); True when one of them raised
+    ``UpdateException``, so that the adaprox call starts anew at ``it = len(loss)``."""
+    restart = False
+    for src in sources:
+        try:
+            src.update()
+        except UpdateException:
+            restart = True
+    return restart
+
+
+def _mark_std(parameters):
+    for p in parameters:
+        if p.v is not None:
+            p.std = STD_FROM_V  # rough estimate, blend.py:189-192
+
+
 class Blend(CombinedComponent):
     """Collection of sources fitted jointly to one observation."""
 
@@ -710,11 +742,8 @@ class Blend(CombinedComponent):
                     raise NotImplementedError(
                         "noise_factor > 0 with a host-stepped psf_shift (prior, constraint or "
                         "step callable on it)")
-                try:
-                    return self._fit_with_psf_shift(max_iter, e_rel, min_iter, prox_max_iter, opt,
-                                                    callback)
-                finally:
-                    self._psf, self._psf_stepped_on_device = None, False
+                return self._fit_with_psf_shift(max_iter, e_rel, min_iter, prox_max_iter, opt,
+                                                callback)
         extra = () if self._psf is None else (self._psf[0],)
 
         from .fitting import _device_hook_covers, _fit_blends_on  # (fitting imports this module)
@@ -735,35 +764,45 @@ class Blend(CombinedComponent):
                 logger.info("scarlet ran for {0} iterations to logL = {1}".format(*out[0]))
                 return out[0]
 
+        noise = partial(self._draw_noise, noise_factor=noise_factor) if noise_factor else None
+        try:
+            return self._fit_rounds(self._build_batch, max_iter, e_rel, min_iter, prox_max_iter,
+                                    opt, callback, before=noise, extra=extra)
+        except _HostSteppedShift:
+            # frames beyond the fused convolution kernel: the shift is stepped by the host
+            if noise_factor:
+                raise NotImplementedError(
+                    "noise_factor > 0 with a free psf_shift on a frame beyond the fused "
+                    "convolution (the host-stepped shift does not redraw the noise)")
+            return self._fit_with_psf_shift(max_iter, e_rel, min_iter, prox_max_iter, opt,
+                                            callback)
+
+    def _fit_rounds(self, make_batch, max_iter, e_rel, min_iter, prox_max_iter, opt, callback,
+                    before=None, after=None, extra=()):
+        """The adaprox round loop of the device-batch modes (blend.py:276-302).  A round is one
+        batch, ``make_batch(comps, capacity)`` with the state uploaded; it ends when a resize
+        hook changed a box (the next round starts anew at ``it = len(self.loss)``), when the
+        stopping rule fires, or at ``max_iter``.
+
+        Host work around every device step: ``before(batch)`` ahead of it (noise redraw,
+        gradients of a host-stepped shift); after a step that went well, the parameters
+        ``_specs`` left to the host (``self._host``) and ``after(batch, local, what before
+        returned)`` (the host-stepped shift's step), which says whether its parameters are
+        finite.  Host work or a callback make every device call one iteration.  ``extra``:
+        free parameters besides the sources' (psf shifts), behind them in the callback's
+        arguments."""
+        stepwise = callback is not None or before is not None or after is not None
         it = 0
         while it < max_iter:
             comps = _flatten(self.sources)
-            try:
-                batch = self._build_batch(comps, max_iter - it)
-            except _HostSteppedShift:
-                # frames beyond the fused convolution kernel: the shift is stepped by the host
-                if noise_factor:
-                    raise NotImplementedError(
-                        "noise_factor > 0 with a free psf_shift on a frame beyond the fused "
-                        "convolution (the host-stepped shift does not redraw the noise)")
-                try:
-                    return self._fit_with_psf_shift(max_iter, e_rel, min_iter, prox_max_iter, opt,
-                                                    callback)
-                finally:
-                    self._psf, self._psf_stepped_on_device = None, False
+            batch = make_batch(comps, max_iter - it)
             batch.set_optimizer(**opt)
             restart = False
             try:
                 local = 0  # adaprox's own counter, restarts after every resize
                 while it + local < max_iter and not restart:
-                    # the resize hook fires after the update of local iterations 10, 20, ...
-                    # i.e. once 11, 21, ... iterations of this batch are done
-                    next_hook = 11 if local == 0 else ((local - 1) // 10 + 1) * 10 + 1
-                    n = min(next_hook - local, max_iter - it - local)
-                    if callback is not None or self._host or noise_factor:
-                        n = 1
-                    if noise_factor:
-                        self._draw_noise(batch, noise_factor)
+                    n = 1 if stepwise or self._host else _next_round(local, max_iter - it - local)
+                    pre = None if before is None else before(batch)
                     # plug-in seam: gradients at the parameters of this iteration for the
                     # parameters the host updates (hoststep.py)
                     grads = self._host_gradients(batch, comps) if self._host else None
@@ -771,23 +810,22 @@ class Blend(CombinedComponent):
                                prox_max_iter=prox_max_iter, check_convergence=True)
                     active, err = batch.status()
                     done = len(batch.loss_history()[0])
-                    if self._host and err < 0 and done == local + 1:
-                        self._host_update(batch, local, grads, e_rel, prox_max_iter, opt)
-                        if not all(hp.p.is_finite for _, hp in self._host):
+                    if err < 0 and done == local + 1:
+                        if self._host:
+                            self._host_update(batch, local, grads, e_rel, prox_max_iter, opt)
+                            if not all(hp.p.is_finite for _, hp in self._host):
+                                err = 0
+                        if after is not None and not after(batch, local, pre):
                             err = 0
                     if err >= 0:
                         self.loss.extend(batch.loss_history()[0])
                         self._download(batch, comps)
                         raise ArithmeticError("parameters of the blend are not finite")
-                    hook = done == local + n and done > 1 and (done - 1) % 10 == 0
+                    hook = done == local + n and _at_hook(done)
                     local = done
                     if hook:
                         self._download(batch, comps)
-                        for src in self.sources:
-                            try:
-                                src.update()
-                            except UpdateException:
-                                restart = True
+                        restart = _update_sources(self.sources)
                     if active == 0 and not restart:
                         break
                     if callback is not None and not restart:
@@ -808,9 +846,7 @@ class Blend(CombinedComponent):
 
         logger.info("scarlet ran for {0} iterations to logL = {1}".format(
             len(self.loss), -self.loss[-1]))
-        for p in self.parameters + extra:
-            if p.v is not None:
-                p.std = STD_FROM_V  # rough estimate, blend.py:189-192
+        _mark_std(self.parameters + extra)
         # what _specs / _observation read is per call: nothing of this fit's renderer
         # parameters or scheme may steer a later fit_blends
         self._psf_stepped_on_device = self._psf is not None
@@ -872,13 +908,13 @@ class Blend(CombinedComponent):
         forward renders with the kernel's derivatives give
         ``d(-logL)/d(shift) = sum w (m - d) (model (*) dK/ds)``; the shift then takes its
         unconstrained AMSGrad step (step 1e-2) on the host."""
+        # (_specs / _download: no device-side shift in this mode)
+        self._psf, self._psf_stepped_on_device = None, False
         shift, renderer = self._free_psf_shift()
         if len(self.observations) != 1:
             raise NotImplementedError(
                 "a free psf_shift with several observations on a frame beyond the fused convolution")
         obs = self.observations[0]
-        alpha0, rel = self._psf_step, self._psf_rel
-        self._psf = None  # _specs / _download: no device-side shift in this mode
         C = self.frame.C
         data = np.ascontiguousarray(obs.data, dtype=np.float32)
         weights = np.ascontiguousarray(obs.weights, dtype=np.float32)
@@ -891,71 +927,37 @@ class Blend(CombinedComponent):
             out[:, oy:oy + k.shape[1], ox:ox + k.shape[2]] = k
             return out
 
-        # (the step itself: hoststep.HostVector -- amsgrad_pair of the device in float64, plus
-        # the shift's prior / constraint / step callable if it has any)
-        stepper = getattr(self, "_psf_host", None) or HostVector(shift, (alpha0, rel, 0.0))
-        it = 0
-        while it < max_iter:
-            comps = _flatten(self.sources)
+        def make_batch(comps, capacity):
             batch = BlendBatch(data[None], weights[None], [self._specs(comps)],
-                               kernel=stamp(renderer.kernel_image()), max_iter=max(max_iter - it, 1),
+                               kernel=stamp(renderer.kernel_image()), max_iter=max(capacity, 1),
                                device=self.device)
             self._upload_state(batch, comps)
-            batch.set_optimizer(**opt)
-            restart = False
-            try:
-                local = 0
-                while it + local < max_iter and not restart:
-                    # gradient w.r.t. the shift at the parameters of this iteration
-                    _, rendered, _ = batch.forward(model=False)
-                    resid = weights.astype(np.float64) * (rendered[0] - data)
-                    g = np.zeros(2)
-                    for a, dk in enumerate(renderer.kernel_derivatives()):
-                        batch.set_kernel(stamp(dk))
-                        g[a] = np.sum(resid * batch.forward(model=False)[1][0])
-                    batch.set_kernel(stamp(renderer.kernel_image()))
-                    batch.step(local, 1, e_rel=e_rel, min_iter=min_iter,
-                               prox_max_iter=prox_max_iter, check_convergence=True)
-                    # AMSGrad (lite/parameters.py:274-291), sub-iterations if it is constrained
-                    stepper.update(local, g, e_rel, prox_max_iter, **opt)
-                    stepper.store()
-                    batch.set_kernel(stamp(renderer.kernel_image()))
-                    active, err = batch.status()
-                    done = len(batch.loss_history()[0])
-                    if err >= 0 or not np.all(np.isfinite(np.asarray(shift))):
-                        self.loss.extend(batch.loss_history()[0])
-                        self._download(batch, comps)
-                        raise ArithmeticError("parameters of the blend are not finite")
-                    hook = done == local + 1 and done > 1 and (done - 1) % 10 == 0
-                    local = done
-                    if hook:
-                        self._download(batch, comps)
-                        for src in self.sources:
-                            try:
-                                src.update()
-                            except UpdateException:
-                                restart = True
-                    if active == 0 and not restart:
-                        break
-                    if callback is not None and not restart:
-                        if not hook:
-                            self._download(batch, comps)
-                        try:
-                            callback(*self.parameters, shift, it=local - 1)
-                        except StopIteration:
-                            break
-                self.loss.extend(batch.loss_history()[0])
-                if not restart:
-                    self._download(batch, comps)
-            finally:
-                batch.close()
-            if not restart:
-                break
-            it = len(self.loss)
-        for p in self.parameters + (shift,):
-            if p.v is not None:
-                p.std = STD_FROM_V
-        return len(self.loss), -self.loss[-1]
+            return batch
+
+        def gradient(batch):
+            """w.r.t. the shift at the parameters of this iteration; the kernel stays at the shift"""
+            _, rendered, _ = batch.forward(model=False)
+            resid = weights.astype(np.float64) * (rendered[0] - data)
+            g = np.zeros(2)
+            for a, dk in enumerate(renderer.kernel_derivatives()):
+                batch.set_kernel(stamp(dk))
+                g[a] = np.sum(resid * batch.forward(model=False)[1][0])
+            batch.set_kernel(stamp(renderer.kernel_image()))
+            return g
+
+        # (the step itself: hoststep.HostVector -- amsgrad_pair of the device in float64, plus
+        # the shift's prior / constraint / step callable if it has any)
+        stepper = self._psf_host or HostVector(shift, (self._psf_step, self._psf_rel, 0.0))
+
+        def step(batch, local, g):
+            # AMSGrad (lite/parameters.py:274-291), sub-iterations if it is constrained
+            stepper.update(local, g, e_rel, prox_max_iter, **opt)
+            stepper.store()
+            batch.set_kernel(stamp(renderer.kernel_image()))
+            return np.all(np.isfinite(np.asarray(shift)))
+
+        return self._fit_rounds(make_batch, max_iter, e_rel, min_iter, prox_max_iter, opt,
+                                callback, gradient, step, (shift,))
 
     def _fit_with_psf_shifts(self, max_iter, e_rel, min_iter, prox_max_iter, opt, callback):
         """Free ``psf_shift``s of SEVERAL observations (blend.py:103-105: the parameters of
@@ -1007,71 +1009,37 @@ class Blend(CombinedComponent):
 
         shifts = tuple(m[2] for m in movers)
         w64 = weights.astype(np.float64)
-        it = 0
-        while it < max_iter:
-            comps = _flatten(self.sources)
+
+        def make_batch(comps, capacity):
             batch = BlendBatch(data[None], weights[None], [self._specs(comps)], kernel=kernel,
-                               max_iter=max(max_iter - it, 1), device=self.device)
+                               max_iter=max(capacity, 1), device=self.device)
             self._upload_state(batch, comps)
-            batch.set_optimizer(**opt)
-            restart = False
-            try:
-                local = 0
-                while it + local < max_iter and not restart:
-                    _, rendered, _ = batch.forward(model=False)
-                    resid = w64 * (rendered[0] - data)
-                    grads = []
-                    for obs, renderer, shift, idx, stepper in movers:
-                        g = np.zeros(2)
-                        for a, dk in enumerate(renderer.kernel_derivatives()):
-                            batch.set_kernel(derivative_cube(idx, dk))
-                            g[a] = np.sum(resid[idx] * batch.forward(model=False)[1][0][idx])
-                        grads.append(g)
-                    batch.set_kernel(kernel)
-                    batch.step(local, 1, e_rel=e_rel, min_iter=min_iter,
-                               prox_max_iter=prox_max_iter, check_convergence=True)
-                    for (obs, renderer, shift, idx, stepper), g in zip(movers, grads):
-                        stepper.update(local, g, e_rel, prox_max_iter, **opt)
-                        stepper.store()
-                    kernel = merged()[2]
-                    batch.set_kernel(kernel)
-                    active, err = batch.status()
-                    done = len(batch.loss_history()[0])
-                    if err >= 0 or not all(np.all(np.isfinite(np.asarray(s))) for s in shifts):
-                        self.loss.extend(batch.loss_history()[0])
-                        self._download(batch, comps)
-                        raise ArithmeticError("parameters of the blend are not finite")
-                    hook = done == local + 1 and done > 1 and (done - 1) % 10 == 0
-                    local = done
-                    if hook:
-                        self._download(batch, comps)
-                        for src in self.sources:
-                            try:
-                                src.update()
-                            except UpdateException:
-                                restart = True
-                    if active == 0 and not restart:
-                        break
-                    if callback is not None and not restart:
-                        if not hook:
-                            self._download(batch, comps)
-                        try:
-                            callback(*self.parameters, *shifts, it=local - 1)
-                        except StopIteration:
-                            break
-                self.loss.extend(batch.loss_history()[0])
-                if not restart:
-                    self._download(batch, comps)
-            finally:
-                batch.close()
-            if not restart:
-                break
-            it = len(self.loss)
-        for p in self.parameters + shifts:
-            if p.v is not None:
-                p.std = STD_FROM_V
-        self._psf_stepped_on_device = False
-        return len(self.loss), -self.loss[-1]
+            return batch
+
+        def gradients(batch):
+            _, rendered, _ = batch.forward(model=False)
+            resid = w64 * (rendered[0] - data)
+            grads = []
+            for obs, renderer, shift, idx, stepper in movers:
+                g = np.zeros(2)
+                for a, dk in enumerate(renderer.kernel_derivatives()):
+                    batch.set_kernel(derivative_cube(idx, dk))
+                    g[a] = np.sum(resid[idx] * batch.forward(model=False)[1][0][idx])
+                grads.append(g)
+            batch.set_kernel(kernel)
+            return grads
+
+        def step(batch, local, grads):
+            nonlocal kernel
+            for (obs, renderer, shift, idx, stepper), g in zip(movers, grads):
+                stepper.update(local, g, e_rel, prox_max_iter, **opt)
+                stepper.store()
+            kernel = merged()[2]
+            batch.set_kernel(kernel)
+            return all(np.all(np.isfinite(np.asarray(s))) for s in shifts)
+
+        return self._fit_rounds(make_batch, max_iter, e_rel, min_iter, prox_max_iter, opt,
+                                callback, gradients, step, shifts)
 
     def _host_render_ops(self):
         """Per observation ``(obs, forward, adjoint, log_norm)`` for the host-rendered mode:
@@ -1193,13 +1161,9 @@ class Blend(CombinedComponent):
                         self._download(batch, comps)
                         raise ArithmeticError("parameters of the blend are not finite")
                     local += 1
-                    if local > 1 and (local - 1) % 10 == 0:  # blend.py:284-292
+                    if _at_hook(local):  # blend.py:284-292
                         self._download(batch, comps)
-                        for src in self.sources:
-                            try:
-                                src.update()
-                            except UpdateException:
-                                restart = True
+                        restart = _update_sources(self.sources)
                     n = len(self.loss)
                     if (not restart and local - 1 > min_iter and n > 1
                             and abs(self.loss[-2] - self.loss[-1]) < e_rel * abs(self.loss[-1])):
@@ -1212,9 +1176,7 @@ class Blend(CombinedComponent):
             if not restart:
                 break
             it = len(self.loss)
-        for p in self.parameters:
-            if p.v is not None:
-                p.std = STD_FROM_V
+        _mark_std(self.parameters)
         self._scheme = ("amsgrad", 0.25)
         return len(self.loss), -self.loss[-1]
 

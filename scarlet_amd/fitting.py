@@ -10,11 +10,12 @@ import os
 import numpy as np
 
 from .batch import BlendBatch
-from .blend import Blend, _adaprox_options, _flatten
+from .blend import (Blend, _adaprox_options, _at_hook, _flatten, _mark_std, _next_round,
+                    _update_sources)
 from .component import CombinedComponent, FactorizedComponent
 from .model import Model, UpdateException
 from .morphology import ImageMorphology, Morphology, _edge_pull
-from .parameter import Parameter, STD_FROM_V
+from .parameter import Parameter
 from .renderer import ConvolutionRenderer, NullRenderer, ResolutionRenderer
 
 logger = logging.getLogger("scarlet_amd.blend")
@@ -131,9 +132,7 @@ def fit_blends(blends, max_iter=200, e_rel=1e-3, min_iter=1, devices=None, **alg
             if part["lo"] != lo:
                 for blend, state in zip(blends[part["lo"]:], part["states"]):
                     _import_state(blend, state)
-                    for p in blend.parameters:
-                        if p.v is not None:
-                            p.std = STD_FROM_V
+                    _mark_std(blend.parameters)
         return out
     if devices is None or np.isscalar(devices) or len(devices) == 1:
         device = 0 if devices is None else int(devices if np.isscalar(devices) else devices[0])
@@ -198,13 +197,6 @@ def _device_hook_covers(node):
     return False
 
 
-def _next_round(local, budget):
-    """Iterations until the resize hook after local iterations 10, 20, ... has to run (once
-    11, 21, ... iterations of this adaprox call are done), capped by ``budget``."""
-    n_hook = (11 if local == 0 else ((local - 1) // 10 + 1) * 10 + 1) - local
-    return min(n_hook, budget)
-
-
 def _fit_group_rebuilt(group, device, max_iter, opt, step_kw):
     """Blends that share the frame and kernel shapes, with components the resident path does
     not cover (point sources, free shifts): a device batch per round and iteration counter,
@@ -246,15 +238,8 @@ def _fit_group_rebuilt(group, device, max_iter, opt, step_kw):
                 if state == 3:
                     r.result = ArithmeticError("parameters of the blend are not finite")
                     continue
-                hook = done == n and local + done > 1 and (local + done - 1) % 10 == 0
                 r.local = local + done
-                restart = False
-                if hook:
-                    for src in blend.sources:
-                        try:
-                            src.update()
-                        except UpdateException:
-                            restart = True
+                restart = done == n and _at_hook(r.local) and _update_sources(blend.sources)
                 if restart:
                     r.base, r.local = len(blend.loss), 0
                 elif state == 2 or r.total >= max_iter:
@@ -406,7 +391,7 @@ def _fit_group_resident(group, device, max_iter, opt, step_kw):
             # failed / stopped by its own rule / paused: goes on
             state[live] = np.where(now[live] == 3, 3, np.where(stopped[live], 2, 0))
             pushed = (now.astype(np.int32), now_push[1])  # (what the device holds now)
-            hook = live & (now != 3) & (done == quota) & (local > 1) & ((local - 1) % 10 == 0)
+            hook = live & (now != 3) & (done == quota) & _at_hook(local)
             if not hook.any() or not resizable.any():
                 continue
             # candidates by the device's reductions; 1e-6: the host decides what is close
@@ -646,8 +631,6 @@ def _fit_blends_on(blends, device, max_iter=200, e_rel=1e-3, min_iter=1, _from_f
             errors.append((i, r.result))
             out.append((len(blend.loss), float("nan")))
             continue
-        for p in blend.parameters:
-            if p.v is not None:
-                p.std = STD_FROM_V
+        _mark_std(blend.parameters)
         out.append((len(blend.loss), -blend.loss[-1]))
     return out, errors

@@ -15,7 +15,6 @@ import threading
 import numpy as np
 
 from ..batch import BlendBatch, fft_shape_for
-from .models import LiteBlend
 
 # rocFFT batches of transposed complex shapes must not be alive on one device at the same
 # time (smi_batch_create, plans_enter): with several host threads on one device, the
@@ -46,8 +45,9 @@ def _conv_plan(h, w, kernel_shape):
 
 
 def _check(blend, max_iter, e_rel):
-    """The refusals of ``LiteBlend.fit`` (and of this driver) for one blend, before any GPU
-    work.  Returns the group key of a blend that runs, or None for one ``fit`` leaves alone."""
+    """The refusals of ``LiteBlend.fit`` for one blend, before any GPU work.  Returns the group
+    key of a blend that runs, or None when there is nothing to run (no components, or the
+    counter is at ``max_iter``)."""
     if not blend.components:
         return None
     kind = blend._kind()
@@ -63,9 +63,6 @@ def _check(blend, max_iter, e_rel):
     if kernel is not None and any(s % 2 == 0 for s in kernel.image.shape[1:]):
         raise NotImplementedError("difference kernels need odd stamps (the flipped kernel "
                                   "of an even stamp is not the transposed convolution)")
-    if any(int(o) != 0 for o in tuple(obs.bbox.origin)[1:]):
-        raise NotImplementedError("observations whose bbox has a non-zero spatial origin are "
-                                  "not supported by lite.fit_blends")
     C, h, w = obs.images.shape
     kshape = None if kernel is None else tuple(kernel.image.shape)
     return (kind, tuple(sorted(settings.items())),
@@ -74,8 +71,8 @@ def _check(blend, max_iter, e_rel):
 
 
 def _upload(blends, kind, key, capacity, device):
-    """One BlendBatch of the group's blends, padded to the largest frame, with their
-    parameters, optimizer state and previous losses."""
+    """One BlendBatch of the group's blends, padded to the largest frame (frame extents only
+    when their frames differ), with their parameters, optimizer state and previous losses."""
     _, settings, opt, C, kshape, _, _, (path, fy, fx, _) = key
     shapes = [b.observation.images.shape[1:] for b in blends]
     H, W = max(s[0] for s in shapes), max(s[1] for s in shapes)
@@ -94,15 +91,16 @@ def _upload(blends, kind, key, capacity, device):
     batch = BlendBatch(
         data, weights, [[b._spec(c, kind) for c in b.components] for b in blends],
         max_iter=max(capacity, 1), scheme="fista" if kind == "fista" else "amsgrad",
-        log_norm=False, device=device, frame_shapes=shapes, **kw)
+        log_norm=False, device=device,
+        frame_shapes=shapes if len(set(shapes)) > 1 else None, **kw)
     try:
         if kind == "fista":
             batch.set_fista_state(z_sed=np.stack([c._sed.z for c in comps]),
                                   z_morph=[c._morph.z for c in comps],
                                   t=[(c._sed.t, c._morph.t) for c in comps])
         else:
-            def finite(a):  # as LiteBlend._upload: vhat starts at -inf
-                return np.where(np.isfinite(a), a, 0)
+            def finite(a):  # vhat starts at -inf (lite/parameters.py:267-269): any value
+                return np.where(np.isfinite(a), a, 0)  # below v is equivalent
 
             batch.set_moments(
                 m_sed=np.stack([c._sed.m for c in comps]), v_sed=np.stack([c._sed.v for c in comps]),
@@ -119,28 +117,21 @@ def _upload(blends, kind, key, capacity, device):
 
 
 def _download(batch, blends, members, kind, offsets):
-    """LiteBlend._download for the blends at positions ``members`` of the batch."""
+    """Parameters and FISTA / AMSGrad state of the blends at positions ``members`` of the
+    batch, from the device."""
     seds, morphs = batch.parameters()
     st = batch.fista_state() if kind == "fista" else batch.moments()
     for j in members:
-        sub = _Slice(seds, morphs, st, offsets[j])
-        LiteBlend._download(blends[j], sub, kind)
-
-
-class _Slice:
-    """What ``LiteBlend._download`` reads from a batch, for one blend's components."""
-
-    def __init__(self, seds, morphs, st, k0):
-        self._p = (seds[k0:], morphs[k0:])
-        self._st = {n: a[k0:] for n, a in st.items()}
-
-    def parameters(self):
-        return self._p
-
-    def fista_state(self):
-        return self._st
-
-    moments = fista_state
+        for k, c in enumerate(blends[j].components, offsets[j]):
+            c._sed.x = seds[k].astype(c._sed.x.dtype)
+            c._morph.x = morphs[k].astype(c._morph.x.dtype)
+            if kind == "fista":
+                c._sed.z, c._morph.z = st["z_sed"][k].copy(), st["z_morph"][k].copy()
+                c._sed.t, c._morph.t = float(st["t"][k][0]), float(st["t"][k][1])
+            else:
+                c._sed.m, c._sed.v, c._sed.vhat = (st[n][k].copy() for n in ("m_sed", "v_sed", "vhat_sed"))
+                c._morph.m, c._morph.v, c._morph.vhat = (
+                    st[n][k].copy() for n in ("m_morph", "v_morph", "vhat_morph"))
 
 
 def _fit_group(blends, key, max_iter, e_rel, min_iter, resize, device):
@@ -178,8 +169,8 @@ def _fit_group(blends, key, max_iter, e_rel, min_iter, resize, device):
                         continue
                     converged = states[j] == 2
                     if converged:
-                        # as LiteBlend.fit: the stopping rule fired in iteration
-                        # it + n_done - 1, before the counter was incremented
+                        # the stopping rule fired in iteration it + n_done - 1; the
+                        # reference breaks before incrementing the counter
                         ended_at[j] = it + int(after[j] - before[j]) - 1
                         running.remove(j)
                         ended = ended_at[j]
@@ -233,7 +224,14 @@ def _fit_on(blends, keys, device, max_iter, e_rel, min_iter, resize):
 def group_keys(blends, max_iter, e_rel=1e-4):
     """The device group of every blend (None: nothing to fit), in input order: what
     ``fit_blends`` batches together.  Raises the refusals ``fit_blends`` raises."""
-    return [_check(b, max_iter, e_rel) for b in blends]
+    keys = []
+    for b in blends:
+        key = _check(b, max_iter, e_rel)
+        if key is not None and any(int(o) != 0 for o in tuple(b.observation.bbox.origin)[1:]):
+            raise NotImplementedError("observations whose bbox has a non-zero spatial origin are "
+                                      "not supported by lite.fit_blends")
+        keys.append(key)
+    return keys
 
 
 def fit_blends(blends, max_iter, e_rel=1e-4, min_iter=1, resize=10, reweight=True, devices=None):
@@ -261,7 +259,7 @@ def fit_blends(blends, max_iter, e_rel=1e-4, min_iter=1, resize=10, reweight=Tru
     fit_blends.errors = []
     if isinstance(devices, str):
         raise ValueError("devices must be None, an int or a list of GPU indices")
-    keys = [_check(b, max_iter, e_rel) for b in blends]
+    keys = group_keys(blends, max_iter, e_rel)
     if devices is None or np.isscalar(devices):
         devices = [0 if devices is None else int(devices)]
     devices = [int(d) for d in devices]

@@ -410,104 +410,19 @@ class LiteBlend:
             raise NotImplementedError("only scheme='amsgrad' runs on the device")
         return dict(prox_max_iter=max_prox_iter, prox_e_rel=e_rel), dict(b1=b1, b2=b2, eps=eps)
 
-    def _upload(self, kind, capacity):
-        obs = self.observation
-        if obs.diff_kernel is not None and any(s % 2 == 0 for s in obs.diff_kernel.image.shape[1:]):
-            raise NotImplementedError("difference kernels need odd stamps (the flipped kernel "
-                                      "of an even stamp is not the transposed convolution)")
-        batch = BlendBatch(
-            obs.images[None], obs.weights[None], [[self._spec(c, kind) for c in self.components]],
-            kernel=None if obs.diff_kernel is None else obs.diff_kernel.image,
-            max_iter=max(capacity, 1), scheme="fista" if kind == "fista" else "amsgrad",
-            log_norm=False)
-        comps = self.components
-        if kind == "fista":
-            batch.set_fista_state(z_sed=np.stack([c._sed.z for c in comps]),
-                                  z_morph=[c._morph.z for c in comps],
-                                  t=[(c._sed.t, c._morph.t) for c in comps])
-        else:
-            def finite(a):  # vhat starts at -inf (lite/parameters.py:267-269): any value
-                return np.where(np.isfinite(a), a, 0)  # below v is equivalent
-
-            batch.set_moments(
-                m_sed=np.stack([c._sed.m for c in comps]), v_sed=np.stack([c._sed.v for c in comps]),
-                vhat_sed=np.stack([finite(c._sed.vhat) for c in comps]),
-                m_morph=[c._morph.m for c in comps], v_morph=[c._morph.v for c in comps],
-                vhat_morph=[finite(c._morph.vhat) for c in comps])
-        return batch
-
-    def _download(self, batch, kind):
-        seds, morphs = batch.parameters()
-        if kind == "fista":
-            st = batch.fista_state()
-        else:
-            st = batch.moments()
-        for k, c in enumerate(self.components):
-            c._sed.x = seds[k].astype(c._sed.x.dtype)
-            c._morph.x = morphs[k].astype(c._morph.x.dtype)
-            if kind == "fista":
-                c._sed.z, c._morph.z = st["z_sed"][k].copy(), st["z_morph"][k].copy()
-                c._sed.t, c._morph.t = float(st["t"][k][0]), float(st["t"][k][1])
-            else:
-                c._sed.m, c._sed.v, c._sed.vhat = (st[n][k].copy() for n in ("m_sed", "v_sed", "vhat_sed"))
-                c._morph.m, c._morph.v, c._morph.vhat = (
-                    st[n][k].copy() for n in ("m_morph", "v_morph", "vhat_morph"))
-
     def fit(self, max_iter, e_rel=1e-4, min_iter=1, resize=10, reweight=True):
         """Fit all parameters; returns ``(it, loss[-1])`` like the reference
         (lite/models.py:589-624): per iteration the likelihood gradient (loss appended,
         ``-1/2 sum w (d - m)^2``), the update of every component (spectrum first), every
         ``resize`` iterations the box check, then ``it > min_iter and |dL| < e_rel |L|``.
-        The iteration counter persists in ``self.it`` across calls."""
+        The iteration counter persists in ``self.it`` across calls.  The loop is that of
+        ``lite.fit_blends`` (lite/fitting.py), for a group of one blend."""
+        from .fitting import _check, _fit_group
         from .measure import weight_sources
 
-        it = self.it
-        converged = not self.components
-        kind = None if converged else self._kind()
-        while it < max_iter and not converged:
-            settings, opt = self._optimizer(kind)
-            if settings["prox_max_iter"] != 1 and settings["prox_e_rel"] != e_rel:
-                raise NotImplementedError(
-                    "more than one proximal sub-iteration needs prox_e_rel == e_rel")
-            batch = self._upload(kind, max_iter - it)
-            if opt:
-                batch.set_optimizer(**opt)
-            if self.loss:
-                batch.set_previous_loss(-self.loss[-1])
-            resized = False
-            try:
-                while it < max_iter and not converged and not resized:
-                    # iterations up to and including the next one that ends with a box check
-                    if resize is None:
-                        last = max_iter - 1
-                    else:
-                        last = min(max(-(-it // resize), 1) * resize, max_iter - 1)
-                    n = last - it + 1
-                    before = len(batch.loss_history()[0])
-                    batch.step(it, n, e_rel=e_rel, min_iter=min_iter,
-                               prox_max_iter=settings["prox_max_iter"], check_convergence=True)
-                    active, err = batch.status()
-                    if err >= 0:
-                        raise ArithmeticError("parameters of the blend are not finite")
-                    n_done = len(batch.loss_history()[0]) - before
-                    if active == 0:
-                        # the stopping rule fired in iteration it + n_done - 1; the
-                        # reference breaks before incrementing the counter
-                        it += n_done - 1
-                        converged = True
-                    else:
-                        it += n
-                    ended = it if converged else it - 1
-                    if resize is not None and ended > 0 and ended % resize == 0:
-                        self._download(batch, kind)
-                        resized = any([c.resize() for c in self.components
-                                       if hasattr(c, "resize")])
-                self.loss += [-float(v) for v in batch.loss_history()[0]]
-                if not resized:
-                    self._download(batch, kind)
-            finally:
-                batch.close()
-        self.it = it
+        key = _check(self, max_iter, e_rel)  # (None: nothing to run)
+        if key is not None and _fit_group([self], key, max_iter, e_rel, min_iter, resize, 0):
+            raise ArithmeticError("parameters of the blend are not finite")
         if reweight:
             weight_sources(self)
-        return it, self.loss[-1]
+        return self.it, self.loss[-1]
