@@ -612,7 +612,9 @@ int smi_batch_get_lowres_rendered(smi_batch *b, int32_t index, float *out);
 /* starlet_transform (wavelet.py:220-266) of n images [n][H][W] at once: coefficients
  * d_coeffs[scales+1][n][H][W] in float64 whatever the input type, generation 1 or 2, bit for
  * bit the reference's.  d_work: n*H*W doubles of scratch.  Device pointers; the work is
- * enqueued on `stream` (hipStream_t, NULL = default stream) and not waited for. */
+ * enqueued on `stream` (hipStream_t, NULL = default stream) and not waited for.
+ * 0 <= scales <= 30 and n*H <= INT32_MAX, whatever H and W: a spacing 2^j of max(H, W) or more
+ * reaches no neighbour and leaves the centre tap. */
 int smi_starlet_transform_f32(const float *d_images, int32_t n, int32_t H, int32_t W,
                               int32_t scales, int32_t generation, double *d_coeffs,
                               double *d_work, void *stream);

@@ -22,6 +22,7 @@
 // The multiresolution support ("ground" branch, wavelet.py:381-407) runs its per-plane
 // standard deviations on the device as deterministic two-pass float64 reductions; the
 // convergence test on a handful of numbers per iteration stays on the host.
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -49,19 +50,23 @@ template <int AXIS>
 __global__ __launch_bounds__(kT) void bspline_pass_kernel(const double *__restrict__ in, int rows,
                                                          int H, int W, int d, double *out,
                                                          const double *addend, double *diff) {
-    const int x = blockIdx.x * kT + threadIdx.x;
+    // 64-bit throughout: the last block's x, row + gridDim.y, u + 2d and the offsets 2d * W
+    // all pass INT32_MAX for sizes the entry points admit (rows and W up to INT32_MAX, d up
+    // to max(H, W))
+    const int64_t x = (int64_t)blockIdx.x * kT + threadIdx.x;
     if (x >= W) return;
-    for (int row = blockIdx.y; row < rows; row += gridDim.y) {
-        const int64_t p = (int64_t)row * W + x;
-        const int u = AXIS == 0 ? row % H : x;
-        const int L = AXIS == 0 ? H : W;
+    for (int64_t row = blockIdx.y; row < rows; row += gridDim.y) {
+        const int64_t p = row * W + x;
+        const int64_t u = AXIS == 0 ? row % H : x;
+        const int64_t L = AXIS == 0 ? H : W;
         const int64_t s = AXIS == 0 ? (int64_t)W : 1;
+        const int64_t d1 = d, d2 = 2 * d1;
         const double *c = in + p;
         double acc = c[0] * H2;
-        if (u >= 2 * d) acc = acc + c[-2 * d * s] * H0;
-        if (u >= d) acc = acc + c[-d * s] * H1;
-        if (u + d < L) acc = acc + c[d * s] * H3;
-        if (u + 2 * d < L) acc = acc + c[2 * d * s] * H4;
+        if (u >= d2) acc = acc + c[-d2 * s] * H0;
+        if (u >= d1) acc = acc + c[-d1 * s] * H1;
+        if (u + d1 < L) acc = acc + c[d1 * s] * H3;
+        if (u + d2 < L) acc = acc + c[d2 * s] * H4;
         if (out) out[p] = addend ? acc + addend[p] : acc;
         if (diff) diff[p] = diff[p] - acc;
     }
@@ -172,7 +177,7 @@ int have_device() {
 template <int AXIS>
 int bspline_pass(const double *in, int rows, int H, int W, int d, double *out,
                  const double *addend, double *diff, hipStream_t st) {
-    const dim3 grid((W + kT - 1) / kT, rows < kMaxGridY ? rows : kMaxGridY);
+    const dim3 grid((unsigned)(((int64_t)W + kT - 1) / kT), rows < kMaxGridY ? rows : kMaxGridY);
     hipLaunchKernelGGL(bspline_pass_kernel<AXIS>, grid, dim3(kT), 0, st, in, rows, H, W, d, out,
                        addend, diff);
     SMI_HIP(hipGetLastError());
@@ -182,7 +187,9 @@ int bspline_pass(const double *in, int rows, int H, int W, int d, double *out,
 // B_j(in) -> out (+ addend) and/or diff -= B_j(in); `tmp` holds the axis-0 pass
 int bspline(const double *in, int rows, int H, int W, int j, double *tmp, double *out,
             const double *addend, double *diff, hipStream_t st) {
-    const int d = 1 << j;
+    // a spacing of max(H, W) or more reaches no neighbour along either axis, the same
+    // result as 2^j (j <= 30 is admitted); the kernel forms 2 * d in 64 bits
+    const int d = std::min(1 << j, std::max(H, W));
     int rc = bspline_pass<0>(in, rows, H, W, d, tmp, nullptr, nullptr, st);
     if (rc) return rc;
     return bspline_pass<1>(tmp, rows, H, W, d, out, addend, diff, st);

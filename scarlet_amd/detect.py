@@ -159,7 +159,7 @@ def get_wavelets(images, variance, scales=3):
     device."""
     images = np.asarray(images)
     sigma = np.median(np.sqrt(variance), axis=(1, 2))
-    scales = wavelet.get_scales(images.shape, scales)
+    scales = wavelet._checked_scales(images.shape, scales)
     d_coeffs = wavelet.transform_device(wavelet._upload(images), scales)
     P = scales + 1
     s0, t0 = zip(*(wavelet.initial_sigma(images[b].dtype, P, sigma[b], 3)
@@ -174,8 +174,8 @@ def get_detect_wavelets(images, variance, scales=3):
     support on the device, one copy of the result to the host."""
     images = np.asarray(images)
     sigma = np.median(np.sqrt(variance))
+    scales = wavelet._checked_scales(images.shape, scales)
     detect = wavelet.coadd_device(wavelet._upload(images))
-    scales = wavelet.get_scales(detect.shape, scales)
     d_coeffs = wavelet.transform_device(detect[None], scales)
     dtype = np.float32 if images.dtype == np.float32 else np.float64
     s0, t0 = wavelet.initial_sigma(dtype, scales + 1, sigma, 3)

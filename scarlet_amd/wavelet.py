@@ -39,6 +39,18 @@ def get_scales(image_shape, scales=None):
     return int(scales)
 
 
+def _checked_scales(image_shape, scales=None):
+    """``get_scales``, refusing what leaves no coefficient plane: an image one pixel high or
+    wide (``get_scales`` gives -1) or a negative ``scales``.  The reference fails there too
+    (``np.zeros`` of a negative or empty first axis); this raises before any device call."""
+    scales = get_scales(image_shape, scales)
+    if scales < 0:
+        raise ValueError(
+            "starlet transform needs scales >= 0, got %d for an image of shape %s (an image "
+            "must be at least 2 pixels high and wide)" % (scales, tuple(image_shape[-2:])))
+    return scales
+
+
 # ---------------------------------------------------------------------------
 # device plumbing: torch tensors hold the device buffers, the library does the work
 # ---------------------------------------------------------------------------
@@ -181,7 +193,7 @@ def starlet_transform(image, scales=None, generation=2, convolve2D=None):
     ``c_scales``.  ``convolve2D=None``: the B-spline on the device."""
     assert len(image.shape) == 2, f"Image should be 2D, got {len(image.shape)}"
     assert generation in (1, 2), f"generation should be 1 or 2, got {generation}"
-    scales = get_scales(image.shape, scales)
+    scales = _checked_scales(image.shape, scales)
     if convolve2D is not None:
         return _host_transform(image, scales, generation, convolve2D)
     d = _upload(image)
@@ -195,7 +207,7 @@ def multiband_starlet_transform(image, scales=None, generation=2, convolve2D=Non
     assert len(image.shape) == 3, \
         f"Image should be 3D (bands, height, width), got shape {len(image.shape)}"
     assert generation in (1, 2), f"generation should be 1 or 2, got {generation}"
-    scales = get_scales(image.shape, scales)
+    scales = _checked_scales(image.shape, scales)
     if convolve2D is not None:
         out = np.empty((scales + 1,) + image.shape, dtype=image.dtype)
         for b, band in enumerate(image):

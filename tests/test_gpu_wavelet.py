@@ -5,39 +5,9 @@ import numpy as np
 import pytest
 
 from conftest import golden
+from wavelet_oracle import bspline as np_bspline, transform as np_transform
 
 pytestmark = pytest.mark.gpu
-
-
-def np_bspline(image, j):
-    """B_j in float64, the reference's order of additions (restated for the test)"""
-    d = 2 ** j
-    taps = (1.0 / 16, 1.0 / 4, 3.0 / 8, 1.0 / 4, 1.0 / 16)
-
-    def one(x):  # along axis 0
-        n = x.shape[0]
-        out = x * taps[2]
-        if 2 * d < n:
-            out[2 * d:] += x[:n - 2 * d] * taps[0]
-        if d < n:
-            out[d:] += x[:n - d] * taps[1]
-            out[:n - d] += x[d:] * taps[3]
-        if 2 * d < n:
-            out[:n - 2 * d] += x[2 * d:] * taps[4]
-        return out
-
-    return one(one(np.asarray(image, dtype=np.float64)).T).T
-
-
-def np_transform(image, scales, generation=2):
-    c = np.asarray(image, dtype=np.float64)
-    out = np.zeros((scales + 1,) + c.shape)
-    for j in range(scales):
-        nxt = np_bspline(c, j)
-        out[j] = c - (np_bspline(nxt, j) if generation == 2 else nxt)
-        c = nxt
-    out[-1] = c
-    return out
 
 
 def unpack(bits, shape):
