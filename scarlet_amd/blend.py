@@ -164,9 +164,11 @@ def _step_rule(step, what):
 # -- the rules of the adaprox round loop (blend.py:276-302), for every fit that runs one
 def _next_round(local, budget):
     """Iterations until the resize hook after local iterations 10, 20, ... has to run (once
-    11, 21, ... iterations of this adaprox call are done), capped by ``budget``."""
-    n_hook = (11 if local == 0 else ((local - 1) // 10 + 1) * 10 + 1) - local
-    return min(n_hook, budget)
+    11, 21, ... iterations of this adaprox call are done), capped by ``budget``.  Ints, or
+    arrays with one entry per blend of a batch."""
+    n_hook = np.where(local == 0, 11, ((local - 1) // 10 + 1) * 10 + 1 - local)
+    n = np.minimum(n_hook, budget)
+    return n if n.ndim else int(n)
 
 
 def _at_hook(done):
@@ -1206,12 +1208,10 @@ class Blend(CombinedComponent):
 
 
 def __getattr__(name):
-    """``fit_blends`` and its helpers live in ``scarlet_amd.fitting`` (which imports this module);
-    the names they had here keep working: ``from scarlet_amd.blend import fit_blends``."""
-    if name in ("fit_blends", "_fit_blends_on", "_fit_group_resident", "_fit_group_rebuilt",
-                "_device_resize_covers", "_device_hook_covers", "_resized_spec", "_refresh_boxes",
-                "_export_state", "_import_state", "_standard_size"):
-        from . import fitting
+    """``fit_blends`` lives in ``scarlet_amd.fitting`` (which imports this module); the name it
+    had here keeps working: ``from scarlet_amd.blend import fit_blends``."""
+    if name == "fit_blends":
+        from .fitting import fit_blends
 
-        return getattr(fitting, name)
+        return fit_blends
     raise AttributeError("module {!r} has no attribute {!r}".format(__name__, name))

@@ -2,10 +2,20 @@
 kernel shapes (reference: the per-blend loop of scarlet/testing/api.py:216-224, every blend through
 ``Blend.fit``, blend.py:85-198).  The batch stays on the device for the whole call: resize test
 and resize on the device, every blend at its own iteration counter and pausing at its own
-hooks (``_fit_group_resident``); ``Blend.fit`` takes the same path for one blend."""
+hooks; ``Blend.fit`` takes the same path for one blend.
+
+``_fit_blends_on`` sorts the blends (``_classify``) into those ``Blend.fit``'s own loop has to
+fit and groups of equal shapes, each opened by ``_open_batch``.  ``_fit_group_resident`` is the
+loop of a group; what it decides is plain NumPy on plain arrays, tested without a device: how
+far every blend runs in the next launch (``_plan_round``, on ``blend._next_round``), which boxes
+shrink or grow and to which size (``_resize_candidates``, on the rules of ``morphology.py``), the
+rows the device resizes by itself (``_device_rows``).  ``_host_visit`` runs ``update()`` of the
+sources the device does not stand for, ``_component_table`` holds what the loop tracks per
+component and ``_write_back`` brings the device's state to the Python objects."""
 
 import logging
 import os
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -14,7 +24,8 @@ from .blend import (Blend, _adaprox_options, _at_hook, _flatten, _mark_std, _nex
                     _update_sources)
 from .component import CombinedComponent, FactorizedComponent
 from .model import Model, UpdateException
-from .morphology import ImageMorphology, Morphology, _edge_pull
+from .morphology import (ImageMorphology, Morphology, _edge_pull, _margin_of_empty,
+                         get_minimal_boxsize)
 from .parameter import Parameter
 from .renderer import ConvolutionRenderer, NullRenderer, ResolutionRenderer
 
@@ -197,6 +208,26 @@ def _device_hook_covers(node):
     return False
 
 
+def _open_batch(runs, specs, flat, capacity, device, opt):
+    """The device batch of a group of blends that share the frame and kernel shapes: their
+    observation cubes stacked, the components ``flat`` described by ``specs`` (per blend),
+    room for ``capacity`` losses per blend, the blends' loss constants, the state stored on the
+    Parameters and the optimizer constants ``opt``."""
+    data, weights, kernel = zip(*(r.obs for r in runs))
+    batch = BlendBatch(np.stack(data), np.stack(weights), specs,
+                       kernel=None if kernel[0] is None else np.stack(kernel),
+                       max_iter=capacity, device=device)
+    try:
+        if any(r.blend._loss_constant for r in runs):
+            batch.add_loss_constant([r.blend._loss_constant for r in runs])
+        Blend._upload_state(batch, flat)
+        batch.set_optimizer(**opt)
+    except BaseException:
+        batch.close()
+        raise
+    return batch
+
+
 def _fit_group_rebuilt(group, device, max_iter, opt, step_kw):
     """Blends that share the frame and kernel shapes, with components the resident path does
     not cover (point sources, free shifts): a device batch per round and iteration counter,
@@ -210,19 +241,11 @@ def _fit_group_rebuilt(group, device, max_iter, opt, step_kw):
             by_local.setdefault(r.local, []).append(r)
         for local, part in by_local.items():
             comps = [_flatten(r.blend.sources) for r in part]
+            flat = [c for cs in comps for c in cs]
             n = _next_round(local, min(max_iter - r.total for r in part))
-            kernel = part[0].obs[2]
-            batch = BlendBatch(
-                np.stack([r.obs[0] for r in part]), np.stack([r.obs[1] for r in part]),
-                [r.blend._specs(c) for r, c in zip(part, comps)],
-                kernel=None if kernel is None else np.stack([r.obs[2] for r in part]),
-                max_iter=n, device=device)
+            batch = _open_batch(part, [r.blend._specs(c) for r, c in zip(part, comps)], flat, n,
+                                device, opt)
             try:
-                flat = [c for cs in comps for c in cs]
-                if any(r.blend._loss_constant for r in part):
-                    batch.add_loss_constant([r.blend._loss_constant for r in part])
-                Blend._upload_state(batch, flat)
-                batch.set_optimizer(**opt)
                 if local > 0:  # the stopping rule compares with the loss before this round
                     batch.set_previous_loss(np.array([r.blend.loss[-1] for r in part]))
                 batch.step(local, n, check_convergence=True, **step_kw)
@@ -268,225 +291,259 @@ def _device_resize_covers(blend, flat=None):
     return True
 
 
-def _standard_size(size):
-    """``get_minimal_boxsize`` (initialization.py:173-177) of an array of sizes."""
-    return 21 + 10 * np.ceil(np.maximum(size - 21, 0) / 10).astype(np.int64)
+def _component_table(group, comps, host_resize=False):
+    """What the resident loop tracks per component of a group, built once from the Python
+    objects (``comps``: the components of every blend).  ``first``: index of each blend's first
+    component (and the total behind them); ``blend_of`` / ``source_of``: the blend and the
+    source (counted through the group) above a component -- ``update()`` of a source stops at
+    its first child that resizes (component.py:172-185); ``resizable``: may ``update()`` act;
+    ``on_device`` (per blend): the device resizes its boxes by itself (``host_resize``: none
+    does, the development switch).  What the host follows for those: ``origin``, the constant
+    ``step`` of the image (nan for a step rule of its own), ``wide`` (a float64 host image) and
+    ``moved``, set once the device has resized the box."""
+    flat = [c for cs in comps for c in cs]
+    images = [c.children[1]._parameters[0] for c in flat]
+    first = np.concatenate([[0], np.cumsum([len(c) for c in comps])]).astype(np.int64)
+    # (a source is one factorized component or a combined one: no second walk through the tree
+    # for the common case)
+    below = np.array([1 if isinstance(src, FactorizedComponent) else len(_flatten([src]))
+                      for r in group for src in r.blend.sources], dtype=np.int64)
+    return SimpleNamespace(
+        first=first,
+        blend_of=np.repeat(np.arange(len(group)), np.diff(first)),
+        source_of=np.repeat(np.arange(len(below)), below),
+        on_device=np.array([not host_resize and _device_resize_covers(r.blend, cs)
+                            for r, cs in zip(group, comps)], dtype=bool),
+        resizable=np.array([bool(c.children[1].resizing) and not image.fixed
+                            for c, image in zip(flat, images)], dtype=bool),
+        origin=np.array([c.children[1].bbox.origin[-2:] for c in flat],
+                        dtype=np.int64).reshape(-1, 2),
+        step=np.array([float(image.step) if isinstance(image.step, (int, float)) else np.nan
+                       for image in images]),
+        wide=np.array([image.dtype == np.float64 for image in images], dtype=bool),
+        moved=np.zeros(len(flat), dtype=bool))
 
 
-def _fit_group_resident(group, device, max_iter, opt, step_kw):
+def _plan_round(state, left, local, g, lockstep=False):
+    """The next launch of the resident batch, whose iteration counter stands at ``g``, from
+    what is known per blend: ``state`` (0 iterating, 2 finished, 3 failed), the iterations
+    ``left`` of its budget and the ``local`` counter of its adaprox call.  None when no blend
+    is live.  Otherwise ``live``; ``quota``: every live blend runs up to ITS next resize hook
+    or to the end of its budget (``_next_round``) -- the device pauses it there, after counter
+    ``pause_at``, while its batch mates go on in the same ``n`` iterations of the launch;
+    ``states`` (a blend out of budget counts as finished) and counter ``base`` for the device.
+    ``lockstep`` (development switch): all blends to the nearest hook of any of them."""
+    live = (state == 0) & (left > 0)
+    if not live.any():
+        return None
+    quota = _next_round(local, left)
+    if lockstep:
+        quota = np.full(len(local), int(quota[live].min()))
+    return SimpleNamespace(
+        live=live, quota=quota, n=int(quota[live].max()),
+        states=np.where((state == 0) & ~live, 2, state).astype(np.int32),
+        base=np.where(live, g - local, 0), pause_at=np.where(live, g + quota - 1, -1))
+
+
+_NO_PIXEL = np.iinfo(np.int32).max  # margin of an image without a pixel > 0 (scarlet_amd.h)
+
+
+def _resize_candidates(margin, pull, shapes, step, at_hook):
+    """What ``ImageMorphology.update`` (morphology.py:132-207) would do to the components
+    ``at_hook``, from the device's two reductions (``BlendBatch.resize_test``: the empty
+    ``margin`` and the largest ``pull`` over an edge), the box ``shapes`` and the constant
+    ``step`` of every image: ``(shrink, grow, standard, close)``.  ``standard``: the standard
+    size that holds the occupied pixels, the new size of a box that shrinks.  An image with a
+    step rule of its own (``step`` nan) always counts as growing: the device's pull is taken
+    with the constant step, so the host's ``update()`` has to see it.  ``close``: indices of
+    growing components whose pull lies within 1e-6 (relative) of the threshold 0.1; the
+    host's own ``_edge_pull`` has the last word on these."""
+    size = shapes.max(axis=1)
+    margin = np.where(margin == _NO_PIXEL, _margin_of_empty(shapes.min(axis=1)), margin)
+    standard = get_minimal_boxsize(size - 2 * margin)
+    shrink = at_hook & (standard < size)
+    grow = at_hook & ~shrink & ((pull > 0.1 * (1 - 1e-6)) | np.isnan(step))
+    return shrink, grow, standard, np.flatnonzero(grow & (pull < 0.1 * (1 + 1e-6)))
+
+
+def _device_rows(dev, shrink, standard, size, source_of, wide, origin, step):
+    """The rows the device resizes by itself, of the candidates ``dev``: exactly one per
+    source, its first (``CombinedComponent.update`` stops at the first child that resizes).
+    ``(resized, keep)``: what ``BlendBatch.update_components`` takes for them -- ``rows`` with
+    the new ``size`` (``standard`` for a box that shrinks, the next standard size for one
+    that grows), the origin moved by the inset (< 0: the pad of a growing box) and the halved
+    step -- and their ``keep`` codes, 2 for a float32 host image, 3 for a float64 one."""
+    rows = np.flatnonzero(dev)
+    rows = rows[np.unique(source_of[rows], return_index=True)[1]]
+    new_size = np.where(shrink[rows], standard[rows], get_minimal_boxsize(size[rows] + 1))
+    new_origin = origin[rows] + ((size[rows] - new_size) // 2)[:, None]
+    return (dict(rows=rows, origin_y=new_origin[:, 0], origin_x=new_origin[:, 1], size=new_size,
+                 morph_step=step[rows] / 2), np.where(wide[rows], 3, 2))
+
+
+def _host_visit(batch, group, flat, specs, t, wanted, hook):
+    """The blends at a ``hook`` that the device does not resize: the sources with a
+    ``wanted`` component below them get their records from the device and have ``update()``
+    run (``update()`` of the others is a no-op by the device's test; a source is visited as a
+    whole, the reference stops at its first child that resizes) -- the host keeps the last
+    word.  Returns the blends that restart, the rows of the component table that take their
+    state from the host (a component whose image Parameter was replaced: sliced or padded,
+    step halved; ``flat`` and ``specs`` are brought up to date) and their state records."""
+    visit = [i for i in np.flatnonzero(hook & ~t.on_device).tolist()
+             if wanted[t.first[i]:t.first[i + 1]].any()]
+    calls = []  # (blend, source, indices of the components below it)
+    for i in visit:
+        k = int(t.first[i])
+        for src in group[i].blend.sources:
+            n = len(_flatten([src]))
+            if wanted[k:k + n].any():
+                calls.append((i, src, np.arange(k, k + n)))
+            k += n
+    rows, states = [], []
+    if not calls:
+        return rows, rows, states
+    idx = np.concatenate([below for _, _, below in calls])
+    for k, rec in zip(idx, batch.component_states(idx)):
+        _record_to_parameters(flat[k], rec)
+    before = {i: [c.children[1]._parameters[0] for c in flat[t.first[i]:t.first[i + 1]]]
+              for i in visit}
+    changed = set()
+    for i, src, _ in calls:
+        try:
+            src.update()
+        except UpdateException:
+            changed.add(i)
+    for i in sorted(changed):
+        lo = int(t.first[i])
+        flat[lo:t.first[i + 1]] = _flatten(group[i].blend.sources)
+        for j, image in enumerate(before[i]):
+            c = flat[lo + j]
+            if c.children[1]._parameters[0] is not image:
+                specs[i][j] = _resized_spec(specs[i][j], c)
+                rows.append(lo + j)
+                states.append(_parameters_to_record(c))
+    return sorted(changed), rows, states
+
+
+def _write_back(batch, group, flat, t):
+    """Device -> Python objects: new image Parameters (morphology.py:155-163, 180-193) and
+    boxes of the components the device has resized, then all values, moments and the losses
+    recorded since the fit began."""
+    for k in np.flatnonzero(t.moved):
+        morphology = flat[k].children[1]
+        image = morphology._parameters[0]
+        shape = tuple(batch._shapes[k])
+        morphology._parameters = (
+            Parameter(np.zeros(shape, dtype=image.dtype), name=image.name, prior=image.prior,
+                      constraint=image.constraint, step=float(t.step[k]), fixed=image.fixed),
+        ) + morphology._parameters[1:]
+        morphology.bbox.origin = tuple(int(o) for o in t.origin[k])
+        morphology.bbox.shape = shape
+    if t.moved.any():
+        sources = [src for r in group for src in r.blend.sources]
+        for j in np.unique(t.source_of[t.moved]):
+            _refresh_boxes(sources[j])
+    Blend._download_all(batch, flat)
+    history = batch.loss_history()
+    n_loss = batch.progress()[1]
+    for i, r in enumerate(group):
+        r.blend.loss.extend(history[i][:n_loss[i]])
+
+
+def _fit_group_resident(group, device, max_iter, opt, step_kw, mode=None):
     """Blends that share the frame and kernel shapes, factorized image components only: ONE
     device batch for the whole fit, and every launch steps ALL blends that are still
     iterating.  The observation is uploaded once.  A blend whose boxes change starts its
     adaprox call anew (blend.py:276-302) while its batch mates go on: the device keeps the
-    counter at which each blend's call began (``smi_batch_set_iteration_base``).  At a resize
+    counter at which each blend's call began (``smi_batch_set_iteration_base``), and blends
+    whose calls restarted at different times do not stop each other at every hook of any of
+    them (``_plan_round``; 1024 benchmark blends: 12 rounds instead of 32).  At a resize
     hook the device evaluates the two reductions ``ImageMorphology.update`` decides on for
-    every component (``smi_batch_resize_test``); for blends made of the stock classes the
-    resize itself -- centred slice, or zero-padded moments and a ``linear_ramp``-padded
-    image, step halved (morphology.py:132-207) -- also happens on the device
-    (``smi_batch_update_components``, keep = 2 / 3) and the Python objects learn their new
-    boxes when the fit is over.  Other blends in which a box may change come to the host,
-    have their sources' ``update()`` run -- the host keeps the last word -- and go back as
-    new rows of the component table."""
+    every component (``smi_batch_resize_test``, ``_resize_candidates``); for blends made of the
+    stock classes the resize itself -- centred slice, or zero-padded moments and a
+    ``linear_ramp``-padded image, step halved (morphology.py:132-207) -- also happens on the
+    device (``_device_rows``, ``smi_batch_update_components`` with keep = 2 / 3) and the Python
+    objects learn their new boxes when the fit is over (``_write_back``).  Other blends in
+    which a box may change come to the host and go back as new rows of the component table
+    (``_host_visit``, keep = 0).  ``mode``: the development switch of ``_fit_blends_on``.
+
+    When a launch or a host hook raises, what the device holds -- boxes it resized,
+    parameters, moments, the losses of the iterations that ran -- still reaches the Python
+    objects, so that no blend is left with a box its Parameters do not fit."""
     nb = len(group)
     comps = [_flatten(r.blend.sources) for r in group]
+    flat = [c for cs in comps for c in cs]
     specs = [r.specs for r in group]
-    first = np.concatenate([[0], np.cumsum([len(c) for c in comps])]).astype(np.int64)
-    kernel = group[0].obs[2]
-    batch = BlendBatch(
-        np.stack([r.obs[0] for r in group]), np.stack([r.obs[1] for r in group]), specs,
-        kernel=None if kernel is None else np.stack([r.obs[2] for r in group]),
-        max_iter=max(max_iter, 1), device=device)
-    write_back, wrote = None, False
+    t = _component_table(group, comps, host_resize=mode == "host-resize")
+    prior = np.array([len(r.blend.loss) for r in group])  # losses of earlier fits
+    base = np.zeros(nb, dtype=np.int64)
+    local = np.zeros(nb, dtype=np.int64)
+    count = np.zeros(nb, dtype=np.int64)  # losses recorded on the device so far
+    state = np.zeros(nb, dtype=np.int32)  # 0 iterating, 2 finished, 3 failed
+    g = 0  # the batch's iteration counter: blend i is at g - (its counter base) = local[i]
+    pushed = (None, None)  # what the device holds as per-blend states / counter bases
+    batch = _open_batch(group, specs, flat, max(max_iter, 1), device, opt)
     try:
-        flat = [c for cs in comps for c in cs]
-        n_comp = len(flat)
-        if any(r.blend._loss_constant for r in group):
-            batch.add_loss_constant([r.blend._loss_constant for r in group])
-        Blend._upload_state(batch, flat)
-        batch.set_optimizer(**opt)
-        prior = np.array([len(r.blend.loss) for r in group])  # losses of earlier fits
-        base = np.zeros(nb, dtype=np.int64)
-        local = np.zeros(nb, dtype=np.int64)
-        count = np.zeros(nb, dtype=np.int64)  # losses recorded on the device so far
-        state = np.zeros(nb, dtype=np.int32)  # 0 iterating, 2 finished, 3 failed
-        frozen = np.zeros(nb, dtype=bool)  # out of iterations
-        g = 0  # the batch's iteration counter: blend i is at g - (its counter base) = local[i]
-        # per component: may update() act, and does the device test stand for it
-        resizable = np.array([bool(c.children[1].resizing) and not c.children[1]._parameters[0].fixed
-                              for c in flat])
-        blend_of = np.repeat(np.arange(nb), np.diff(first))
-        # blends the device resizes by itself, and what the host tracks for their components
-        on_device = np.array([_device_resize_covers(r.blend, cs) for r, cs in zip(group, comps)])
-        if os.environ.get("SCARLET_AMD_FIT_BLENDS") == "host-resize":  # development aid: A/B runs
-            on_device[:] = False
-        origin = np.array([c.children[1].bbox.origin[-2:] for c in flat], dtype=np.int64).reshape(-1, 2)
-        step = np.array([float(c.children[1]._parameters[0].step)
-                         if isinstance(c.children[1]._parameters[0].step, (int, float)) else np.nan
-                         for c in flat])
-        wide = np.array([c.children[1]._parameters[0].dtype == np.float64 for c in flat])
-        moved = np.zeros(n_comp, dtype=bool)
-        # (update() of a source stops at its first child that resizes, component.py:172-185)
-        # (a source is one factorized component or a combined one: no second walk through the tree
-        # for the common case)
-        source_of = np.concatenate(
-            [np.full(1 if isinstance(src, FactorizedComponent) else len(_flatten([src])), j)
-             for j, src in enumerate(src for r in group for src in r.blend.sources)]).astype(np.int64) \
-            if n_comp else np.zeros(0, dtype=np.int64)
-        def write_back():
-            """Device -> Python objects: new image Parameters (morphology.py:155-163, 180-193)
-            and boxes of the components the device has resized, then all values, moments and
-            the losses recorded since the fit began."""
-            for k in np.flatnonzero(moved):
-                morphology = flat[k].children[1]
-                image = morphology._parameters[0]
-                shape = tuple(batch._shapes[k])
-                morphology._parameters = (
-                    Parameter(np.zeros(shape, dtype=image.dtype), name=image.name, prior=image.prior,
-                              constraint=image.constraint, step=float(step[k]), fixed=image.fixed),
-                ) + morphology._parameters[1:]
-                morphology.bbox.origin = tuple(int(o) for o in origin[k])
-                morphology.bbox.shape = shape
-            if moved.any():
-                sources = [src for r in group for src in r.blend.sources]
-                for j in np.unique(source_of[moved]):
-                    _refresh_boxes(sources[j])
-            Blend._download_all(batch, flat)
-            history = batch.loss_history()
-            n_loss = batch.progress()[1]
-            for i, r in enumerate(group):
-                r.blend.loss.extend(history[i][:n_loss[i]])
-
-        pushed = None  # what the device holds as per-blend states / counter bases
-        lockstep = os.environ.get("SCARLET_AMD_FIT_BLENDS") == "lockstep"
         while True:
-            live = (state == 0) & ~frozen
-            left = max_iter - base - local
-            frozen |= live & (left <= 0)
-            live &= ~frozen
-            if not live.any():
+            plan = _plan_round(state, max_iter - base - local, local, g, mode == "lockstep")
+            if plan is None:
                 break
-            # Every blend up to ITS next resize hook (after 11, 21, ... iterations of its own
-            # adaprox call) or to the end of its budget: the device pauses it there
-            # (smi_batch_set_pause_at) while its batch mates go on in the same launches.  Blends
-            # whose calls restarted at different times no longer stop each other at every hook
-            # of any of them (1024 benchmark blends: 12 rounds instead of 32).
-            n_hook = np.where(local == 0, 11, ((local - 1) // 10 + 1) * 10 + 1 - local)
-            quota = np.minimum(n_hook, left)
-            if lockstep:  # (development aid: all blends to the nearest hook of any of them)
-                quota = np.full(nb, int(quota[live].min()))
-            n = int(quota[live].max())
-            now_push = (np.where(frozen & (state == 0), 2, state).astype(np.int32),
-                        np.where(live, g - local, 0))
-            batch.set_round(
-                now_push[0] if pushed is None or not np.array_equal(pushed[0], now_push[0]) else None,
-                now_push[1] if pushed is None or not np.array_equal(pushed[1], now_push[1]) else None,
-                np.where(live, g + quota - 1, -1))
-            batch.step(g, n, check_convergence=True, **step_kw)
-            g += n
+            live = plan.live
+            batch.set_round(*[new if old is None or not np.array_equal(old, new) else None
+                              for old, new in zip(pushed, (plan.states, plan.base))],
+                            plan.pause_at)
+            batch.step(g, plan.n, check_convergence=True, **step_kw)
+            g += plan.n
             now, cnt, stopped = batch.round()
-            stopped = stopped != 0
             done = cnt - count
             count = cnt.astype(np.int64)
             local[live] += done[live]
             # failed / stopped by its own rule / paused: goes on
-            state[live] = np.where(now[live] == 3, 3, np.where(stopped[live], 2, 0))
-            pushed = (now.astype(np.int32), now_push[1])  # (what the device holds now)
-            hook = live & (now != 3) & (done == quota) & _at_hook(local)
-            if not hook.any() or not resizable.any():
+            state[live] = np.where(now[live] == 3, 3, np.where(stopped[live] != 0, 2, 0))
+            pushed = (now.astype(np.int32), plan.base)
+            hook = live & (now != 3) & (done == plan.quota) & _at_hook(local)
+            if not hook.any() or not t.resizable.any():
                 continue
-            # candidates by the device's reductions; 1e-6: the host decides what is close
             margin, pull = batch.resize_test()
             shapes = np.array(batch._shapes)
-            size = shapes.max(axis=1)
-            inner = size - 2 * np.where(margin == np.iinfo(np.int32).max,
-                                        (shapes.min(axis=1) + 1) // 2, margin)
-            standard = _standard_size(inner)
-            at_hook = hook[blend_of] & resizable
-            shrink = at_hook & (standard < size)
-            # (the device's pull is taken with the constant step of the table: an image with a
-            # step rule of its own is always shown to the host's update())
-            grow = at_hook & ~shrink & ((pull > 0.1 * (1 - 1e-6)) | np.isnan(step))
-            restart = np.zeros(nb, dtype=bool)
-            keep = np.ones(n_comp, dtype=np.int32)
-            states = []
-            resized = None
+            shrink, grow, standard, close = _resize_candidates(
+                margin, pull, shapes, t.step, hook[t.blend_of] & t.resizable)
             # -- blends of the stock classes: the device resizes
-            dev = (shrink | grow) & on_device[blend_of]
-            close = np.flatnonzero(dev & grow & (pull < 0.1 * (1 + 1e-6)))
+            dev = (shrink | grow) & t.on_device[t.blend_of]
+            close = close[dev[close]]
             if close.size:  # the host's own arithmetic on the edges of these few
                 for k, rec in zip(close, batch.component_states(close)):
                     edges = _edge_pull(rec["morph"], rec["m_morph"].astype(np.float64),
-                                       rec["v_morph"].astype(np.float64), step[k])
+                                       rec["v_morph"].astype(np.float64), t.step[k])
                     grow[k] = dev[k] = bool(np.any(edges > 0.1))
-            rows = np.flatnonzero(dev)
-            if rows.size:
-                rows = rows[np.unique(source_of[rows], return_index=True)[1]]  # first of its source
-                new_size = np.where(shrink[rows], standard[rows], _standard_size(size[rows] + 1))
-                inset = (size[rows] - new_size) // 2  # < 0: the pad of a growing box
-                origin[rows] += inset[:, None]
-                step[rows] /= 2
-                moved[rows] = True
-                keep[rows] = np.where(wide[rows], 3, 2)
-                resized = dict(rows=rows, origin_y=origin[rows, 0], origin_x=origin[rows, 1],
-                               size=new_size, morph_step=step[rows])
-                restart[blend_of[rows]] = True
-            # -- the others: only the sources with a candidate below them go over the host:
-            # update() of the others is a no-op by the test above.  (Within a source the
-            # reference stops at the first child that resizes: a source is visited as a whole.)
-            wanted = (shrink | grow) & ~on_device[blend_of]
-            visit = [int(i) for i in np.flatnonzero(hook & ~on_device)
-                     if wanted[first[i]:first[i + 1]].any()]
-            if visit:
-                calls = []  # (blend, source, index of its first component, components)
-                for i in visit:
-                    k = int(first[i])
-                    for src in group[i].blend.sources:
-                        below = _flatten([src])
-                        if wanted[k:k + len(below)].any():
-                            calls.append((i, src, k, below))
-                        k += len(below)
-                idx = np.concatenate([np.arange(k, k + len(below)) for _, _, k, below in calls])
-                for k, rec in zip(idx, batch.component_states(idx)):
-                    _record_to_parameters(flat[k], rec)
-                changed = set()
-                images = {i: [c.children[1]._parameters[0] for c in comps[i]] for i in visit}
-                for i, src, k, below in calls:
-                    try:
-                        src.update()
-                    except UpdateException:
-                        changed.add(i)
-                # new rows of the component table: a component whose image Parameter was
-                # replaced (sliced or padded, step halved) takes its state from the host, all
-                # others keep theirs on the device
-                for i in sorted(changed):
-                    restart[i] = True
-                    before = images[i]
-                    comps[i] = _flatten(group[i].blend.sources)
-                    flat[first[i]:first[i + 1]] = comps[i]
-                    for j, c in enumerate(comps[i]):
-                        if c.children[1]._parameters[0] is before[j]:
-                            continue
-                        specs[i][j] = _resized_spec(specs[i][j], c)
-                        keep[first[i] + j] = 0
-                        states.append(_parameters_to_record(c))
+            if not (shrink | grow).any():
+                continue
+            resized, codes = _device_rows(dev, shrink, standard, shapes.max(axis=1),
+                                          t.source_of, t.wide, t.origin, t.step)
+            rows = resized["rows"]
+            t.origin[rows, 0], t.origin[rows, 1] = resized["origin_y"], resized["origin_x"]
+            t.step[rows], t.moved[rows] = resized["morph_step"], True
+            # -- the others: over the host
+            changed, from_host, states = _host_visit(
+                batch, group, flat, specs, t, (shrink | grow) & ~t.on_device[t.blend_of], hook)
+            restart = np.zeros(nb, dtype=bool)
+            restart[t.blend_of[rows]] = restart[changed] = True
             if not restart.any():
                 continue
-            batch.update_components(specs, keep, states, resized=resized)
+            keep = np.ones(len(flat), dtype=np.int32)
+            keep[rows], keep[from_host] = codes, 0
+            batch.update_components(specs, keep, states, resized=resized if rows.size else None)
             # adaprox starts anew (a restarted blend that was about to stop goes on)
             base[restart] = prior[restart] + count[restart]
             local[restart] = 0
             state[restart & (state == 2)] = 0
-        write_back()
-        wrote = True
+        _write_back(batch, group, flat, t)
     except BaseException:
-        # a launch or a host hook raised: what the device holds -- boxes it resized, parameters,
-        # moments, the losses of the iterations that ran -- still reaches the Python objects, so
-        # that no blend is left with a box its Parameters do not fit
-        if write_back is not None and not wrote:
-            try:
-                write_back()
-            except Exception:
-                pass
+        # (an error of the regular write-back itself included: it is tried once more)
+        try:
+            _write_back(batch, group, flat, t)
+        except Exception:
+            pass
         raise
     finally:
         batch.close()
@@ -532,105 +589,108 @@ def _parameters_to_record(comp):
                 morph=np.asarray(image), m_morph=image.m, v_morph=image.v, vhat_morph=image.vhat)
 
 
+class _Run:
+    """A blend in a device batch: its observation cubes, the device description of its
+    components, and where its fit stands."""
+
+    def __init__(self, blend, obs, specs):
+        # `base + local` is the reference's `it`: 0 at the start of fit(), the length
+        # of the whole loss history after a restart (blend.py:101, 198)
+        self.blend, self.obs, self.specs = blend, obs, specs
+        self.base, self.local, self.result = 0, 0, None
+
+    @property
+    def total(self):
+        return self.base + self.local
+
+
+def _classify(blend):
+    """``(why, run)`` of a blend of ``fit_blends``: ``why`` it has to be fitted by itself, in
+    ``Blend.fit``'s own loop -- like ``[b.fit() for b in blends]`` would
+    (scarlet/testing/api.py:216-224) -- or None and its ``_Run`` in a device batch."""
+    blend._psf, blend._scheme = None, ("amsgrad", 0.25)  # nothing left over from an earlier fit()
+    if any(not p.fixed for obs in blend.observations for p in obs.parameters):
+        return "free renderer parameters (psf_shift)", None
+    if any(type(obs.renderer) not in (NullRenderer, ConvolutionRenderer, ResolutionRenderer)
+           for obs in blend.observations):
+        return "a user-defined renderer: Blend.fit's host-rendered mode", None
+    obs = blend._observation()  # (built once: the data, weight and kernel cubes)
+    if blend._lowres or blend._extra_layers:
+        # a ResolutionRenderer observation / several observations of one channel are terms of
+        # ONE blend's loss on the device (smi_batch_attach_lowres, smi_batch_add_observation)
+        return "several terms in its loss", None
+    specs = blend._specs(_flatten(blend.sources))  # (once: 15 us per component)
+    if blend._host:  # (hoststep.py: one iteration per device call)
+        return "parameters the host updates", None
+    return None, _Run(blend, obs, specs)
+
+
+def _fit_alone(blend, device, *args, **kwargs):
+    """``Blend.fit`` on GPU ``device``; an ArithmeticError is returned instead of raised."""
+    blend.device = device
+    try:
+        return blend.fit(*args, **kwargs)
+    except ArithmeticError as e:
+        return e
+
+
+def _assemble(blends, fitted):
+    """(results, [(index, error)]) of ``fit_blends`` from what is there per blend: what its own
+    ``Blend.fit`` returned, the ArithmeticError that ended its fit, or its ``_Run``."""
+    out, errors = [], []
+    for i, (blend, res) in enumerate(zip(blends, fitted)):
+        if isinstance(res, _Run):
+            res = res.result
+            if not isinstance(res, Exception):
+                _mark_std(blend.parameters)
+                res = (len(blend.loss), -blend.loss[-1])
+        if isinstance(res, Exception):
+            errors.append((i, res))
+            res = (len(blend.loss), float("nan"))
+        out.append(res)
+    return out, errors
+
+
 def _fit_blends_on(blends, device, max_iter=200, e_rel=1e-3, min_iter=1, _from_fit=False,
                    **alg_kwargs):
     """``fit_blends`` of ``blends`` on GPU ``device``: (results, [(index, error)]).
     ``_from_fit``: the call comes from ``Blend.fit`` itself, which keeps a blend that has to be
-    fitted by its own loop (``None, None`` is returned then)."""
+    fitted by its own loop (``None, None`` is returned then).  The environment variable
+    ``SCARLET_AMD_FIT_BLENDS`` is a development switch for A/B runs, read here once per call:
+    ``rebuild`` (a batch per round instead of the resident one), ``host-resize`` (every resize
+    over the host), ``lockstep`` (all blends stop at the nearest hook of any of them)."""
+    args = (max_iter, e_rel, min_iter)
     if alg_kwargs.get("callback") is not None or alg_kwargs.get("scheme", "amsgrad") != "amsgrad":
         # a callback sees every blend's parameters after every iteration, another scheme of
         # proxmin.adaprox steps on the host from the device's gradients: both are Blend.fit's
         # host-stepped modes, one blend at a time -- which is what this call stands for
         # (scarlet/testing/api.py:216-224)
-        out, errors = [], []
-        for i, b in enumerate(blends):
-            b.device = device
-            try:
-                out.append(b.fit(max_iter, e_rel, min_iter, **alg_kwargs))
-            except ArithmeticError as e:
-                errors.append((i, e))
-                out.append((len(b.loss), float("nan")))
-        return out, errors
+        return _assemble(blends, [_fit_alone(b, device, *args, **alg_kwargs) for b in blends])
     alg_kwargs.pop("scheme", None)
     alg_kwargs.pop("callback", None)
     prox_max_iter, opt = _adaprox_options(alg_kwargs)
-
-    class _Run:
-        def __init__(self, blend, obs):
-            # `base + local` is the reference's `it`: 0 at the start of fit(), the length
-            # of the whole loss history after a restart (blend.py:101, 198)
-            self.blend, self.base, self.local, self.result = blend, 0, 0, None
-            blend._scheme = ("amsgrad", 0.25)  # the batched device loop
-            self.obs = obs
-
-        @property
-        def total(self):
-            return self.base + self.local
-
-    # blends with host-updated parameters (hoststep.py) step one iteration per device call
-    solo, observed, described = set(), {}, {}
-    for i, b in enumerate(blends):
-        b._psf, b._scheme = None, ("amsgrad", 0.25)  # nothing left over from an earlier fit()
-        if any(not p.fixed for obs in b.observations for p in obs.parameters):
-            solo.add(i)  # free renderer parameters (psf_shift): Blend.fit's own loop
-            continue
-        if any(type(obs.renderer) not in (NullRenderer, ConvolutionRenderer, ResolutionRenderer)
-               for obs in b.observations):
-            solo.add(i)  # a user-defined renderer: Blend.fit's host-rendered mode
-            continue
-        observed[i] = b._observation()  # (built once: the data, weight and kernel cubes)
-        if b._lowres or b._extra_layers:
-            # a ResolutionRenderer observation / several observations of one channel are
-            # terms of ONE blend's loss on the device (smi_batch_attach_lowres,
-            # smi_batch_add_observation): such a blend is fitted by itself, like
-            # [b.fit() for b in blends] would (scarlet/testing/api.py:216-224)
-            solo.add(i)
-    for i, b in enumerate(blends):
-        if i in solo or i not in observed:
-            continue
-        described[i] = b._specs(_flatten(b.sources))  # (once: 15 us per component)
-        if b._host:
-            solo.add(i)
-    if solo and _from_fit:
+    mode = os.environ.get("SCARLET_AMD_FIT_BLENDS")
+    # -- every blend: by itself (and why), or in a batch
+    sorted_out = [_classify(b) for b in blends]
+    if _from_fit and any(why is not None for why, _ in sorted_out):
         return None, None
-    solo_results = {}
-    for i in sorted(solo):
-        blends[i].device = device
-        try:
-            solo_results[i] = blends[i].fit(max_iter, e_rel, min_iter, prox_max_iter=prox_max_iter, **opt)
-        except ArithmeticError as e:
-            solo_results[i] = e
-    runs = [_Run(b, observed[i]) for i, b in enumerate(blends) if i not in solo]
-    for r, i in zip(runs, (i for i in range(len(blends)) if i not in solo)):
-        r.specs = described[i]
+    fitted = []
+    for i, (why, run) in enumerate(sorted_out):
+        if why is not None:
+            logger.debug("fit_blends: blend %d is fitted by itself: %s", i, why)
+            run = _fit_alone(blends[i], device, *args, prox_max_iter=prox_max_iter, **opt)
+        fitted.append(run)
+    # -- the groups of equal frame and kernel shapes
     step_kw = dict(e_rel=e_rel, min_iter=min_iter, prox_max_iter=prox_max_iter)
     by_shape = {}
-    for r in runs:
-        data, _, kernel = r.obs
-        by_shape.setdefault((data.shape, None if kernel is None else kernel.shape), []).append(r)
+    for r in fitted:
+        if isinstance(r, _Run):
+            data, _, kernel = r.obs
+            by_shape.setdefault((data.shape, None if kernel is None else kernel.shape), []).append(r)
     for group in by_shape.values():
-        plain = all(_device_hook_covers(src) for r in group for src in r.blend.sources)
-        if os.environ.get("SCARLET_AMD_FIT_BLENDS") == "rebuild":  # development aid: A/B runs
-            plain = False
-        if plain:
-            _fit_group_resident(group, device, max_iter, opt, step_kw)
+        if mode != "rebuild" and all(_device_hook_covers(src) for r in group
+                                     for src in r.blend.sources):
+            _fit_group_resident(group, device, max_iter, opt, step_kw, mode)
         else:
             _fit_group_rebuilt(group, device, max_iter, opt, step_kw)
-    out, errors = [], []
-    batched = iter(runs)
-    for i, blend in enumerate(blends):
-        if i in solo:
-            res = solo_results[i]
-            if isinstance(res, Exception):
-                errors.append((i, res))
-                res = (len(blend.loss), float("nan"))
-            out.append(res)
-            continue
-        r = next(batched)
-        if isinstance(r.result, Exception):
-            errors.append((i, r.result))
-            out.append((len(blend.loss), float("nan")))
-            continue
-        _mark_std(blend.parameters)
-        out.append((len(blend.loss), -blend.loss[-1]))
-    return out, errors
+    return _assemble(blends, fitted)

@@ -21,11 +21,16 @@ from .parameter import prepare_param, Parameter, relative_step
 
 def get_minimal_boxsize(size, min_size=21, increment=10):
     """Smallest odd box size ``min_size + k * increment`` that holds ``size``
-    pixels (reference initialization.py:173-177)."""
-    boxsize = min_size
-    while boxsize < size:
-        boxsize += increment
-    return boxsize
+    pixels (reference initialization.py:173-177); ``size`` is a number or an array."""
+    steps = np.ceil(np.maximum(np.asarray(size) - min_size, 0) / increment).astype(np.int64)
+    boxsize = min_size + increment * steps
+    return boxsize if boxsize.ndim else int(boxsize)
+
+
+def _margin_of_empty(short_side):
+    """``_empty_margin`` of an image (or an array of images) that holds no pixel above the
+    threshold, from the shorter side of its box: all of it is margin."""
+    return (short_side + 1) // 2
 
 
 def _empty_margin(image, thresh):
@@ -35,7 +40,7 @@ def _empty_margin(image, thresh):
     mask = np.asarray(image) > thresh
     rows = mask.any(axis=1)
     if not rows.any():
-        return (min(image.shape) + 1) // 2
+        return _margin_of_empty(min(image.shape))
     cols = mask.any(axis=0)
     # first and last occupied row / column, counted from the nearer edge
     return int(min(rows.argmax(), cols.argmax(), rows[::-1].argmax(), cols[::-1].argmax()))

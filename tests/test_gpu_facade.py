@@ -872,7 +872,7 @@ def test_fit_blends_mixes_device_and_host_resizes(monkeypatch):
     import sys
 
     import scarlet_amd as scarlet
-    from scarlet_amd.blend import _device_resize_covers
+    from scarlet_amd.fitting import _device_resize_covers
 
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import bench
@@ -928,7 +928,7 @@ def test_centre_fitting_with_resizing_on_the_resident_path(monkeypatch):
     import sys
 
     import scarlet_amd as scarlet
-    from scarlet_amd.blend import _device_resize_covers
+    from scarlet_amd.fitting import _device_resize_covers
 
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import bench

@@ -576,10 +576,11 @@ def test_bench_prices_the_bytes_of_survey_8d():
 
 def test_resized_component_description_is_what_specs_would_make(hsc):
     """fit_blends derives the device description of a resized component from the old one
-    (blend._resized_spec: new image, new origin, halved step); it must be field for field what
+    (fitting._resized_spec: new image, new origin, halved step); it must be field for field what
     Blend._specs makes from scratch after ImageMorphology.update shrank or grew the box."""
     import scarlet_amd as scarlet
-    from scarlet_amd.blend import _flatten, _resized_spec
+    from scarlet_amd.blend import _flatten
+    from scarlet_amd.fitting import _resized_spec
     from scarlet_amd.model import UpdateException
     from test_gpu_facade import build_blend
 
@@ -616,6 +617,7 @@ def test_resized_component_description_is_what_specs_would_make(hsc):
     assert changed >= 6
 
 
+def test_empty_margin_is_the_reference_loop():
     """morphology._empty_margin against the loop of the reference's shrink_box
     (morphology.py:50-67): peel while all four outermost rows / columns hold nothing above
     the threshold."""
@@ -856,3 +858,223 @@ def test_bench_dumps_the_outputs_of_its_last_step(tmp_path):
     assert len(pick) == 256 and np.all(np.diff(pick) > 0)
     morph = np.load(tmp_path / "a" / "morph_sample.npy").reshape(len(pick), 10, 41 * 41)
     assert_array_equal(morph[:, :, 0], 10 * pick[:, None] + np.arange(10))
+
+
+def test_next_round_takes_arrays_and_plans_the_launches_of_the_resident_batch():
+    """blend._next_round is the one place of the rule "the resize hook runs once 11, 21, 31, ...
+    iterations of an adaprox call are done": ints and arrays give the same, and both what the
+    rule says in words.  fitting._plan_round makes a launch of the resident batch from it, here
+    for two blends at their own counters, one out of budget and one that failed."""
+    from scarlet_amd.blend import _next_round
+    from scarlet_amd.fitting import _plan_round
+
+    local = np.arange(500)
+    for budget in (1, 3, 10, 11, 200):
+        got = _next_round(local, budget)
+        assert isinstance(got, np.ndarray) and got.shape == (500,)
+        for k in local.tolist():
+            one = _next_round(k, budget)
+            assert type(one) is int and one == got[k]
+            assert one == min(next(h for h in range(11, 600, 10) if h > k) - k, budget)
+    assert_array_equal(_next_round(np.array([0, 14, 21]), np.array([5, 30, 4])), [5, 7, 4])
+
+    state = np.array([0, 0, 0, 3], dtype=np.int32)
+    local = np.array([0, 14, 30, 7])
+    left = 30 - local
+    plan = _plan_round(state, left, local, 40)
+    assert_array_equal(plan.live, [True, True, False, False])
+    assert_array_equal(plan.quota[:2], [11, 7])  # to the hooks after 11 and 21 iterations
+    assert plan.n == 11 and type(plan.n) is int
+    assert_array_equal(plan.pause_at, [50, 46, -1, -1])  # g + quota - 1, nobody else pauses
+    assert_array_equal(plan.states, [0, 0, 2, 3])  # out of budget: finished for the device
+    assert plan.states.dtype == np.int32
+    assert_array_equal(plan.base, [40, 26, 0, 0])  # g - local: where each call began
+    # the end of the budget comes before the hook
+    plan = _plan_round(state, np.array([5, 16, 0, 23]), local, 40)
+    assert_array_equal(plan.quota[:2], [5, 7])
+    assert plan.n == 7 and list(plan.pause_at) == [44, 46, -1, -1]
+    # development switch: everybody to the nearest hook of any live blend
+    plan = _plan_round(state, left, local, 40, lockstep=True)
+    assert_array_equal(plan.quota, [7, 7, 7, 7])
+    assert plan.n == 7 and list(plan.pause_at) == [46, 46, -1, -1]
+    assert _plan_round(np.array([2, 3, 0], dtype=np.int32), np.array([9, 9, 0]),
+                       np.array([3, 3, 12]), 12) is None
+
+
+def test_standard_box_size_of_numbers_and_arrays():
+    """morphology.get_minimal_boxsize in closed form against the reference's loop
+    (initialization.py:173-177), for numbers and for an array of them."""
+    from scarlet_amd.morphology import get_minimal_boxsize
+
+    def loop(size, min_size=21, increment=10):
+        boxsize = min_size
+        while boxsize < size:
+            boxsize += increment
+        return boxsize
+
+    sizes = np.arange(-5, 400)
+    assert_array_equal(get_minimal_boxsize(sizes), [loop(s) for s in sizes])
+    for s in (-3, 0, 20, 21, 22, 31, 32, 1000, 1001, np.int64(45), 30.5, 31.0):
+        got = get_minimal_boxsize(s)
+        assert type(got) is int and got == loop(s)
+    assert get_minimal_boxsize(40, min_size=15, increment=4) == loop(40, 15, 4) == 43
+
+
+def _resize_cases(n, seed):
+    """Seeded ImageMorphology objects on odd square boxes of 21 to 61 pixels, float32 and
+    float64 images: empty, a centred or a one-sided block, or the full box; random moments,
+    some edges or whole images at v == 0; in some the largest edge pull is put within 1e-6 of
+    the threshold.  With them the inputs of the resize plan as the device defines them
+    (include/scarlet_amd.h): margin = ``_empty_margin``, INT32_MAX for an image without a pixel
+    > 0; pull = the largest finite entry of ``_edge_pull``, -inf if there is none."""
+    import scarlet_amd as scarlet
+    from scarlet_amd.morphology import _edge_pull, _empty_margin
+    from scarlet_amd.parameter import Parameter
+
+    rng = np.random.default_rng(seed)
+    frame = scarlet.Frame((3, 200, 200), channels=list("abc"))
+    morphs, margin, pull = [], [], []
+    for k in range(n):
+        s = int(rng.choice([21, 31, 41, 51, 61]))
+        img = np.zeros((s, s), dtype=rng.choice([np.float32, np.float64]))
+        kind = rng.integers(0, 5)
+        if kind > 0:  # (kind 0: empty image)
+            r = int(rng.integers(1, s // 2 + 1))  # occupied half-width
+            c = s // 2
+            img[c - r:c + r + 1, c - r:c + r + 1] = rng.uniform(0.01, 1, (2 * r + 1, 2 * r + 1))
+            if kind == 1:  # one-sided occupancy
+                img[:c, :] = 0
+        m = rng.normal(0, 1, (s, s)) * rng.choice([0.0, 1e-3, 1.0, 30.0])
+        v = rng.uniform(0, 1, (s, s)) ** 2
+        if kind >= 3:  # flux up to the edges and a gradient that pulls outwards on one of them
+            img[...] = rng.uniform(0.01, 1, (s, s))
+            m = rng.normal(0, 1, (s, s))
+            m[0, :] = -rng.uniform(0.0, 40.0)
+        if rng.random() < 0.3:
+            v[:, 0] = 0  # an edge without a seen pixel
+        if rng.random() < 0.1:
+            v[...] = 0
+        step = float(rng.choice([1e-2, 5e-3, 2.5e-3]))
+        if kind == 4 and not (v == 0).all():  # the largest edge mean within 1e-6 of the threshold
+            top = np.nanmax(_edge_pull(img, m, v, step))
+            if top > 0:
+                m *= 0.1 * (1 + rng.uniform(-8e-7, 8e-7)) / top
+        image = Parameter(img, name="image", step=step)
+        image.m, image.v, image.vhat = m, v, v.copy()
+        origin = (int(rng.integers(0, 100)), int(rng.integers(0, 100)))
+        morphs.append(scarlet.ImageMorphology(frame, image, bbox=scarlet.Box((s, s), origin=origin),
+                                              resizing=True))
+        edges = _edge_pull(img, m, v, step)
+        margin.append(_empty_margin(img, 0) if (img > 0).any() else np.iinfo(np.int32).max)
+        pull.append(edges[np.isfinite(edges)].max() if np.isfinite(edges).any() else -np.inf)
+    return morphs, np.array(margin), np.array(pull)
+
+
+def test_resize_plan_of_the_resident_batch_is_what_update_does():
+    """fitting._resize_candidates and _device_rows -- the resident loop's decisions on the device's
+    two reductions -- against ``ImageMorphology.update()`` on the host objects: for every one of
+    400 components the same verdict (resized or not), new shape, new origin and new step.  The
+    components close to the threshold are decided by ``_edge_pull`` like in the loop.  The sample
+    holds every kind of case in numbers."""
+    from scarlet_amd.fitting import _device_rows, _resize_candidates
+    from scarlet_amd.model import UpdateException
+    from scarlet_amd.morphology import _edge_pull
+
+    n = 400
+    morphs, margin, pull = _resize_cases(n, 11)
+    images = [mo._parameters[0] for mo in morphs]
+    shapes = np.array([im.shape for im in images])
+    origin = np.array([mo.bbox.origin for mo in morphs], dtype=np.int64)
+    step = np.array([im.step for im in images])
+    wide = np.array([im.dtype == np.float64 for im in images])
+    shrink, grow, standard, close = _resize_candidates(margin, pull, shapes, step,
+                                                       np.ones(n, dtype=bool))
+    assert not (shrink & grow).any()
+    dev = shrink | grow
+    for k in close:
+        im = images[k]
+        grow[k] = dev[k] = bool(np.any(_edge_pull(np.asarray(im), im.m, im.v, im.step) > 0.1))
+    # (every component a source of its own: all candidates get a row)
+    resized, keep = _device_rows(dev, shrink, standard, shapes.max(axis=1), np.arange(n), wide,
+                                 origin, step)
+    rows = resized["rows"]
+    assert_array_equal(rows, np.flatnonzero(dev))
+    assert_array_equal(keep, np.where(wide[rows], 3, 2))
+    row_of = {int(k): j for j, k in enumerate(rows)}
+    two_sizes = 0
+    for k, mo in enumerate(morphs):
+        try:
+            mo.update()
+            changed = False
+        except UpdateException:
+            changed = True
+        assert changed == (k in row_of), k
+        want = (shapes[k, 0], origin[k, 0], origin[k, 1], step[k])
+        if changed:
+            j = row_of[k]
+            want = (resized["size"][j], resized["origin_y"][j], resized["origin_x"][j],
+                    resized["morph_step"][j])
+            two_sizes += shrink[k] and shapes[k, 0] - want[0] >= 20
+        assert tuple(mo.bbox.shape) == (want[0], want[0]), k
+        assert tuple(mo.bbox.origin) == (want[1], want[2]), k
+        assert mo._parameters[0].step == want[3] and mo._parameters[0].shape == mo.bbox.shape, k
+    assert shrink.sum() >= 50 and two_sizes >= 50 and grow.sum() >= 50
+    assert (~dev).sum() >= 50 and (margin == np.iinfo(np.int32).max).sum() >= 30
+    assert len(close) >= 30
+    # nothing is decided for a component that is not at a hook
+    none = _resize_candidates(margin, pull, shapes, step, np.zeros(n, dtype=bool))
+    assert not none[0].any() and not none[1].any() and none[3].size == 0
+
+
+def test_only_the_first_resizing_child_of_a_source_gets_a_row(hsc):
+    """``CombinedComponent.update()`` stops at its first child that raises ``UpdateException``
+    (component.py:172-185): of a source whose two children both would shrink, only the first is
+    resized at this hook.  fitting._component_table numbers the sources and _device_rows picks
+    exactly one row per source, the first candidate."""
+    from types import SimpleNamespace
+
+    import scarlet_amd as scarlet
+    from scarlet_amd.blend import _flatten
+    from scarlet_amd.fitting import _component_table, _device_rows, _resize_candidates
+    from scarlet_amd.model import UpdateException
+    from scarlet_amd.morphology import _empty_margin
+    from test_gpu_facade import build_blend
+
+    blend, _ = build_blend(hsc, resizing=True)
+    comps = _flatten(blend.sources)
+    t = _component_table([SimpleNamespace(blend=blend)], [comps])
+    n = len(comps)
+    assert_array_equal(t.first, [0, n])
+    assert_array_equal(t.blend_of, np.zeros(n))
+    assert t.resizable.all() and not t.moved.any() and t.on_device.all()
+    j = next(j for j, src in enumerate(blend.sources)
+             if isinstance(src, scarlet.CombinedComponent) and len(src.children) == 2)
+    source = blend.sources[j]
+    pair = np.flatnonzero(t.source_of == j)
+    assert [comps[k] for k in pair] == list(source.children)
+    for k, c in enumerate(comps):
+        assert tuple(t.origin[k]) == tuple(c.children[1].bbox.origin[-2:])
+        assert t.step[k] == c.children[1]._parameters[0].step == 1e-2
+        assert t.wide[k] == (c.children[1]._parameters[0].dtype == np.float64)
+    boxes = [tuple(c.children[1].bbox.shape) for c in comps]
+    assert all(h == w and h > 21 for h, w in (boxes[k] for k in pair))
+    for k in pair:  # both children: nothing but the centre pixel above zero
+        image = comps[k].children[1]._parameters[0]
+        image[...] = 0
+        image[image.shape[0] // 2, image.shape[1] // 2] = 1
+    images = [np.asarray(c.children[1]._parameters[0]) for c in comps]
+    margin = np.array([_empty_margin(im, 0) for im in images])
+    shapes = np.array(boxes)
+    at_hook = t.source_of == j
+    shrink, grow, standard, close = _resize_candidates(margin, np.full(n, -np.inf), shapes,
+                                                       t.step, at_hook)
+    assert list(np.flatnonzero(shrink)) == list(pair) and not grow.any() and not close.size
+    resized, keep = _device_rows(shrink | grow, shrink, standard, shapes.max(axis=1),
+                                 t.source_of, t.wide, t.origin, t.step)
+    assert list(resized["rows"]) == [pair[0]] and list(resized["size"]) == [21]
+    assert list(keep) == [3 if t.wide[pair[0]] else 2] and list(resized["morph_step"]) == [5e-3]
+    with pytest.raises(UpdateException):
+        source.update()
+    first, second = (comps[k].children[1] for k in pair)
+    assert tuple(first.bbox.shape) == (21, 21) and tuple(second.bbox.shape) == boxes[pair[1]]
+    assert tuple(first.bbox.origin) == (resized["origin_y"][0], resized["origin_x"][0])
