@@ -164,7 +164,13 @@ enum {
      * are still applied, as proxmin does with the expanded zero gradient.  FIXED_MORPH
      * fixes the image of an extended source or the centre of a point source. */
     SMI_COMPONENT_FIXED_SED = 1 << 18,
-    SMI_COMPONENT_FIXED_MORPH = 1 << 19
+    SMI_COMPONENT_FIXED_MORPH = 1 << 19,
+    /* the morphology is the reconstruction of starlet coefficients, which are the parameter
+     * (StarletSource, source.py:525-612; StarletMorphology, morphology.py:516-604): see the
+     * star_* fields of smi_components.  SMI_COMPONENT_FIXED_MORPH fixes the coefficients.
+     * No other prox flag: the constraint is PositivityConstraint(pos_floor) followed by the
+     * per-plane hard threshold star_thresh. */
+    SMI_COMPONENT_STARLET = 1 << 20
 };
 #define SMI_PROX_EXTENDED_SOURCE \
     (SMI_PROX_MONOTONIC | SMI_PROX_POSITIVE | SMI_PROX_CENTER_ON | SMI_PROX_NORM_MAX)
@@ -242,6 +248,19 @@ typedef struct smi_components {
                                 /* (psf.py:145-202): (1 + r^2 / alpha^2)^-beta sampled at    */
                                 /* the pixel centres, alpha in psf_sigma; 0 or NULL = the    */
                                 /* pixel-integrated Gaussian of width psf_sigma              */
+    /* starlet components (SMI_COMPONENT_STARLET in prox_flags); all NULL if none.  For such a
+     * component `morph` is ignored (the library reconstructs the image from the coefficients),
+     * `morph_step` is the constant step of the coefficients (1e-2, morphology.py:564) and
+     * `pos_floor` the floor of their PositivityConstraint. */
+    const int32_t *star_planes; /* [n_components] coefficient planes, scales + 1 (<= 31); 0   */
+                                /* for other components                                       */
+    const float *star_coeffs;   /* the [planes][box_h][box_w] stacks of the starlet           */
+                                /* components, back to back in component order                */
+    const float *star_thresh;   /* their per-plane absolute thresholds of the L0Constraint,   */
+                                /* planes entries each, back to back (last plane: 0)          */
+    const float *sed_floor;     /* [n_components] PositivityConstraint(zero) of the spectrum: */
+                                /* 1e-20 (spectrum.py:54-56) or 0 (RandomSource,              */
+                                /* source.py:81-86); NULL = 1e-20                             */
 } smi_components;
 
 int smi_batch_create(const smi_batch_desc *desc, int device, smi_batch **out);
@@ -335,6 +354,16 @@ int smi_batch_set_center_moments(smi_batch *b, const double *m, const double *v,
 int smi_batch_set_centers(smi_batch *b, const double *center);
 int smi_batch_get_model_morphology(smi_batch *b, float *morph);
 int smi_batch_set_parameters(smi_batch *b, const float *sed, const float *morph);
+/* Starlet components: the coefficients, their AMSGrad moments and the gradient of -logL
+ * w.r.t. them (valid after smi_batch_gradient), each packed like star_coeffs; any pointer may be
+ * NULL.  smi_batch_get_parameters returns the reconstructed image of such a component.
+ * smi_batch_set_starlet_moments: warm start (NULL = zeros).  A batch with starlet components
+ * keeps one range of blends and the model cube; smi_batch_set_frame_extents,
+ * smi_batch_update_components, smi_batch_set_iteration_base, SMI_SCHEME_FISTA and the
+ * state-record / save-state calls refuse it. */
+int smi_batch_get_starlet(smi_batch *b, float *coeffs, float *m, float *v, float *vhat,
+                          float *gradient);
+int smi_batch_set_starlet_moments(smi_batch *b, const float *m, const float *v, const float *vhat);
 
 /* Update rule of the parameters.  SMI_SCHEME_AMSGRAD (default): proxmin.adaprox as used
  * by Blend.fit and lite's AdaproxParameter.  SMI_SCHEME_FISTA: lite's FistaParameter

@@ -41,6 +41,7 @@ from .morphology import (  # noqa: F401
     ImageMorphology,
     ExtendedSourceMorphology,
     PointSourceMorphology,
+    StarletMorphology,
 )
 from .component import (  # noqa: F401
     Component,
@@ -56,6 +57,8 @@ from .source import (  # noqa: F401
     MultiExtendedSource,
     CompactExtendedSource,
     PointSource,
+    RandomSource,
+    StarletSource,
 )
 from .model import Model, UpdateException  # noqa: F401
 from .wavelet import Starlet  # noqa: F401

@@ -33,6 +33,7 @@ COMPONENT_POINT_SOURCE = 1 << 16  # PointSource: morphology = model PSF at a fre
 COMPONENT_SHIFTING = 1 << 17  # image morphology moved by a free Fourier shift
 COMPONENT_FIXED_SED = 1 << 18
 COMPONENT_FIXED_MORPH = 1 << 19
+COMPONENT_STARLET = 1 << 20  # morphology = reconstruction of starlet coefficients (the parameter)
 PROX_EXTENDED_SOURCE = PROX_MONOTONIC | PROX_POSITIVE | PROX_CENTER_ON | PROX_NORM_MAX
 
 ERR_ARITHMETIC = -4
@@ -64,6 +65,8 @@ class Components(ctypes.Structure):
         ("center_floor", c_f32p), ("bg_level", c_f32p), ("fista_step", c_f32p),
         ("sym_strength", c_f32p), ("pos_floor", c_f32p), ("chain_repeat", c_i32p),
         ("shift_rel_step", c_f32p), ("psf_beta", c_f32p),
+        ("star_planes", c_i32p), ("star_coeffs", c_f32p), ("star_thresh", c_f32p),
+        ("sed_floor", c_f32p),
     ]
 
 
@@ -166,6 +169,8 @@ SYMBOLS = {
     "smi_batch_set_center_moments": (ctypes.c_int, [ctypes.c_void_p] + [c_f64p] * 3),
     "smi_batch_set_centers": (ctypes.c_int, [ctypes.c_void_p, c_f64p]),
     "smi_batch_get_model_morphology": (ctypes.c_int, [ctypes.c_void_p, c_f32p]),
+    "smi_batch_get_starlet": (ctypes.c_int, [ctypes.c_void_p] + [c_f32p] * 5),
+    "smi_batch_set_starlet_moments": (ctypes.c_int, [ctypes.c_void_p] + [c_f32p] * 3),
     "smi_batch_set_scheme": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "smi_batch_get_fista_state": (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, c_f64p]),
     "smi_batch_set_fista_state": (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, c_f64p]),

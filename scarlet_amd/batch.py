@@ -20,8 +20,11 @@ class ComponentSpec:
                  morph_step=1e-2, morph_rel_step=0.0, prox_flags=_lib.PROX_EXTENDED_SOURCE,
                  neighbor_weight="angle", min_gradient=0.0, l_thresh=0.0, shift=None,
                  shift_step=1e-1, center_floor=1e-6, bg_level=None, fista_step=0.0,
-                 sym_strength=1.0, chain_repeat=1, pos_floor=0.0, shift_rel_step=0.0):
+                 sym_strength=1.0, chain_repeat=1, pos_floor=0.0, shift_rel_step=0.0,
+                 starlet=None, sed_floor=None):
         self.sed = np.asarray(sed, dtype=np.float32)
+        # PositivityConstraint(zero) of the spectrum; None: the 1e-20 of spectrum.py:54-56
+        self.sed_floor = None if sed_floor is None else float(sed_floor)
         self.morph = np.ascontiguousarray(morph, dtype=np.float32)
         self.origin = (int(origin[0]), int(origin[1]))
         step = np.asarray(sed_min_step, dtype=np.float32)
@@ -52,6 +55,19 @@ class ComponentSpec:
         if shift is not None:
             self.center = np.array(shift, dtype=np.float64).reshape(2)
             self.prox_flags |= _lib.COMPONENT_SHIFTING
+        # StarletMorphology (morphology.py:516-604): ``starlet = (coefficients (planes, h, w),
+        # absolute threshold per plane)``; the coefficients are the parameter, ``morph`` only
+        # gives the box shape, ``morph_step`` / ``pos_floor`` are the coefficients' step and
+        # positivity floor.  Of ``prox_flags`` only the two FIXED bits are kept.
+        self.star_coeffs = self.star_thresh = None
+        if starlet is not None:
+            coeffs, thresh = starlet
+            self.star_coeffs = np.ascontiguousarray(coeffs, dtype=np.float32)
+            assert self.star_coeffs.ndim == 3 and self.star_coeffs.shape[1:] == self.morph.shape
+            self.star_thresh = np.ascontiguousarray(thresh, dtype=np.float32)
+            assert self.star_thresh.shape == self.star_coeffs.shape[:1]
+            fixed = _lib.COMPONENT_FIXED_SED | _lib.COMPONENT_FIXED_MORPH
+            self.prox_flags = _lib.COMPONENT_STARLET | (self.prox_flags & fixed)
 
 
 class PointSourceSpec(ComponentSpec):
@@ -247,6 +263,8 @@ class BlendBatch:
             pos_floor=_lib.f32([c.pos_floor for c in part]),
             shift_rel_step=_lib.f32([c.shift_rel_step for c in part]),
             psf_beta=_lib.f32([getattr(c, "psf_beta", 0.0) for c in part]),
+            star_planes=_lib.i32([0 if c.star_coeffs is None else len(c.star_coeffs)
+                                  for c in part]),
         )
         if rows is None:
             arrays = fields
@@ -268,8 +286,24 @@ class BlendBatch:
                                  else np.zeros((0, C)))
         arrays["morph"] = _lib.f32(np.concatenate([c.morph.reshape(-1) for c in flat])
                                    if flat and values else np.zeros(0))
+        # starlet components: coefficient stacks and per-plane thresholds, back to back
+        star = [k for k, c in enumerate(flat) if c.star_coeffs is not None]
+        self._star = star
+        self._star_shapes = [flat[k].star_coeffs.shape for k in star]
+        arrays["star_coeffs"] = _lib.f32(np.concatenate(
+            [flat[k].star_coeffs.reshape(-1) for k in star]) if star and values else np.zeros(0))
+        arrays["star_thresh"] = _lib.f32(np.concatenate(
+            [flat[k].star_thresh for k in star]) if star and values else np.zeros(0))
+        # spectrum floors: sent only when some component asks for another one than 1e-20
+        floors = None
+        if any(c.sed_floor is not None for c in flat):
+            floors = _lib.f32([1e-20 if c.sed_floor is None else c.sed_floor for c in flat])
+        arrays["sed_floor"] = floors
         comps = _lib.Components()
         for name, ctype in _lib.Components._fields_:
+            if arrays[name] is None:
+                setattr(comps, name, None)
+                continue
             setattr(comps, name, arrays[name].ctypes.data_as(ctype))
         comps._keepalive = arrays  # the ctypes struct only holds pointers
         return comps
@@ -727,6 +761,42 @@ class BlendBatch:
             )
         )
         return sed, self._split_morphs(morph)
+
+    # -- starlet components ---------------------------------------------------------
+    def _split_starlets(self, flat):
+        out, pos = [], 0
+        for shape in self._star_shapes:
+            n = int(np.prod(shape))
+            out.append(flat[pos:pos + n].reshape(shape))
+            pos += n
+        return out
+
+    def starlet_state(self, dtype=np.float32):
+        """State of the starlet components: ``components`` (their indices) and, one
+        ``(planes, h, w)`` array per such component, ``coeffs``, ``m``, ``v``, ``vhat`` and --
+        valid after ``gradient()`` -- ``gradient`` of ``-logL`` w.r.t. the coefficients."""
+        n = int(sum(np.prod(s) for s in self._star_shapes))
+        names = ("coeffs", "m", "v", "vhat", "gradient")
+        bufs = [np.zeros(n, dtype=np.float32) for _ in names]
+        _lib.check(self._lib.smi_batch_get_starlet(
+            self._h, *[_lib.ptr(b, ctypes.c_float) for b in bufs]))
+        out = {name: self._split_starlets(b.astype(dtype, copy=False))
+               for name, b in zip(names, bufs)}
+        out["components"] = list(self._star)
+        return out
+
+    def set_starlet_moments(self, m=None, v=None, vhat=None):
+        """Warm start of the coefficients' AMSGrad moments: per argument one
+        ``(planes, h, w)`` array per starlet component, or ``None`` for zeros."""
+        def pack(x):
+            if x is None:
+                return None
+            assert [np.shape(a) for a in x] == [tuple(s) for s in self._star_shapes]
+            return _lib.f32(np.concatenate([np.asarray(a).reshape(-1) for a in x]))
+
+        arrs = [pack(m), pack(v), pack(vhat)]
+        _lib.check(self._lib.smi_batch_set_starlet_moments(
+            self._h, *[_lib.ptr(a, ctypes.c_float) for a in arrs]))
 
     def has_shift(self, k):
         """True if component ``k`` carries a Fourier shift on the device."""

@@ -21,7 +21,7 @@ from .component import CombinedComponent, FactorizedComponent
 from .constraint import PositivityConstraint, device_flags
 from .hoststep import HostBandSource, HostParameter, HostVector
 from .model import UpdateException
-from .morphology import PointSourceMorphology
+from .morphology import PointSourceMorphology, StarletMorphology, plane_thresholds
 from .psf import GaussianPSF, ImagePSF, MoffatPSF
 from .parameter import relative_step, STD_FROM_V
 from .renderer import ConvolutionRenderer, NullRenderer, ResolutionRenderer
@@ -162,6 +162,44 @@ def _step_rule(step, what):
 
 
 # -- the rules of the adaprox round loop (blend.py:276-302), for every fit that runs one
+def _starlet_rules(morphology, scheme):
+    """``(step, positivity floor, threshold per plane)`` of the coefficients of a
+    ``StarletMorphology`` as the device runs them; ``NotImplementedError`` for what it does
+    not: monotonic planes, another scheme than amsgrad, a prior, a step callable, another
+    constraint than ``ConstraintChain(PositivityConstraint, L0Constraint(absolute))``."""
+    coeffs = morphology._parameters[0]
+    if morphology.monotonic:
+        raise NotImplementedError(
+            "StarletMorphology(monotonic=True) cannot be fitted yet: the per-plane "
+            "MonotonicMaskConstraint does not run in the device loop")
+    if scheme != "amsgrad":
+        raise NotImplementedError("starlet sources with another scheme than amsgrad")
+    if coeffs.prior is not None:
+        raise NotImplementedError("a prior on starlet coefficients")
+    if coeffs.fixed and coeffs.step is None:
+        rule = (0.0, 0.0, 0)  # never used (blend.py:107-115)
+    else:
+        rule = _step_rule(coeffs.step, "morphology")
+    if rule is None or rule[1]:
+        raise NotImplementedError("starlet coefficients need a constant step (got a callable)")
+    limits = plane_thresholds(coeffs.constraint)
+    if limits is None or len(limits[1]) != coeffs.shape[0]:
+        raise NotImplementedError(
+            "starlet coefficients need the constraint ConstraintChain(PositivityConstraint, "
+            "L0Constraint(per-plane thresholds, type='absolute'))")
+    return float(rule[0]), limits[0], limits[1]
+
+
+def _refuse_unfittable_starlets(sources, scheme):
+    """Raise for a starlet source the device loop cannot run, before anything else of a fit."""
+    for src in sources:
+        if isinstance(src, FactorizedComponent):
+            if isinstance(src.children[1], StarletMorphology):
+                _starlet_rules(src.children[1], scheme)
+        elif isinstance(src, CombinedComponent):
+            _refuse_unfittable_starlets(src.children, scheme)
+
+
 def _next_round(local, budget):
     """Iterations until the resize hook after local iterations 10, 20, ... has to run (once
     11, 21, ... iterations of this adaprox call are done), capped by ``budget``.  Ints, or
@@ -363,6 +401,9 @@ class Blend(CombinedComponent):
                     prox_flags=_lib.COMPONENT_FIXED_MORPH | _lib.COMPONENT_FIXED_SED,
                     shift=np.asarray(shift, dtype=np.float64), shift_step=0.0))
                 continue
+            if isinstance(morphology, StarletMorphology):
+                specs.append(self._starlet_spec(k, sed, image, morphology))
+                continue
             if isinstance(morphology, PointSourceMorphology):
                 if self._scheme_args()[0] != "amsgrad":
                     raise NotImplementedError("point sources with another scheme than amsgrad")
@@ -461,6 +502,33 @@ class Blend(CombinedComponent):
 
     def _scheme_args(self):
         return getattr(self, "_scheme", ("amsgrad", 0.25))
+
+    def _starlet_spec(self, k, sed, coeffs, morphology):
+        """StarletSource -> device description: the coefficients are stepped by the starlet
+        kernels (constant step, positivity floor, one hard threshold per plane), the spectrum
+        by the ordinary update kernel -- with the floor of its PositivityConstraint, 0 for the
+        spectrum of a ``RandomSource`` -- or, if its rules are the user's, on the host."""
+        step, floor, thresh = _starlet_rules(morphology, self._scheme_args()[0])
+        sed_rule = _rule(sed, "spectrum")
+        positive = type(sed.constraint) is PositivityConstraint
+        sed_on_device = not callable(sed_rule) and sed.prior is None and (
+            positive or (sed.fixed and sed.constraint is None and np.all(np.asarray(sed) > 1e-20)))
+        if not sed_on_device:
+            self._host.append((k, HostParameter(sed, "sed", sed_rule, *self._scheme_args())))
+            sed_rule = (0.0, 0.0, 0.0)
+        s_const, s_rel, s_min = sed_rule
+        sed_floor = None
+        if positive and sed.constraint.zero != 1e-20:
+            sed_floor = float(sed.constraint.zero)
+        values = np.asarray(coeffs)
+        return ComponentSpec(
+            np.asarray(sed), np.zeros(values.shape[-2:], dtype=np.float32),
+            morphology.bbox.origin[-2:],
+            sed_min_step=np.maximum(np.asarray(s_min, dtype=np.float64), s_const),
+            sed_rel_step=s_rel, morph_step=step, pos_floor=floor,
+            prox_flags=(_lib.COMPONENT_FIXED_SED if sed.fixed or not sed_on_device else 0) | (
+                _lib.COMPONENT_FIXED_MORPH if coeffs.fixed else 0),
+            starlet=(values, thresh), sed_floor=sed_floor)
 
     def _host_gradients(self, batch, comps):
         """(g_sed, g_morph, g_vec) at the parameters of this iteration for the parameters the
@@ -611,9 +679,11 @@ class Blend(CombinedComponent):
                for name in ("m", "v", "vhat")):
             # missing moments (fresh parameters) are zeros (blend.py:154-160); a point
             # source has no image on the device side: zeros of its box shape
+            star = set(batch._star)  # (their moments belong to the coefficients: below)
+
             def image_state(name):
-                return [np.zeros(batch._shapes[k]) if point[k] else state(i, name, i.shape)
-                        for k, (_, i) in enumerate(params)]
+                return [np.zeros(batch._shapes[k]) if point[k] or k in star
+                        else state(i, name, i.shape) for k, (_, i) in enumerate(params)]
 
             batch.set_moments(
                 m_sed=np.stack([state(s_, "m", s_.shape) for s_, _ in params]),
@@ -621,6 +691,10 @@ class Blend(CombinedComponent):
                 vhat_sed=np.stack([state(s_, "vhat", s_.shape) for s_, _ in params]),
                 m_morph=image_state("m"), v_morph=image_state("v"), vhat_morph=image_state("vhat"),
             )
+        coeffs = [params[k][1] for k in batch._star]
+        if any(getattr(p, name) is not None for p in coeffs for name in ("m", "v", "vhat")):
+            batch.set_starlet_moments(*[[state(p, name, p.shape) for p in coeffs]
+                                        for name in ("m", "v", "vhat")])
         vec = [None] * len(comps)  # the free 2-vector of a component, if it has one
         for k, c in enumerate(comps):
             if point[k]:
@@ -655,7 +729,10 @@ class Blend(CombinedComponent):
         m_morph, v_morph, vhat_morph = mom["m_morph"], mom["v_morph"], mom["vhat_morph"]
         centers = None
         shifted = (np.asarray(batch._flags) & _lib.COMPONENT_SHIFTING).astype(bool).tolist()
-        if not any(shifted) and not any(isinstance(c._children[1], PointSourceMorphology) for c in comps):
+        star = dict(zip(batch._star, range(len(batch._star))))
+        starlets = batch.starlet_state(dtype=np.float64) if star else None
+        if not any(shifted) and not star and \
+                not any(isinstance(c._children[1], PointSourceMorphology) for c in comps):
             # images only (a thousand blends: ten thousand components): nothing but assignments
             for k, comp in enumerate(comps):
                 spectrum, morphology = comp._children
@@ -687,6 +764,10 @@ class Blend(CombinedComponent):
                 shift = comp.children[1]._parameters[1]
                 shift[...] = centers["center"][k]
                 shift.m, shift.v, shift.vhat = (centers[n][k].copy() for n in ("m", "v", "vhat"))
+            if k in star:  # the parameter is the coefficient stack, not the image
+                image[...] = starlets["coeffs"][star[k]]
+                image.m, image.v, image.vhat = (starlets[n][star[k]] for n in ("m", "v", "vhat"))
+                continue
             image[...] = morphs[k]
             image.m, image.v, image.vhat = m_morph[k], v_morph[k], vhat_morph[k]
 
@@ -713,6 +794,7 @@ class Blend(CombinedComponent):
         # the device loop is AMSGrad (the reference's default); any other scheme of
         # proxmin.adaprox steps every parameter on the host from the device's gradients
         self._scheme = (scheme, alg_kwargs.pop("p", 0.25))
+        _refuse_unfittable_starlets(self.sources, scheme)
         prox_max_iter, opt = _adaprox_options(alg_kwargs)
         if any(type(obs.renderer) not in (NullRenderer, ConvolutionRenderer, ResolutionRenderer)
                for obs in self.observations):

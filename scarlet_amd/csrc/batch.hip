@@ -225,6 +225,13 @@ struct smi_batch {
     float *morph_param = nullptr, *c_shift_step = nullptr, *c_shift_rel = nullptr;
     int32_t *c_shift_fft = nullptr;
     std::vector<char> is_shift;
+    // starlet components (starlet_source.hip): the view and the arrays it points into
+    smi::StarletView star{};
+    int32_t *st_comp = nullptr, *st_planes = nullptr, *st_fixed = nullptr, *st_toff = nullptr;
+    int64_t *st_coff = nullptr;
+    float *st_thresh = nullptr, *st_coeffs = nullptr, *st_mom[3] = {nullptr, nullptr, nullptr},
+          *st_grad = nullptr, *st_work = nullptr;
+    int64_t n_star_coeffs = 0;
     std::vector<int64_t> h_moff;
     std::vector<int32_t> h_blend;  // owning blend of every component
     // scarlet.lite
@@ -232,7 +239,7 @@ struct smi_batch {
     float *c_sym_strength = nullptr;
     int32_t *c_chain_repeat = nullptr;
     int32_t mono_mask = 0;  // a component carries SMI_PROX_MONO_MASK
-    float *c_pos_floor = nullptr;
+    float *c_pos_floor = nullptr, *c_sed_floor = nullptr;
     double *fista_t = nullptr;
     // free shift of the difference kernel (smi_batch_set_kernel_shift); ks.stamp == nullptr: none
     smi::KernelShiftView ks{};
@@ -371,6 +378,7 @@ void refresh_view(smi_batch *b) {
     v.c_sym_strength = b->c_sym_strength;
     v.c_chain_repeat = b->c_chain_repeat;
     v.c_pos_floor = b->c_pos_floor;
+    v.c_sed_floor = b->c_sed_floor;
     v.c_bg_level = b->c_bg_level;
     v.scheme = b->scheme;
     v.lite = b->scheme == SMI_SCHEME_FISTA || b->lite_flags;
@@ -905,7 +913,9 @@ int smi_batch_destroy(smi_batch *b) {
                     b->g_sed, b->g_morph, b->xp_tmp, b->pt, b->g_center, b->c_sigma, b->c_beta, b->morph_param,
                     b->c_shift_step, b->c_shift_rel, b->c_shift_fft, b->c_center_floor, b->c_sym_strength, b->c_chain_repeat, b->c_pos_floor, b->c_bg_level,
                     b->c_fista_step, b->fista_t, b->have_prev, b->scratch, b->state, b->zero_state, b->n_loss, b->status_out, b->it_base, b->frame_hw, b->pause_at, b->conv_flag, b->shift_scratch,
-                    b->loss_hist, b->last_loss, b->loss_partial, b->d_plans, b->work_items};
+                    b->loss_hist, b->last_loss, b->loss_partial, b->d_plans, b->work_items,
+                    b->c_sed_floor, b->st_comp, b->st_planes, b->st_fixed, b->st_toff, b->st_coff, b->st_thresh,
+                    b->st_coeffs, b->st_mom[0], b->st_mom[1], b->st_mom[2], b->st_grad, b->st_work};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     for (auto e : b->events) (void)hipEventDestroy(e);
@@ -1560,7 +1570,7 @@ static int set_components_impl(smi_batch *b, const smi_components *c, const int3
     } free_old{old_px};
     std::vector<int32_t> start(nb + 1, 0);
     std::vector<int64_t> moff(n + 1, 0);
-    int max_pix = 1, prev = 0;
+    int max_pix = 1, prev = 0, n_star = 0;
     for (int k = 0; k < n; ++k) {
         SMI_REQUIRE(c->blend[k] >= prev && c->blend[k] < nb, "components must be grouped by blend");
         SMI_REQUIRE(c->box_h[k] > 0 && c->box_w[k] > 0, "empty component box");
@@ -1593,8 +1603,24 @@ static int set_components_impl(smi_batch *b, const smi_components *c, const int3
         }
         if (c->prox_flags[k] & SMI_PROX_BG_THRESH)
             SMI_REQUIRE(c->bg_level, "SMI_PROX_BG_THRESH without bg_level");
+        if (c->prox_flags[k] & SMI_COMPONENT_STARLET) {
+            SMI_REQUIRE(!keep, "smi_batch_update_components: starlet components are not supported");
+            SMI_REQUIRE(c->star_planes && c->star_coeffs && c->star_thresh,
+                        "starlet component without star_planes / star_coeffs / star_thresh");
+            SMI_REQUIRE(!(c->prox_flags[k] & ~(SMI_COMPONENT_STARLET | SMI_COMPONENT_FIXED_SED |
+                                               SMI_COMPONENT_FIXED_MORPH)),
+                        "a starlet component takes no other flag than the two FIXED ones");
+            SMI_REQUIRE(b->scheme == SMI_SCHEME_AMSGRAD, "starlet components with SMI_SCHEME_FISTA");
+            SMI_REQUIRE(!b->frame_hw, "frame extents: starlet components are not supported");
+            SMI_REQUIRE(c->star_planes[k] >= 1 && c->star_planes[k] <= 31, "starlet planes out of range");
+            SMI_REQUIRE(c->box_h[k] <= 4096 && c->box_w[k] <= 4096 && np * c->star_planes[k] < ((int64_t)1 << 31),
+                        "starlet component box too large");
+            ++n_star;
+        }
         SMI_REQUIRE(C <= 64, "more than 64 bands");
     }
+    SMI_REQUIRE(!keep || b->star.n_star == 0,
+                "smi_batch_update_components: starlet components are not supported");
     for (int i = 0; i < nb; ++i) start[i + 1] += start[i];
     b->h_comp_start = start;
     b->lite_flags = false;
@@ -1626,7 +1652,12 @@ static int set_components_impl(smi_batch *b, const smi_components *c, const int3
     UP(c_ox, c->origin_x, n);
     UP(c_h, c->box_h, n);
     UP(c_w, c->box_w, n);
-    UP(c_flags, c->prox_flags, n);
+    // the ordinary update kernel steps the spectrum of a starlet component; the image in its
+    // `morph` slot is derived: held fixed there, without constraint
+    std::vector<int32_t> dev_flags(c->prox_flags, c->prox_flags + n);
+    for (int k = 0; k < n; ++k)
+        if (dev_flags[k] & SMI_COMPONENT_STARLET) dev_flags[k] |= SMI_COMPONENT_FIXED_MORPH;
+    UP(c_flags, dev_flags.data(), n);
     UP(c_plan, c->sweep_plan ? c->sweep_plan : noplan.data(), n);
     UP(c_moff, moff.data(), n + 1);
     UP(c_sed_min_step, c->sed_min_step, (size_t)n * C);
@@ -1662,6 +1693,12 @@ static int set_components_impl(smi_batch *b, const smi_components *c, const int3
     } else if (b->c_chain_repeat) {
         SMI_HIP(hipFree(b->c_chain_repeat));
         b->c_chain_repeat = nullptr;
+    }
+    if (c->sed_floor) {
+        UP(c_sed_floor, c->sed_floor, n);
+    } else if (b->c_sed_floor && !keep) {
+        SMI_HIP(hipFree(b->c_sed_floor));
+        b->c_sed_floor = nullptr;
     }
     if (c->bg_level) {
         UP(c_bg_level, c->bg_level, (size_t)n * C);
@@ -1823,6 +1860,59 @@ static int set_components_impl(smi_batch *b, const smi_components *c, const int3
             b->stage_plan[cls] = best;
         }
     }
+    // starlet components: coefficients, thresholds and moments in arrays of their own
+    {
+        std::vector<int32_t> comp, planes, fixed, toff(1, 0);
+        std::vector<int64_t> coff(1, 0);
+        int star_pix = 0;
+        for (int k = 0; k < n; ++k) {
+            if (!(c->prox_flags[k] & SMI_COMPONENT_STARLET)) continue;
+            comp.push_back(k);
+            planes.push_back(c->star_planes[k]);
+            fixed.push_back((c->prox_flags[k] & SMI_COMPONENT_FIXED_MORPH) ? 1 : 0);
+            toff.push_back(toff.back() + c->star_planes[k]);
+            coff.push_back(coff.back() + (int64_t)c->star_planes[k] * (moff[k + 1] - moff[k]));
+            star_pix = std::max(star_pix, (int)(moff[k + 1] - moff[k]));
+        }
+        for (float **p : {&b->st_coeffs, &b->st_mom[0], &b->st_mom[1], &b->st_mom[2], &b->st_grad, &b->st_work})
+            if (*p) {
+                SMI_HIP(hipFree(*p));
+                *p = nullptr;
+            }
+        b->star = smi::StarletView{};
+        b->n_star_coeffs = coff.back();
+        if (n_star) {
+            const size_t nc = (size_t)coff.back();
+            if ((rc = upload(&b->st_comp, comp.data(), comp.size()))) return rc;
+            if ((rc = upload(&b->st_planes, planes.data(), planes.size()))) return rc;
+            if ((rc = upload(&b->st_fixed, fixed.data(), fixed.size()))) return rc;
+            if ((rc = upload(&b->st_toff, toff.data(), toff.size()))) return rc;
+            if ((rc = upload(&b->st_coff, coff.data(), coff.size()))) return rc;
+            if ((rc = upload(&b->st_thresh, c->star_thresh, (size_t)toff.back()))) return rc;
+            if ((rc = upload(&b->st_coeffs, c->star_coeffs, nc))) return rc;
+            for (int i = 0; i < 3; ++i) {
+                SMI_HIP(dev_alloc(&b->st_mom[i], nc));
+                SMI_HIP(hipMemset(b->st_mom[i], 0, nc * sizeof(float)));
+            }
+            SMI_HIP(dev_alloc(&b->st_grad, nc));
+            SMI_HIP(hipMemset(b->st_grad, 0, nc * sizeof(float)));
+            if (starlet_needs_scratch(star_pix)) SMI_HIP(dev_alloc(&b->st_work, 2 * (size_t)b->n_morph));
+            b->star.n_star = n_star;
+            b->star.max_pixels = star_pix;
+            b->star.comp = b->st_comp;
+            b->star.planes = b->st_planes;
+            b->star.fixed = b->st_fixed;
+            b->star.toff = b->st_toff;
+            b->star.coff = b->st_coff;
+            b->star.thresh = b->st_thresh;
+            b->star.coeffs = b->st_coeffs;
+            b->star.m = b->st_mom[0];
+            b->star.v = b->st_mom[1];
+            b->star.vh = b->st_mom[2];
+            b->star.grad = b->st_grad;
+            b->star.work = b->st_work;
+        }
+    }
     b->have_components = true;
     const int max_pixels = b->view.max_box_pixels;
     refresh_view(b);
@@ -1856,6 +1946,7 @@ static int set_components_impl(smi_batch *b, const smi_components *c, const int3
     }
     if ((rc = launch_point_sources(v, nullptr, 0, 0.f, 0, nullptr, nullptr, 2, b->stream))) return rc;
     if ((rc = launch_shift_forward(v, 0, b->stream))) return rc;
+    if ((rc = launch_starlet_forward(v, b->star, 0, b->stream))) return rc;
     SMI_HIP(hipStreamSynchronize(b->stream));
     SMI_HIP(hipGetLastError());
     return SMI_OK;
@@ -1894,7 +1985,8 @@ int smi_batch_get_component_states(smi_batch *b, const int32_t *components, int3
                                    float *states) {
     SMI_REQUIRE(b && b->have_components && (n_sel == 0 || (components && states)),
                 "components not set / null argument");
-    SMI_REQUIRE(b->n_point == 0 && b->n_shift == 0, "state records: factorized image components only");
+    SMI_REQUIRE(b->n_point == 0 && b->n_shift == 0 && b->star.n_star == 0,
+                "state records: factorized image components only");
     if (n_sel == 0) return SMI_OK;
     SMI_HIP(hipSetDevice(b->device));
     const int n = b->d.n_components, C = b->d.C;
@@ -1924,6 +2016,8 @@ int smi_batch_set_iteration_base(smi_batch *b, const int32_t *base) {
     SMI_REQUIRE(b != nullptr, "null batch");
     SMI_REQUIRE(b->n_point == 0 && b->n_shift == 0 && !b->ks.stamp && b->scheme != SMI_SCHEME_FISTA,
                 "smi_batch_set_iteration_base: factorized image components under AMSGrad only");
+    SMI_REQUIRE(!base || b->star.n_star == 0,
+                "smi_batch_set_iteration_base: starlet components are not supported");
     SMI_HIP(hipSetDevice(b->device));
     SMI_HIP(hipStreamSynchronize(b->stream));
     if (!base) {
@@ -1951,6 +2045,7 @@ int smi_batch_set_frame_extents(smi_batch *b, const int32_t *h, const int32_t *w
     SMI_REQUIRE(b->n_point == 0 && b->n_shift == 0,
                 "frame extents: point sources and shifting components are not supported");
     SMI_REQUIRE(!b->ks.stamp, "frame extents: a shifting difference kernel is not supported");
+    SMI_REQUIRE(b->star.n_star == 0, "frame extents: starlet components are not supported");
     SMI_REQUIRE(b->lowres.empty() && b->layers.empty(),
                 "frame extents: further observations are not supported");
     const int nb = b->d.n_blends;
@@ -2210,6 +2305,41 @@ int smi_batch_set_parameters(smi_batch *b, const float *sed, const float *morph)
             if (rc) return rc;
             SMI_HIP(hipStreamSynchronize(b->stream));
         }
+        if (b->star.n_star) {  // the image of a starlet component is derived from its coefficients
+            int rc = launch_starlet_forward(unmasked_view(b), b->star, 0, b->stream);
+            if (rc) return rc;
+            SMI_HIP(hipStreamSynchronize(b->stream));
+        }
+    }
+    return SMI_OK;
+}
+
+int smi_batch_get_starlet(smi_batch *b, float *coeffs, float *m, float *v, float *vhat,
+                          float *gradient) {
+    SMI_REQUIRE(b && b->have_components, "components not set");
+    SMI_HIP(hipSetDevice(b->device));
+    SMI_HIP(hipStreamSynchronize(b->stream));
+    const size_t bytes = (size_t)b->n_star_coeffs * sizeof(float);
+    if (!bytes) return SMI_OK;
+    float *dst[5] = {coeffs, m, v, vhat, gradient};
+    const float *src[5] = {b->st_coeffs, b->st_mom[0], b->st_mom[1], b->st_mom[2], b->st_grad};
+    for (int i = 0; i < 5; ++i)
+        if (dst[i]) SMI_HIP(hipMemcpy(dst[i], src[i], bytes, hipMemcpyDeviceToHost));
+    return SMI_OK;
+}
+
+int smi_batch_set_starlet_moments(smi_batch *b, const float *m, const float *v, const float *vhat) {
+    SMI_REQUIRE(b && b->have_components, "components not set");
+    SMI_HIP(hipSetDevice(b->device));
+    SMI_HIP(hipStreamSynchronize(b->stream));  // pending steps may still read the old arrays
+    const size_t bytes = (size_t)b->n_star_coeffs * sizeof(float);
+    if (!bytes) return SMI_OK;
+    const float *src[3] = {m, v, vhat};
+    for (int i = 0; i < 3; ++i) {
+        if (src[i])
+            SMI_HIP(hipMemcpy(b->st_mom[i], src[i], bytes, hipMemcpyHostToDevice));
+        else
+            SMI_HIP(hipMemset(b->st_mom[i], 0, bytes));
     }
     return SMI_OK;
 }
@@ -2323,6 +2453,7 @@ int smi_batch_gradient(smi_batch *b, float *g_sed, float *g_morph) {
     if ((rc = launch_point_sources(v, b->Q, 0, 0.f, 0, b->g_sed, b->g_center, 1, b->stream)))
         return rc;
     if ((rc = launch_shift_backward(v, b->Q, 0, b->g_center, 1, b->stream))) return rc;
+    if ((rc = launch_starlet_step(v, b->star, b->Q, 0, 0.f, 0, 1, b->stream))) return rc;
     SMI_HIP(hipStreamSynchronize(b->stream));
     if (g_sed)
         SMI_HIP(hipMemcpy(g_sed, b->g_sed, (size_t)v.n_comp * v.C * sizeof(float),
@@ -2336,8 +2467,8 @@ int smi_batch_gradient(smi_batch *b, float *g_sed, float *g_morph) {
 
 // nothing but factorized components under one fused convolution
 static bool plain_batch(const smi_batch *b) {
-    return b->fused && b->n_point == 0 && b->n_shift == 0 && b->lowres.empty() &&
-           b->layers.empty() && !b->ks.stamp;
+    return b->fused && b->n_point == 0 && b->n_shift == 0 && b->star.n_star == 0 &&
+           b->lowres.empty() && b->layers.empty() && !b->ks.stamp;
 }
 
 // A plain batch needs the model only as the input rows of the convolution, and the
@@ -2352,7 +2483,7 @@ static bool inline_render(const smi_batch *b) {
     // the convolution runs; further observations, a low-resolution term and a free kernel shift
     // read the cube)
     return allowed && b->inline_render && b->fused && b->lowres.empty() && b->layers.empty() &&
-           !b->ks.stamp && b->view.render_slots > 0;
+           !b->ks.stamp && b->star.n_star == 0 && b->view.render_slots > 0;
 }
 
 
@@ -2541,6 +2672,9 @@ int smi_batch_step(smi_batch *b, int32_t it0, int32_t n_iter, float e_rel, int32
         }
         lowres_add_all(b);
         if ((rc = launch_shift_backward(v, b->Q, it, nullptr, 0, b->stream))) return rc;
+        // (before the spectra move: the coefficient gradient belongs to this iteration's spectrum)
+        if ((rc = launch_starlet_step(v, b->star, b->Q, it, e_rel, prox_max_iter, 0, b->stream)))
+            return rc;
         if (plain) {  // (the loss bookkeeping rides along with the updates)
             if ((rc = launch_update_finalize(v, b->Q, it, e_rel, min_iter, check, prox_max_iter,
                                              b->stream)))
@@ -2553,6 +2687,7 @@ int smi_batch_step(smi_batch *b, int32_t it0, int32_t n_iter, float e_rel, int32
                                        b->stream)))
             return rc;
         if ((rc = launch_shift_forward(v, 1, b->stream))) return rc;
+        if ((rc = launch_starlet_forward(v, b->star, 1, b->stream))) return rc;
         if (b->ks.stamp && (rc = refresh_shifted_kernel(b, 1))) return rc;
         if (check) launch_advance(v, b->stream);
         if (ev) SMI_HIP(hipEventRecord(ev[5], b->stream));
@@ -2680,6 +2815,7 @@ void mutable_state(smi_batch *b, void **ptr, size_t *bytes) {
 
 int smi_batch_save_state(smi_batch *b) {
     SMI_REQUIRE(b && b->have_components, "components not set");
+    SMI_REQUIRE(b->star.n_star == 0, "smi_batch_save_state: starlet components are not supported");
     SMI_HIP(hipSetDevice(b->device));
     void *ptr[12];
     size_t bytes[12];
@@ -2699,6 +2835,7 @@ int smi_batch_save_state(smi_batch *b) {
 
 int smi_batch_restore_state(smi_batch *b) {
     SMI_REQUIRE(b && b->have_components, "components not set");
+    SMI_REQUIRE(b->star.n_star == 0, "smi_batch_restore_state: starlet components are not supported");
     SMI_HIP(hipSetDevice(b->device));
     void *ptr[12];
     size_t bytes[12];

@@ -263,6 +263,7 @@ struct BatchView {
     const float *c_center_floor;
     const float *c_sym_strength;  // SymmetryConstraint(strength)
     const float *c_pos_floor;  // PositivityConstraint(zero) of the morphology
+    const float *c_sed_floor = nullptr;  // ... of the spectrum; nullptr: 1e-20 everywhere
     const int32_t *c_chain_repeat;  // ConstraintChain(repeat); nullptr when every chain runs once
     const float *c_bg_level;
     float *scratch;              // 3 * n_morph floats when the largest box exceeds the LDS
@@ -345,6 +346,38 @@ bool shift_needs_scratch(int max_box_pixels, int max_box_side);
 int launch_shift_backward(const BatchView &v, const float *G, int32_t it, double *g_shift_out,
                           int32_t grad_only, hipStream_t s);
 int launch_shift_forward(const BatchView &v, int32_t respect_state, hipStream_t s);
+
+// Starlet components (starlet_source.hip; SMI_COMPONENT_STARLET): the parameter of the
+// morphology is the (planes, h, w) stack of starlet coefficients, kept with its moments in
+// arrays of its own -- component comp[s] owns [coff[s], coff[s + 1]) of them and the per-plane
+// thresholds [toff[s], toff[s + 1]) -- while the component's `morph` slot holds the
+// reconstruction the model uses.  Step and positivity floor: c_morph_step / c_pos_floor.
+struct StarletView {
+    int32_t n_star = 0;
+    int32_t max_pixels = 0;   // largest box among the starlet components
+    const int32_t *comp = nullptr;
+    const int32_t *planes = nullptr;
+    const int32_t *fixed = nullptr;  // Parameter(fixed=True): zero gradient, prox still applied
+    const int64_t *coff = nullptr;
+    const int32_t *toff = nullptr;
+    const float *thresh = nullptr;
+    float *coeffs = nullptr, *m = nullptr, *v = nullptr, *vh = nullptr;
+    // the cascade a_0 .. a_S of the last gradient evaluation; a step leaves the pre-prox
+    // coefficients there
+    float *grad = nullptr;
+    // work planes of boxes beyond the LDS: 2 N floats per component at 2 c_moff[k] (nullptr:
+    // every starlet box of the batch has at most kStarLdsPixels pixels and they live in LDS)
+    float *work = nullptr;
+};
+constexpr int kStarLdsPixels = 20000;  // two float planes + reduction scratch in 160 KiB
+bool starlet_needs_scratch(int max_pixels);
+// the box gradient and its cascade; unless grad_only also the AMSGrad / proximal update of the
+// coefficients (of blends that are still iterating)
+int launch_starlet_step(const BatchView &v, const StarletView &sv, const float *G, int32_t it,
+                        float e_rel, int32_t prox_max_iter, int32_t grad_only, hipStream_t s);
+// coefficients -> the `morph` slots
+int launch_starlet_forward(const BatchView &v, const StarletView &sv, int32_t respect_state,
+                           hipStream_t s);
 
 // ConvolutionRenderer(psf_shift=...) (renderer.py:175-177, 215-228): the difference kernel
 // carries a free sub-pixel Fourier shift, one per kernel set (the batch's kernel, or one

@@ -573,9 +573,10 @@ __device__ __forceinline__ int update_spectrum(const BatchView &v, const CompCtx
     }
     const float pmax = wave_max(psi);
     const float ratio = on ? psi / pmax : 0.f;
+    const float floor_ = v.c_sed_floor ? v.c_sed_floor[c.k] : 1e-20f;
     float z = x;
     for (int tau = 0; tau < prox_max_iter; ++tau) {
-        const float zn = on ? max_nan(z - ratio * (z - x), 1e-20f) : 0.f;
+        const float zn = on ? max_nan(z - ratio * (z - x), floor_) : 0.f;
         const float d2 = wave_sum((zn - z) * (zn - z));
         const float z2 = wave_sum(z * z);
         z = zn;

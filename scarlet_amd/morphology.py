@@ -1,6 +1,6 @@
-"""Image morphologies of factorized components (reference
-scarlet/morphology.py:26-207, 476-513, 607-688).  Parametric profiles (Gaussian,
-Spergel, starlet) are outside the scope of this package."""
+"""Image and starlet morphologies of factorized components (reference
+scarlet/morphology.py:26-207, 476-604, 607-688).  Parametric profiles (Gaussian,
+Spergel) are outside the scope of this package."""
 
 import numpy as np
 import numpy.ma as ma
@@ -9,6 +9,8 @@ from .bbox import Box, overlapped_slices
 from .constraint import (
     CenterOnConstraint,
     ConstraintChain,
+    L0Constraint,
+    MonotonicMaskConstraint,
     MonotonicityConstraint,
     NormalizationConstraint,
     PositivityConstraint,
@@ -230,3 +232,122 @@ class PointSourceMorphology(Morphology):
     @property
     def integral(self):
         return self.psf.get_model().sum()
+
+
+def starlet_thresholds(norm, threshold):
+    """Absolute hard threshold of every coefficient plane of a ``StarletMorphology``:
+    ``threshold`` times the norm of that scale's wavelet, and no threshold on the last
+    (coarse) plane (morphology.py:549-556).  ``norm``: ``Starlet.norm``, one entry per plane."""
+    per_plane = np.zeros(len(norm)) + threshold
+    per_plane *= np.asarray(norm, dtype=np.float64)
+    per_plane[-1] = 0
+    return per_plane
+
+
+def shrink_slices(old_origin, old_shape, new_origin, new_shape):
+    """Slices that cut the last two axes of an array over the box ``(old_origin, old_shape)``
+    down to its overlap with the box ``(new_origin, new_shape)``: what a shrink applies to
+    coefficients and moments (morphology.py:582-598)."""
+    return tuple(slice(max(n - o, 0), min(n - o + size, extent))
+                 for o, extent, n, size in zip(old_origin[-2:], old_shape[-2:],
+                                               new_origin[-2:], new_shape[-2:]))
+
+
+def plane_thresholds(constraint):
+    """``(positivity floor, threshold per plane)`` of the constraint a non-monotonic
+    ``StarletMorphology`` puts on its coefficients -- ``ConstraintChain(PositivityConstraint,
+    L0Constraint(absolute))``, applied once, with a threshold that is constant over every
+    plane -- or ``None`` for anything else (which the device loop does not run)."""
+    if not isinstance(constraint, ConstraintChain) or constraint.repeat != 1:
+        return None
+    if len(constraint.constraints) != 2:
+        return None
+    positive, hard = constraint.constraints
+    if type(positive) is not PositivityConstraint or type(hard) is not L0Constraint:
+        return None
+    if hard.type != "absolute":
+        return None
+    thresh = np.asarray(hard.thresh, dtype=np.float64)
+    if thresh.ndim == 3:
+        flat = thresh.reshape(len(thresh), -1)
+        if not np.all(flat == flat[:, :1]):
+            return None
+        thresh = flat[:, 0]
+    if thresh.ndim != 1:
+        return None
+    return float(positive.zero), thresh
+
+
+class StarletMorphology(Morphology):
+    """Morphology whose parameter ``coeffs`` is the stack of generation-2 starlet
+    coefficients of an image, all scales the box admits; the model is their reconstruction.
+
+    Not monotonic (the default): the coefficients are kept positive and every plane but the
+    last is hard-thresholded at ``threshold`` times the norm of its wavelet.  ``monotonic``:
+    a ``MonotonicMaskConstraint`` about the middle of the box instead (constructed here;
+    ``Blend.fit`` does not run it).  The transform runs on the device, so the coefficients
+    are the reference's bit for bit.
+
+    Unlike the reference, a shrink keeps the thresholds per plane: the reference's
+    ``L0Constraint`` holds an array of the old box's shape and fails at the next proximal
+    step."""
+
+    def __init__(self, frame, image, bbox=None, monotonic=False, threshold=0):
+        from .wavelet import Starlet
+
+        if bbox is None:
+            assert frame.bbox[1:].shape == image.shape
+            bbox = Box(image.shape)
+        self.monotonic = monotonic
+        self.transform = Starlet.from_image(image)
+        coeffs = self.transform.coefficients
+        if monotonic:
+            middle = tuple(n // 2 for n in bbox.shape)
+            constraint = MonotonicMaskConstraint(middle, center_radius=1)
+        else:
+            per_plane = starlet_thresholds(self.transform.norm, threshold)
+            constraint = ConstraintChain(
+                PositivityConstraint(0),
+                L0Constraint(np.broadcast_to(per_plane[:, None, None], coeffs.shape).copy()))
+        super().__init__(frame, Parameter(coeffs, name="coeffs", step=1e-2, constraint=constraint),
+                         bbox=bbox)
+
+    def get_model(self, *parameters):
+        from .wavelet import starlet_reconstruction
+
+        return starlet_reconstruction(np.asarray(self.get_parameter(0, *parameters)))
+
+    def update(self):
+        """Every 10 iterations: peel off borders the reconstruction leaves empty (below
+        1e-8).  Coefficients and moments are cut to the new box, planes and step stay
+        (morphology.py:572-604)."""
+        coeffs = self.get_parameter(0)
+        if coeffs.fixed:
+            return
+        before = self.bbox.copy()
+        self.shrink_box(self.get_model(), thresh=1e-8)
+        if before == self.bbox:
+            return
+        cut = (slice(None),) + shrink_slices(before.origin, before.shape, self.bbox.origin,
+                                             self.bbox.shape)
+
+        def sliced(a):
+            return None if a is None else np.asarray(a)[cut]
+
+        constraint = coeffs.constraint
+        if self.monotonic:
+            constraint = MonotonicMaskConstraint(tuple(n // 2 for n in self.bbox.shape),
+                                                 center_radius=1)
+        else:
+            rule = plane_thresholds(constraint)
+            if rule is not None:  # the thresholds never depended on the pixel
+                floor, per_plane = rule
+                constraint = ConstraintChain(
+                    PositivityConstraint(floor),
+                    L0Constraint(np.broadcast_to(
+                        per_plane[:, None, None], (len(per_plane),) + tuple(self.bbox.shape)).copy()))
+        shrunk = Parameter(np.asarray(coeffs)[cut].copy(), name=coeffs.name, prior=coeffs.prior,
+                           constraint=constraint, step=coeffs.step, fixed=coeffs.fixed,
+                           m=sliced(coeffs.m), v=sliced(coeffs.v), vhat=sliced(coeffs.vhat))
+        self._parameters = (shrunk,) + self._parameters[1:]
+        raise UpdateException

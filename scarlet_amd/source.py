@@ -1,9 +1,11 @@
 """Extended-source models (reference scarlet/source.py:249-522, 615-807):
 ``ExtendedSource`` factory -> ``SingleExtendedSource`` / ``MultiExtendedSource`` /
-``CompactExtendedSource``, and ``PointSource`` (source.py:92-128).  Gaussian,
-Spergel, starlet and random sources are outside the scope of this package."""
+``CompactExtendedSource``, ``PointSource`` (source.py:92-128), ``RandomSource``
+(source.py:61-89) and ``StarletSource`` (source.py:525-612).  Gaussian and Spergel sources
+are outside the scope of this package."""
 
 import logging
+from functools import partial
 
 import numpy as np
 
@@ -11,9 +13,10 @@ from . import initialization as init
 from . import operator
 from .bbox import Box, overlapped_slices
 from .component import CombinedComponent, FactorizedComponent
-from .constraint import CenterOnConstraint
-from .morphology import ExtendedSourceMorphology, PointSourceMorphology
-from .parameter import Parameter
+from .constraint import CenterOnConstraint, PositivityConstraint
+from .morphology import (ExtendedSourceMorphology, ImageMorphology, PointSourceMorphology,
+                         StarletMorphology)
+from .parameter import Parameter, relative_step
 from .spectrum import TabulatedSpectrum
 
 logger = logging.getLogger("scarlet_amd.source")
@@ -45,6 +48,20 @@ def _fitted_morphology(frame, sky_coord, image, bbox, shifting, resizing):
     return ExtendedSourceMorphology(
         frame, frame.get_pixel(sky_coord), image, bbox=bbox, monotonic="angle",
         symmetric=False, min_grad=0, shifting=shifting, resizing=resizing)
+
+
+class RandomSource(FactorizedComponent):
+    """A source without a shape of its own: uniform random numbers over the whole model
+    frame as image, then as spectrum (drawn from ``np.random`` in that order).  The spectrum
+    moves in steps of a tenth of its mean and is kept non-negative."""
+
+    def __init__(self, model_frame, observations=None):
+        n_channels, height, width = model_frame.bbox.shape
+        morphology = ImageMorphology(model_frame, np.random.rand(height, width))
+        amplitudes = Parameter(np.random.rand(n_channels), name="spectrum",
+                               step=partial(relative_step, factor=1e-1),
+                               constraint=PositivityConstraint())
+        super().__init__(model_frame, TabulatedSpectrum(model_frame, amplitudes), morphology)
 
 
 class PointSource(FactorizedComponent):
@@ -165,6 +182,48 @@ class SingleExtendedSource(FactorizedComponent):
             floor, _ = CompactExtendedSource.init_morph(frame, sky_coord, boxsize=max(bbox.shape))
             image = np.maximum(image, floor)
         return image, bbox
+
+
+class StarletSource(FactorizedComponent):
+    """A source whose morphology is a stack of starlet coefficients (``StarletMorphology``).
+
+    With ``sky_coord`` it starts from the ``ExtendedSource`` at that position, without one
+    from a ``RandomSource`` over the whole frame: diffuse light that is neither monotonic nor
+    symmetric.  ``spectrum`` replaces the initial spectrum (a ``Parameter`` named "spectrum",
+    or an array, which then takes the noise of ``observations`` as its minimal step).
+    ``starlet_thresh`` is the hard threshold of all but the coarsest plane in units of the
+    norm of every scale's wavelet; ``monotonic`` asks for monotonic planes instead."""
+
+    def __init__(self, model_frame, sky_coord=None, observations=None, spectrum=None, thresh=1.0,
+                 monotonic=False, starlet_thresh=5e-3, boxsize=None):
+        if sky_coord is None:
+            seed = RandomSource(model_frame)
+        else:
+            seed = ExtendedSource(model_frame, sky_coord, observations, thresh=thresh,
+                                  boxsize=boxsize)
+        converted = StarletSource.from_source(seed, monotonic=monotonic,
+                                              starlet_thresh=starlet_thresh)
+        own_spectrum, morphology = converted.children
+        if spectrum is not None:
+            if isinstance(spectrum, Parameter):
+                assert spectrum.name == "spectrum"
+                own_spectrum = spectrum
+            else:
+                own_spectrum = TabulatedSpectrum(
+                    model_frame, spectrum, min_step=_noise_rms(_as_sequence(observations)))
+        super().__init__(converted.frame, own_spectrum, morphology)
+
+    @classmethod
+    def from_source(cls, source, monotonic=False, starlet_thresh=5e-3):
+        """The factorized ``source`` with its morphology turned into starlet coefficients
+        of the image it models now; the spectrum object is shared."""
+        assert isinstance(source, FactorizedComponent)
+        spectrum, morphology = source.children
+        starlets = StarletMorphology(source.frame, morphology.get_model(), bbox=morphology.bbox,
+                                     monotonic=monotonic, threshold=starlet_thresh)
+        made = cls.__new__(cls)
+        FactorizedComponent.__init__(made, source.frame, spectrum, starlets)
+        return made
 
 
 class MultiExtendedSource(CombinedComponent):
