@@ -170,8 +170,16 @@ enum {
      * star_* fields of smi_components.  SMI_COMPONENT_FIXED_MORPH fixes the coefficients.
      * No other prox flag: the constraint is PositivityConstraint(pos_floor) followed by the
      * per-plane hard threshold star_thresh. */
-    SMI_COMPONENT_STARLET = 1 << 20
+    SMI_COMPONENT_STARLET = 1 << 20,
+    /* the morphology is a radial profile of a few float64 numbers, which are the parameters
+     * (GaussianSource / SpergelSource, source.py:131-246; ProfileMorphology, morphology.py:210-473):
+     * see the prof_* fields of smi_components.  The only other flag it takes is
+     * SMI_COMPONENT_FIXED_SED; its parameters are fixed one by one through prof_fixed. */
+    SMI_COMPONENT_PROFILE = 1 << 21
 };
+enum { SMI_PROFILE_GAUSSIAN = 0, SMI_PROFILE_SPERGEL = 1 };
+/* bits of prof_fixed and order of the four entries of prof_step / prof_rel_step */
+enum { SMI_PROFILE_CENTER = 0, SMI_PROFILE_RADIUS = 1, SMI_PROFILE_ELLIPTICITY = 2, SMI_PROFILE_NU = 3 };
 #define SMI_PROX_EXTENDED_SOURCE \
     (SMI_PROX_MONOTONIC | SMI_PROX_POSITIVE | SMI_PROX_CENTER_ON | SMI_PROX_NORM_MAX)
 
@@ -261,6 +269,17 @@ typedef struct smi_components {
     const float *sed_floor;     /* [n_components] PositivityConstraint(zero) of the spectrum: */
                                 /* 1e-20 (spectrum.py:54-56) or 0 (RandomSource,              */
                                 /* source.py:81-86); NULL = 1e-20                             */
+    /* profile components (SMI_COMPONENT_PROFILE in prox_flags); all NULL if none, entries of
+     * other components are ignored.  `morph` is ignored for such a component (the library
+     * evaluates exp(-R2 / 2) or the Spergel profile on the box, unnormalised, in double). */
+    const int32_t *prof_kind;    /* [n_components] SMI_PROFILE_*                              */
+    const double *prof_params;   /* [n_components][6] centre y, x (model-frame pixels),       */
+                                 /* radius, e1, e2, nu (ignored by a Gaussian)                */
+    const double *prof_step;     /* [n_components][4] constant step (or the minimum of a      */
+                                 /* relative step) of centre, radius, ellipticity, nu         */
+    const double *prof_rel_step; /* [n_components][4] relative_step factor (parameter.py:     */
+                                 /* 126-129: max(minimum, factor * mean)); 0 = constant step  */
+    const int32_t *prof_fixed;   /* [n_components] bit 1 << SMI_PROFILE_*: Parameter(fixed)   */
 } smi_components;
 
 int smi_batch_create(const smi_batch_desc *desc, int device, smi_batch **out);
@@ -364,6 +383,22 @@ int smi_batch_set_parameters(smi_batch *b, const float *sed, const float *morph)
 int smi_batch_get_starlet(smi_batch *b, float *coeffs, float *m, float *v, float *vhat,
                           float *gradient);
 int smi_batch_set_starlet_moments(smi_batch *b, const float *m, const float *v, const float *vhat);
+/* Profile components: the six doubles {centre y, x, radius, e1, e2, nu} of every component
+ * ([n_components][6], zeros for the others), their AMSGrad moments and the gradient of -logL
+ * w.r.t. them (valid after smi_batch_gradient or a step); any pointer may be NULL.  The nu entry
+ * of the gradient follows the reference's fit: the derivative of K_nu w.r.t. its order is left
+ * out (morphology.py:380-381).  smi_batch_get_parameters returns the float32 image of such a
+ * component.  smi_batch_set_profile_moments: warm start (NULL = zeros).  The calls that refuse
+ * starlet components refuse profile components too. */
+int smi_batch_get_profiles(smi_batch *b, double *params, double *m, double *v, double *vhat,
+                           double *gradient);
+int smi_batch_set_profile_moments(smi_batch *b, const double *m, const double *v,
+                                  const double *vhat);
+/* Probe: the profile `kind` with the six doubles `params` on the h x w box at (origin_y,
+ * origin_x), evaluated on `device` in double: out[0] the values, out[1 .. 6] the partial
+ * derivatives w.r.t. the six doubles (out is [7][h][w], host memory). */
+int smi_profile_probe(int device, int32_t kind, const double *params, int32_t h, int32_t w,
+                      int32_t origin_y, int32_t origin_x, double *out);
 
 /* Update rule of the parameters.  SMI_SCHEME_AMSGRAD (default): proxmin.adaprox as used
  * by Blend.fit and lite's AdaproxParameter.  SMI_SCHEME_FISTA: lite's FistaParameter

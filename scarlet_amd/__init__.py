@@ -42,6 +42,9 @@ from .morphology import (  # noqa: F401
     ExtendedSourceMorphology,
     PointSourceMorphology,
     StarletMorphology,
+    ProfileMorphology,
+    GaussianMorphology,
+    SpergelMorphology,
 )
 from .component import (  # noqa: F401
     Component,
@@ -59,6 +62,8 @@ from .source import (  # noqa: F401
     PointSource,
     RandomSource,
     StarletSource,
+    GaussianSource,
+    SpergelSource,
 )
 from .model import Model, UpdateException  # noqa: F401
 from .wavelet import Starlet  # noqa: F401

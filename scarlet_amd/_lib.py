@@ -34,6 +34,8 @@ COMPONENT_SHIFTING = 1 << 17  # image morphology moved by a free Fourier shift
 COMPONENT_FIXED_SED = 1 << 18
 COMPONENT_FIXED_MORPH = 1 << 19
 COMPONENT_STARLET = 1 << 20  # morphology = reconstruction of starlet coefficients (the parameter)
+COMPONENT_PROFILE = 1 << 21  # morphology = Gaussian / Spergel profile of six float64 numbers
+PROFILE_GAUSSIAN, PROFILE_SPERGEL = 0, 1
 PROX_EXTENDED_SOURCE = PROX_MONOTONIC | PROX_POSITIVE | PROX_CENTER_ON | PROX_NORM_MAX
 
 ERR_ARITHMETIC = -4
@@ -67,6 +69,8 @@ class Components(ctypes.Structure):
         ("shift_rel_step", c_f32p), ("psf_beta", c_f32p),
         ("star_planes", c_i32p), ("star_coeffs", c_f32p), ("star_thresh", c_f32p),
         ("sed_floor", c_f32p),
+        ("prof_kind", c_i32p), ("prof_params", c_f64p), ("prof_step", c_f64p),
+        ("prof_rel_step", c_f64p), ("prof_fixed", c_i32p),
     ]
 
 
@@ -170,6 +174,10 @@ SYMBOLS = {
     "smi_batch_set_centers": (ctypes.c_int, [ctypes.c_void_p, c_f64p]),
     "smi_batch_get_model_morphology": (ctypes.c_int, [ctypes.c_void_p, c_f32p]),
     "smi_batch_get_starlet": (ctypes.c_int, [ctypes.c_void_p] + [c_f32p] * 5),
+    "smi_batch_get_profiles": (ctypes.c_int, [ctypes.c_void_p] + [c_f64p] * 5),
+    "smi_batch_set_profile_moments": (ctypes.c_int, [ctypes.c_void_p] + [c_f64p] * 3),
+    "smi_profile_probe": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, c_f64p] + [ctypes.c_int32] * 4
+                          + [c_f64p]),
     "smi_batch_set_starlet_moments": (ctypes.c_int, [ctypes.c_void_p] + [c_f32p] * 3),
     "smi_batch_set_scheme": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "smi_batch_get_fista_state": (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, c_f64p]),

@@ -21,7 +21,7 @@ class ComponentSpec:
                  neighbor_weight="angle", min_gradient=0.0, l_thresh=0.0, shift=None,
                  shift_step=1e-1, center_floor=1e-6, bg_level=None, fista_step=0.0,
                  sym_strength=1.0, chain_repeat=1, pos_floor=0.0, shift_rel_step=0.0,
-                 starlet=None, sed_floor=None):
+                 starlet=None, sed_floor=None, profile=None):
         self.sed = np.asarray(sed, dtype=np.float32)
         # PositivityConstraint(zero) of the spectrum; None: the 1e-20 of spectrum.py:54-56
         self.sed_floor = None if sed_floor is None else float(sed_floor)
@@ -68,6 +68,19 @@ class ComponentSpec:
             assert self.star_thresh.shape == self.star_coeffs.shape[:1]
             fixed = _lib.COMPONENT_FIXED_SED | _lib.COMPONENT_FIXED_MORPH
             self.prox_flags = _lib.COMPONENT_STARLET | (self.prox_flags & fixed)
+        # ProfileMorphology (morphology.py:210-473): ``profile = dict(kind=PROFILE_*, params=
+        # (centre y, x, radius, e1, e2, nu), step=, rel_step= (centre, radius, ellipticity, nu),
+        # fixed=bit mask of the four)``; ``morph`` only gives the box shape.  Of ``prox_flags``
+        # only COMPONENT_FIXED_SED is kept.
+        self.profile = None
+        if profile is not None:
+            self.profile = dict(
+                kind=int(profile["kind"]),
+                params=np.array(profile["params"], dtype=np.float64).reshape(6),
+                step=np.array(profile["step"], dtype=np.float64).reshape(4),
+                rel_step=np.array(profile.get("rel_step", np.zeros(4)), dtype=np.float64).reshape(4),
+                fixed=int(profile.get("fixed", 0)))
+            self.prox_flags = _lib.COMPONENT_PROFILE | (self.prox_flags & _lib.COMPONENT_FIXED_SED)
 
 
 class PointSourceSpec(ComponentSpec):
@@ -142,6 +155,12 @@ class BlendBatch:
     def __init__(self, data, weights, components, kernel=None, max_iter=200,
                  fft_shape=None, device=0, conv_path="auto", scheme="amsgrad", log_norm=True,
                  frame_shapes=None):
+        if any(getattr(c, "profile", None) is not None for blend in components for c in blend):
+            # (refused by the library as well; here before any device work)
+            if scheme != "amsgrad":
+                raise NotImplementedError("profile components with scheme={!r} (FISTA)".format(scheme))
+            if frame_shapes is not None:
+                raise NotImplementedError("profile components with frame extents")
         lib = _lib.load()
         self._lib = lib
         self._h = ctypes.c_void_p()
@@ -196,6 +215,8 @@ class BlendBatch:
     def set_frame_extents(self, frame_shapes):
         """One ``(h, w)`` per blend with ``1 <= h <= H``, ``1 <= w <= W``, or ``None`` for
         the full frame everywhere (``smi_batch_set_frame_extents``)."""
+        if frame_shapes is not None and getattr(self, "_profile", None):
+            raise NotImplementedError("profile components with frame extents")
         if frame_shapes is None:
             _lib.check(self._lib.smi_batch_set_frame_extents(self._h, None, None))
             self.frame_shapes = None
@@ -299,6 +320,24 @@ class BlendBatch:
         if any(c.sed_floor is not None for c in flat):
             floors = _lib.f32([1e-20 if c.sed_floor is None else c.sed_floor for c in flat])
         arrays["sed_floor"] = floors
+        # profile components: per-component rows, sent only when there is one
+        profiles = [getattr(c, "profile", None) for c in flat]
+        self._profile = [k for k, p in enumerate(profiles) if p is not None]
+        if self._profile:
+            def rows_of(name, width, dtype):
+                out = np.zeros((len(flat), width), dtype=dtype)
+                for k in self._profile:
+                    out[k] = profiles[k][name]
+                return np.ascontiguousarray(out.reshape(-1) if width == 1 else out)
+
+            arrays["prof_kind"] = rows_of("kind", 1, np.int32)
+            arrays["prof_params"] = rows_of("params", 6, np.float64)
+            arrays["prof_step"] = rows_of("step", 4, np.float64)
+            arrays["prof_rel_step"] = rows_of("rel_step", 4, np.float64)
+            arrays["prof_fixed"] = rows_of("fixed", 1, np.int32)
+        else:
+            for name in ("prof_kind", "prof_params", "prof_step", "prof_rel_step", "prof_fixed"):
+                arrays[name] = None
         comps = _lib.Components()
         for name, ctype in _lib.Components._fields_:
             if arrays[name] is None:
@@ -797,6 +836,28 @@ class BlendBatch:
         arrs = [pack(m), pack(v), pack(vhat)]
         _lib.check(self._lib.smi_batch_set_starlet_moments(
             self._h, *[_lib.ptr(a, ctypes.c_float) for a in arrs]))
+
+    # -- profile components ---------------------------------------------------------
+    def profile_state(self):
+        """State of the profile components: ``components`` (their indices) and, as
+        ``(n_components, 6)`` float64 arrays with rows {centre y, x, radius, e1, e2, nu} (zeros
+        for other components), ``params``, ``m``, ``v``, ``vhat`` and -- valid after
+        ``gradient()`` or a step -- ``gradient`` of ``-logL``."""
+        names = ("params", "m", "v", "vhat", "gradient")
+        bufs = [np.zeros((self.n_components, 6), dtype=np.float64) for _ in names]
+        _lib.check(self._lib.smi_batch_get_profiles(
+            self._h, *[_lib.ptr(b, ctypes.c_double) for b in bufs]))
+        out = dict(zip(names, bufs))
+        out["components"] = list(self._profile)
+        return out
+
+    def set_profile_moments(self, m=None, v=None, vhat=None):
+        """Warm start of the profile parameters' AMSGrad moments: ``(n_components, 6)``
+        arrays (rows of other components are ignored), or ``None`` for zeros."""
+        arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape(
+            self.n_components, 6) for a in (m, v, vhat)]
+        _lib.check(self._lib.smi_batch_set_profile_moments(
+            self._h, *[_lib.ptr(a, ctypes.c_double) for a in arrs]))
 
     def has_shift(self, k):
         """True if component ``k`` carries a Fourier shift on the device."""

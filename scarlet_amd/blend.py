@@ -21,7 +21,8 @@ from .component import CombinedComponent, FactorizedComponent
 from .constraint import PositivityConstraint, device_flags
 from .hoststep import HostBandSource, HostParameter, HostVector
 from .model import UpdateException
-from .morphology import PointSourceMorphology, StarletMorphology, plane_thresholds
+from .morphology import (GaussianMorphology, PointSourceMorphology, ProfileMorphology, ProfileProx,
+                         SpergelMorphology, StarletMorphology, plane_thresholds)
 from .psf import GaussianPSF, ImagePSF, MoffatPSF
 from .parameter import relative_step, STD_FROM_V
 from .renderer import ConvolutionRenderer, NullRenderer, ResolutionRenderer
@@ -198,6 +199,82 @@ def _refuse_unfittable_starlets(sources, scheme):
                 _starlet_rules(src.children[1], scheme)
         elif isinstance(src, CombinedComponent):
             _refuse_unfittable_starlets(src.children, scheme)
+
+
+# the four parameters of a profile component in the order of the device's step / fixed tables
+_PROFILE_GROUPS = ("center", "radius", "ellipticity", "nu")
+
+
+def _profile_rules(morphology, scheme):
+    """``dict(kind, params, step, rel_step, fixed)`` of a ``GaussianMorphology`` /
+    ``SpergelMorphology`` as the device runs it; ``NotImplementedError`` for what it does not:
+    a subclass with a profile function of its own (no gradient without autograd), another
+    scheme than amsgrad, a prior, another constraint than the morphology's own, a step
+    callable other than ``relative_step`` or a ``partial`` of it."""
+    if type(morphology) not in (GaussianMorphology, SpergelMorphology):
+        raise NotImplementedError(
+            "{}: only GaussianMorphology and SpergelMorphology can be fitted; a profile function "
+            "of the user's has no gradient on the device".format(type(morphology).__name__))
+    if scheme != "amsgrad":
+        raise NotImplementedError("profile sources (Gaussian, Spergel) with another scheme than amsgrad")
+    spergel = type(morphology) is SpergelMorphology
+    params, step, rel, fixed = np.zeros(6), np.zeros(4), np.zeros(4), 0
+    slots = {"center": slice(0, 2), "radius": slice(2, 3), "ellipticity": slice(3, 5),
+             "nu": slice(5, 6)}
+    for g, name in enumerate(_PROFILE_GROUPS):
+        if name == "nu" and not spergel:
+            fixed |= 1 << g
+            continue
+        p = morphology.get_parameter(name)
+        if not isinstance(p, np.ndarray) or p.dtype != np.float64 or p.shape != params[slots[name]].shape:
+            raise NotImplementedError("profile parameter '{}' must be one float64 array of shape {}"
+                                      .format(name, params[slots[name]].shape))
+        if p.prior is not None:
+            raise NotImplementedError("a prior on the profile parameter '{}'".format(name))
+        own = p.constraint is None if name == "center" else (
+            type(p.constraint) is ProfileProx and p.constraint.kind == name)
+        if not own:
+            raise NotImplementedError(
+                "a user constraint on the profile parameter '{}': the device applies the "
+                "morphology's own proximal operators only".format(name))
+        params[slots[name]] = np.asarray(p)
+        if p.fixed:
+            fixed |= 1 << g
+            if p.step is None:
+                continue
+        rule = _step_rule(p.step, "profile")
+        if rule is None:
+            raise NotImplementedError(
+                "the step of the profile parameter '{}' must be a number, relative_step or a "
+                "partial of relative_step (got another callable)".format(name))
+        const, factor, minimum = rule
+        step[g], rel[g] = max(const, float(np.max(minimum))), factor
+    return dict(kind=_lib.PROFILE_SPERGEL if spergel else _lib.PROFILE_GAUSSIAN, params=params,
+                step=step, rel_step=rel, fixed=fixed)
+
+
+def _refuse_unfittable_profiles(sources, scheme):
+    """Raise for a profile source the device loop cannot run, before anything else of a fit."""
+    for src in sources:
+        if isinstance(src, FactorizedComponent):
+            if isinstance(src.children[1], ProfileMorphology):
+                _profile_rules(src.children[1], scheme)
+        elif isinstance(src, CombinedComponent):
+            _refuse_unfittable_profiles(src.children, scheme)
+
+
+def _profile_rows(comps, k, name):
+    """Row of six doubles of component ``k`` from the moment ``name`` of its profile
+    parameters (zeros where a parameter has none yet)."""
+    row = np.zeros(6)
+    morphology = comps[k].children[1]
+    for group, sl in (("center", slice(0, 2)), ("radius", slice(2, 3)),
+                      ("ellipticity", slice(3, 5)), ("nu", slice(5, 6))):
+        p = morphology.get_parameter(group)
+        value = None if p is None else getattr(p, name)
+        if value is not None:
+            row[sl] = np.asarray(value, dtype=np.float64).reshape(-1)
+    return row
 
 
 def _next_round(local, budget):
@@ -404,6 +481,9 @@ class Blend(CombinedComponent):
             if isinstance(morphology, StarletMorphology):
                 specs.append(self._starlet_spec(k, sed, image, morphology))
                 continue
+            if isinstance(morphology, ProfileMorphology):
+                specs.append(self._profile_spec(k, sed, morphology))
+                continue
             if isinstance(morphology, PointSourceMorphology):
                 if self._scheme_args()[0] != "amsgrad":
                     raise NotImplementedError("point sources with another scheme than amsgrad")
@@ -529,6 +609,27 @@ class Blend(CombinedComponent):
             prox_flags=(_lib.COMPONENT_FIXED_SED if sed.fixed or not sed_on_device else 0) | (
                 _lib.COMPONENT_FIXED_MORPH if coeffs.fixed else 0),
             starlet=(values, thresh), sed_floor=sed_floor)
+
+    def _profile_spec(self, k, sed, morphology):
+        """GaussianSource / SpergelSource -> device description: the profile kernels step the
+        four float64 parameters, the ordinary update kernel the spectrum (or, if its rules are
+        the user's, the host)."""
+        profile = _profile_rules(morphology, self._scheme_args()[0])
+        sed_rule = _rule(sed, "spectrum")
+        free_form = isinstance(sed.constraint, PositivityConstraint) and sed.constraint.zero == 1e-20
+        sed_on_device = not callable(sed_rule) and sed.prior is None and (
+            free_form or (sed.fixed and sed.constraint is None and np.all(np.asarray(sed) > 1e-20)))
+        if not sed_on_device:
+            self._host.append((k, HostParameter(sed, "sed", sed_rule, *self._scheme_args())))
+            sed_rule = (0.0, 0.0, 0.0)
+        s_const, s_rel, s_min = sed_rule
+        return ComponentSpec(
+            np.asarray(sed), np.zeros(morphology.bbox.shape[-2:], dtype=np.float32),
+            morphology.bbox.origin[-2:],
+            sed_min_step=np.maximum(np.asarray(s_min, dtype=np.float64), s_const),
+            sed_rel_step=s_rel, morph_step=0.0,
+            prox_flags=_lib.COMPONENT_FIXED_SED if sed.fixed or not sed_on_device else 0,
+            profile=profile)
 
     def _host_gradients(self, batch, comps):
         """(g_sed, g_morph, g_vec) at the parameters of this iteration for the parameters the
@@ -679,7 +780,8 @@ class Blend(CombinedComponent):
                for name in ("m", "v", "vhat")):
             # missing moments (fresh parameters) are zeros (blend.py:154-160); a point
             # source has no image on the device side: zeros of its box shape
-            star = set(batch._star)  # (their moments belong to the coefficients: below)
+            # (the moments of starlet coefficients and profile parameters are sent below)
+            star = set(batch._star) | set(batch._profile)
 
             def image_state(name):
                 return [np.zeros(batch._shapes[k]) if point[k] or k in star
@@ -695,6 +797,13 @@ class Blend(CombinedComponent):
         if any(getattr(p, name) is not None for p in coeffs for name in ("m", "v", "vhat")):
             batch.set_starlet_moments(*[[state(p, name, p.shape) for p in coeffs]
                                         for name in ("m", "v", "vhat")])
+        if batch._profile:
+            rows = {name: np.zeros((len(comps), 6)) for name in ("m", "v", "vhat")}
+            for k in batch._profile:
+                for name in rows:
+                    rows[name][k] = _profile_rows(comps, k, name)
+            if any(r.any() for r in rows.values()):
+                batch.set_profile_moments(rows["m"], rows["v"], rows["vhat"])
         vec = [None] * len(comps)  # the free 2-vector of a component, if it has one
         for k, c in enumerate(comps):
             if point[k]:
@@ -731,7 +840,8 @@ class Blend(CombinedComponent):
         shifted = (np.asarray(batch._flags) & _lib.COMPONENT_SHIFTING).astype(bool).tolist()
         star = dict(zip(batch._star, range(len(batch._star))))
         starlets = batch.starlet_state(dtype=np.float64) if star else None
-        if not any(shifted) and not star and \
+        profiles = batch.profile_state() if batch._profile else None
+        if not any(shifted) and not star and profiles is None and \
                 not any(isinstance(c._children[1], PointSourceMorphology) for c in comps):
             # images only (a thousand blends: ten thousand components): nothing but assignments
             for k, comp in enumerate(comps):
@@ -749,6 +859,16 @@ class Blend(CombinedComponent):
             image = morphology._parameters[0]
             sed[...] = seds[k]
             sed.m, sed.v, sed.vhat = m_sed[k], v_sed[k], vhat_sed[k]
+            if isinstance(morphology, ProfileMorphology):
+                # the parameters are the six doubles, not the image
+                for name, sl in (("center", slice(0, 2)), ("radius", slice(2, 3)),
+                                 ("ellipticity", slice(3, 5)), ("nu", slice(5, 6))):
+                    p = morphology.get_parameter(name)
+                    if p is None:
+                        continue
+                    p[...] = profiles["params"][k][sl]
+                    p.m, p.v, p.vhat = (profiles[n][k][sl].copy() for n in ("m", "v", "vhat"))
+                continue
             if isinstance(morphology, PointSourceMorphology):
                 if centers is None:
                     centers = batch.centers()
@@ -795,6 +915,7 @@ class Blend(CombinedComponent):
         # proxmin.adaprox steps every parameter on the host from the device's gradients
         self._scheme = (scheme, alg_kwargs.pop("p", 0.25))
         _refuse_unfittable_starlets(self.sources, scheme)
+        _refuse_unfittable_profiles(self.sources, scheme)
         prox_max_iter, opt = _adaprox_options(alg_kwargs)
         if any(type(obs.renderer) not in (NullRenderer, ConvolutionRenderer, ResolutionRenderer)
                for obs in self.observations):
@@ -910,6 +1031,13 @@ class Blend(CombinedComponent):
                     if hook:
                         self._download(batch, comps)
                         restart = _update_sources(self.sources)
+                        if not restart and getattr(batch, "_profile", None) and not self._host:
+                            # The device holds a point source's centre relative to its box, so
+                            # a centre that went over the host has lost the last bit.  fit_blends
+                            # opens a batch per round for these blends (_fit_group_rebuilt):
+                            # continue from the downloaded centres as it does, for equal bits.
+                            # Blends without profile components keep the batch untouched.
+                            batch.set_centers(batch.centers()["center"])
                     if active == 0 and not restart:
                         break
                     if callback is not None and not restart:

@@ -232,6 +232,11 @@ struct smi_batch {
     float *st_thresh = nullptr, *st_coeffs = nullptr, *st_mom[3] = {nullptr, nullptr, nullptr},
           *st_grad = nullptr, *st_work = nullptr;
     int64_t n_star_coeffs = 0;
+    // profile components (profile_source.hip): the view and the arrays it points into
+    smi::ProfileView prof{};
+    int32_t *pf_comp = nullptr, *pf_kind = nullptr, *pf_fixed = nullptr;
+    double *pf_step = nullptr, *pf_rel = nullptr, *pf_par = nullptr, *pf_grad = nullptr,
+           *pf_mom[3] = {nullptr, nullptr, nullptr};
     std::vector<int64_t> h_moff;
     std::vector<int32_t> h_blend;  // owning blend of every component
     // scarlet.lite
@@ -915,7 +920,9 @@ int smi_batch_destroy(smi_batch *b) {
                     b->c_fista_step, b->fista_t, b->have_prev, b->scratch, b->state, b->zero_state, b->n_loss, b->status_out, b->it_base, b->frame_hw, b->pause_at, b->conv_flag, b->shift_scratch,
                     b->loss_hist, b->last_loss, b->loss_partial, b->d_plans, b->work_items,
                     b->c_sed_floor, b->st_comp, b->st_planes, b->st_fixed, b->st_toff, b->st_coff, b->st_thresh,
-                    b->st_coeffs, b->st_mom[0], b->st_mom[1], b->st_mom[2], b->st_grad, b->st_work};
+                    b->st_coeffs, b->st_mom[0], b->st_mom[1], b->st_mom[2], b->st_grad, b->st_work,
+                    b->pf_comp, b->pf_kind, b->pf_fixed, b->pf_step, b->pf_rel, b->pf_par, b->pf_grad,
+                    b->pf_mom[0], b->pf_mom[1], b->pf_mom[2]};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     for (auto e : b->events) (void)hipEventDestroy(e);
@@ -1570,7 +1577,7 @@ static int set_components_impl(smi_batch *b, const smi_components *c, const int3
     } free_old{old_px};
     std::vector<int32_t> start(nb + 1, 0);
     std::vector<int64_t> moff(n + 1, 0);
-    int max_pix = 1, prev = 0, n_star = 0;
+    int max_pix = 1, prev = 0, n_star = 0, n_prof = 0;
     for (int k = 0; k < n; ++k) {
         SMI_REQUIRE(c->blend[k] >= prev && c->blend[k] < nb, "components must be grouped by blend");
         SMI_REQUIRE(c->box_h[k] > 0 && c->box_w[k] > 0, "empty component box");
@@ -1617,10 +1624,25 @@ static int set_components_impl(smi_batch *b, const smi_components *c, const int3
                         "starlet component box too large");
             ++n_star;
         }
+        if (c->prox_flags[k] & SMI_COMPONENT_PROFILE) {
+            SMI_REQUIRE(!keep, "smi_batch_update_components: profile components are not supported");
+            SMI_REQUIRE(c->prof_kind && c->prof_params && c->prof_step && c->prof_rel_step && c->prof_fixed,
+                        "profile component without prof_kind / prof_params / prof_step / prof_rel_step / prof_fixed");
+            SMI_REQUIRE(!(c->prox_flags[k] & ~(SMI_COMPONENT_PROFILE | SMI_COMPONENT_FIXED_SED)),
+                        "a profile component takes no other flag than SMI_COMPONENT_FIXED_SED");
+            SMI_REQUIRE(b->scheme == SMI_SCHEME_AMSGRAD, "profile components with SMI_SCHEME_FISTA");
+            SMI_REQUIRE(!b->frame_hw, "frame extents: profile components are not supported");
+            SMI_REQUIRE(c->prof_kind[k] == SMI_PROFILE_GAUSSIAN || c->prof_kind[k] == SMI_PROFILE_SPERGEL,
+                        "unknown profile kind");
+            SMI_REQUIRE(c->box_h[k] <= 4096 && c->box_w[k] <= 4096, "profile component box too large");
+            ++n_prof;
+        }
         SMI_REQUIRE(C <= 64, "more than 64 bands");
     }
     SMI_REQUIRE(!keep || b->star.n_star == 0,
                 "smi_batch_update_components: starlet components are not supported");
+    SMI_REQUIRE(!keep || b->prof.n_prof == 0,
+                "smi_batch_update_components: profile components are not supported");
     for (int i = 0; i < nb; ++i) start[i + 1] += start[i];
     b->h_comp_start = start;
     b->lite_flags = false;
@@ -1652,11 +1674,12 @@ static int set_components_impl(smi_batch *b, const smi_components *c, const int3
     UP(c_ox, c->origin_x, n);
     UP(c_h, c->box_h, n);
     UP(c_w, c->box_w, n);
-    // the ordinary update kernel steps the spectrum of a starlet component; the image in its
+    // the ordinary update kernel steps the spectrum of a starlet or profile component; the image in its
     // `morph` slot is derived: held fixed there, without constraint
     std::vector<int32_t> dev_flags(c->prox_flags, c->prox_flags + n);
     for (int k = 0; k < n; ++k)
-        if (dev_flags[k] & SMI_COMPONENT_STARLET) dev_flags[k] |= SMI_COMPONENT_FIXED_MORPH;
+        if (dev_flags[k] & (SMI_COMPONENT_STARLET | SMI_COMPONENT_PROFILE))
+            dev_flags[k] |= SMI_COMPONENT_FIXED_MORPH;
     UP(c_flags, dev_flags.data(), n);
     UP(c_plan, c->sweep_plan ? c->sweep_plan : noplan.data(), n);
     UP(c_moff, moff.data(), n + 1);
@@ -1913,6 +1936,50 @@ static int set_components_impl(smi_batch *b, const smi_components *c, const int3
             b->star.work = b->st_work;
         }
     }
+    // profile components: six doubles of parameters, moments and gradient each
+    {
+        std::vector<int32_t> comp, kind, fixed;
+        std::vector<double> step, rel, par;
+        for (int k = 0; k < n; ++k) {
+            if (!(c->prox_flags[k] & SMI_COMPONENT_PROFILE)) continue;
+            comp.push_back(k);
+            kind.push_back(c->prof_kind[k]);
+            fixed.push_back(c->prof_fixed[k]);
+            step.insert(step.end(), c->prof_step + 4 * (size_t)k, c->prof_step + 4 * (size_t)k + 4);
+            rel.insert(rel.end(), c->prof_rel_step + 4 * (size_t)k, c->prof_rel_step + 4 * (size_t)k + 4);
+            par.insert(par.end(), c->prof_params + 6 * (size_t)k, c->prof_params + 6 * (size_t)k + 6);
+        }
+        for (double **p : {&b->pf_grad, &b->pf_mom[0], &b->pf_mom[1], &b->pf_mom[2]})
+            if (*p) {
+                SMI_HIP(hipFree(*p));
+                *p = nullptr;
+            }
+        b->prof = smi::ProfileView{};
+        if (n_prof) {
+            const size_t nd = 6 * (size_t)n_prof;
+            if ((rc = upload(&b->pf_comp, comp.data(), comp.size()))) return rc;
+            if ((rc = upload(&b->pf_kind, kind.data(), kind.size()))) return rc;
+            if ((rc = upload(&b->pf_fixed, fixed.data(), fixed.size()))) return rc;
+            if ((rc = upload(&b->pf_step, step.data(), step.size()))) return rc;
+            if ((rc = upload(&b->pf_rel, rel.data(), rel.size()))) return rc;
+            if ((rc = upload(&b->pf_par, par.data(), par.size()))) return rc;
+            for (double **p : {&b->pf_grad, &b->pf_mom[0], &b->pf_mom[1], &b->pf_mom[2]}) {
+                SMI_HIP(dev_alloc(p, nd));
+                SMI_HIP(hipMemset(*p, 0, nd * sizeof(double)));
+            }
+            b->prof.n_prof = n_prof;
+            b->prof.comp = b->pf_comp;
+            b->prof.kind = b->pf_kind;
+            b->prof.fixed = b->pf_fixed;
+            b->prof.step = b->pf_step;
+            b->prof.rel = b->pf_rel;
+            b->prof.par = b->pf_par;
+            b->prof.m = b->pf_mom[0];
+            b->prof.v = b->pf_mom[1];
+            b->prof.vh = b->pf_mom[2];
+            b->prof.grad = b->pf_grad;
+        }
+    }
     b->have_components = true;
     const int max_pixels = b->view.max_box_pixels;
     refresh_view(b);
@@ -1947,6 +2014,7 @@ static int set_components_impl(smi_batch *b, const smi_components *c, const int3
     if ((rc = launch_point_sources(v, nullptr, 0, 0.f, 0, nullptr, nullptr, 2, b->stream))) return rc;
     if ((rc = launch_shift_forward(v, 0, b->stream))) return rc;
     if ((rc = launch_starlet_forward(v, b->star, 0, b->stream))) return rc;
+    if ((rc = launch_profile_forward(v, b->prof, 0, b->stream))) return rc;
     SMI_HIP(hipStreamSynchronize(b->stream));
     SMI_HIP(hipGetLastError());
     return SMI_OK;
@@ -1985,7 +2053,7 @@ int smi_batch_get_component_states(smi_batch *b, const int32_t *components, int3
                                    float *states) {
     SMI_REQUIRE(b && b->have_components && (n_sel == 0 || (components && states)),
                 "components not set / null argument");
-    SMI_REQUIRE(b->n_point == 0 && b->n_shift == 0 && b->star.n_star == 0,
+    SMI_REQUIRE(b->n_point == 0 && b->n_shift == 0 && b->star.n_star == 0 && b->prof.n_prof == 0,
                 "state records: factorized image components only");
     if (n_sel == 0) return SMI_OK;
     SMI_HIP(hipSetDevice(b->device));
@@ -2018,6 +2086,8 @@ int smi_batch_set_iteration_base(smi_batch *b, const int32_t *base) {
                 "smi_batch_set_iteration_base: factorized image components under AMSGrad only");
     SMI_REQUIRE(!base || b->star.n_star == 0,
                 "smi_batch_set_iteration_base: starlet components are not supported");
+    SMI_REQUIRE(!base || b->prof.n_prof == 0,
+                "smi_batch_set_iteration_base: profile components are not supported");
     SMI_HIP(hipSetDevice(b->device));
     SMI_HIP(hipStreamSynchronize(b->stream));
     if (!base) {
@@ -2046,6 +2116,7 @@ int smi_batch_set_frame_extents(smi_batch *b, const int32_t *h, const int32_t *w
                 "frame extents: point sources and shifting components are not supported");
     SMI_REQUIRE(!b->ks.stamp, "frame extents: a shifting difference kernel is not supported");
     SMI_REQUIRE(b->star.n_star == 0, "frame extents: starlet components are not supported");
+    SMI_REQUIRE(b->prof.n_prof == 0, "frame extents: profile components are not supported");
     SMI_REQUIRE(b->lowres.empty() && b->layers.empty(),
                 "frame extents: further observations are not supported");
     const int nb = b->d.n_blends;
@@ -2305,12 +2376,82 @@ int smi_batch_set_parameters(smi_batch *b, const float *sed, const float *morph)
             if (rc) return rc;
             SMI_HIP(hipStreamSynchronize(b->stream));
         }
+        if (b->prof.n_prof) {  // the image of a profile component is derived from its parameters
+            int rc = launch_profile_forward(unmasked_view(b), b->prof, 0, b->stream);
+            if (rc) return rc;
+            SMI_HIP(hipStreamSynchronize(b->stream));
+        }
         if (b->star.n_star) {  // the image of a starlet component is derived from its coefficients
             int rc = launch_starlet_forward(unmasked_view(b), b->star, 0, b->stream);
             if (rc) return rc;
             SMI_HIP(hipStreamSynchronize(b->stream));
         }
     }
+    return SMI_OK;
+}
+
+int smi_batch_get_profiles(smi_batch *b, double *params, double *m, double *v, double *vhat,
+                           double *gradient) {
+    SMI_REQUIRE(b && b->have_components, "components not set");
+    SMI_HIP(hipSetDevice(b->device));
+    SMI_HIP(hipStreamSynchronize(b->stream));
+    const int n = b->d.n_components, np_ = b->prof.n_prof;
+    if (!np_) return SMI_OK;
+    std::vector<int32_t> comp(np_);
+    SMI_HIP(hipMemcpy(comp.data(), b->pf_comp, np_ * sizeof(int32_t), hipMemcpyDeviceToHost));
+    std::vector<double> packed(6 * (size_t)np_);
+    double *dst[5] = {params, m, v, vhat, gradient};
+    const double *src[5] = {b->pf_par, b->pf_mom[0], b->pf_mom[1], b->pf_mom[2], b->pf_grad};
+    for (int i = 0; i < 5; ++i) {
+        if (!dst[i]) continue;
+        SMI_HIP(hipMemcpy(packed.data(), src[i], packed.size() * sizeof(double), hipMemcpyDeviceToHost));
+        std::fill(dst[i], dst[i] + 6 * (size_t)n, 0.0);
+        for (int s = 0; s < np_; ++s)
+            std::copy(packed.begin() + 6 * s, packed.begin() + 6 * s + 6, dst[i] + 6 * (size_t)comp[s]);
+    }
+    return SMI_OK;
+}
+
+int smi_batch_set_profile_moments(smi_batch *b, const double *m, const double *v, const double *vhat) {
+    SMI_REQUIRE(b && b->have_components, "components not set");
+    SMI_HIP(hipSetDevice(b->device));
+    SMI_HIP(hipStreamSynchronize(b->stream));  // pending steps may still read the old arrays
+    const int np_ = b->prof.n_prof;
+    if (!np_) return SMI_OK;
+    std::vector<int32_t> comp(np_);
+    SMI_HIP(hipMemcpy(comp.data(), b->pf_comp, np_ * sizeof(int32_t), hipMemcpyDeviceToHost));
+    std::vector<double> packed(6 * (size_t)np_);
+    const double *src[3] = {m, v, vhat};
+    for (int i = 0; i < 3; ++i) {
+        if (!src[i]) {
+            SMI_HIP(hipMemset(b->pf_mom[i], 0, packed.size() * sizeof(double)));
+            continue;
+        }
+        for (int s = 0; s < np_; ++s)
+            std::copy(src[i] + 6 * (size_t)comp[s], src[i] + 6 * (size_t)comp[s] + 6, packed.begin() + 6 * s);
+        SMI_HIP(hipMemcpy(b->pf_mom[i], packed.data(), packed.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    return SMI_OK;
+}
+
+int smi_profile_probe(int device, int32_t kind, const double *params, int32_t h, int32_t w,
+                      int32_t origin_y, int32_t origin_x, double *out) {
+    SMI_REQUIRE(params && out && h > 0 && w > 0 && h <= 4096 && w <= 4096, "smi_profile_probe: bad argument");
+    SMI_REQUIRE(kind == SMI_PROFILE_GAUSSIAN || kind == SMI_PROFILE_SPERGEL, "unknown profile kind");
+    SMI_HIP(hipSetDevice(device));
+    const size_t n_out = 7 * (size_t)h * w;
+    double *d_par = nullptr, *d_out = nullptr;
+    SMI_HIP(hipMalloc(&d_par, 6 * sizeof(double)));
+    hipError_t err = hipMalloc(&d_out, n_out * sizeof(double));
+    if (err == hipSuccess) err = hipMemcpy(d_par, params, 6 * sizeof(double), hipMemcpyHostToDevice);
+    if (err == hipSuccess) {
+        smi::launch_profile_probe(kind, d_par, h, w, origin_y, origin_x, d_out, nullptr);
+        err = hipDeviceSynchronize();
+    }
+    if (err == hipSuccess) err = hipMemcpy(out, d_out, n_out * sizeof(double), hipMemcpyDeviceToHost);
+    (void)hipFree(d_par);
+    if (d_out) (void)hipFree(d_out);
+    SMI_HIP(err);
     return SMI_OK;
 }
 
@@ -2454,6 +2595,7 @@ int smi_batch_gradient(smi_batch *b, float *g_sed, float *g_morph) {
         return rc;
     if ((rc = launch_shift_backward(v, b->Q, 0, b->g_center, 1, b->stream))) return rc;
     if ((rc = launch_starlet_step(v, b->star, b->Q, 0, 0.f, 0, 1, b->stream))) return rc;
+    if ((rc = launch_profile_step(v, b->prof, b->Q, 0, 0.f, 0, 1, b->stream))) return rc;
     SMI_HIP(hipStreamSynchronize(b->stream));
     if (g_sed)
         SMI_HIP(hipMemcpy(g_sed, b->g_sed, (size_t)v.n_comp * v.C * sizeof(float),
@@ -2467,7 +2609,7 @@ int smi_batch_gradient(smi_batch *b, float *g_sed, float *g_morph) {
 
 // nothing but factorized components under one fused convolution
 static bool plain_batch(const smi_batch *b) {
-    return b->fused && b->n_point == 0 && b->n_shift == 0 && b->star.n_star == 0 &&
+    return b->fused && b->n_point == 0 && b->n_shift == 0 && b->star.n_star == 0 && b->prof.n_prof == 0 &&
            b->lowres.empty() && b->layers.empty() && !b->ks.stamp;
 }
 
@@ -2483,7 +2625,7 @@ static bool inline_render(const smi_batch *b) {
     // the convolution runs; further observations, a low-resolution term and a free kernel shift
     // read the cube)
     return allowed && b->inline_render && b->fused && b->lowres.empty() && b->layers.empty() &&
-           !b->ks.stamp && b->star.n_star == 0 && b->view.render_slots > 0;
+           !b->ks.stamp && b->star.n_star == 0 && b->prof.n_prof == 0 && b->view.render_slots > 0;
 }
 
 
@@ -2675,6 +2817,8 @@ int smi_batch_step(smi_batch *b, int32_t it0, int32_t n_iter, float e_rel, int32
         // (before the spectra move: the coefficient gradient belongs to this iteration's spectrum)
         if ((rc = launch_starlet_step(v, b->star, b->Q, it, e_rel, prox_max_iter, 0, b->stream)))
             return rc;
+        if ((rc = launch_profile_step(v, b->prof, b->Q, it, e_rel, prox_max_iter, 0, b->stream)))
+            return rc;
         if (plain) {  // (the loss bookkeeping rides along with the updates)
             if ((rc = launch_update_finalize(v, b->Q, it, e_rel, min_iter, check, prox_max_iter,
                                              b->stream)))
@@ -2688,6 +2832,7 @@ int smi_batch_step(smi_batch *b, int32_t it0, int32_t n_iter, float e_rel, int32
             return rc;
         if ((rc = launch_shift_forward(v, 1, b->stream))) return rc;
         if ((rc = launch_starlet_forward(v, b->star, 1, b->stream))) return rc;
+        if ((rc = launch_profile_forward(v, b->prof, 1, b->stream))) return rc;
         if (b->ks.stamp && (rc = refresh_shifted_kernel(b, 1))) return rc;
         if (check) launch_advance(v, b->stream);
         if (ev) SMI_HIP(hipEventRecord(ev[5], b->stream));
@@ -2816,6 +2961,7 @@ void mutable_state(smi_batch *b, void **ptr, size_t *bytes) {
 int smi_batch_save_state(smi_batch *b) {
     SMI_REQUIRE(b && b->have_components, "components not set");
     SMI_REQUIRE(b->star.n_star == 0, "smi_batch_save_state: starlet components are not supported");
+    SMI_REQUIRE(b->prof.n_prof == 0, "smi_batch_save_state: profile components are not supported");
     SMI_HIP(hipSetDevice(b->device));
     void *ptr[12];
     size_t bytes[12];
@@ -2836,6 +2982,7 @@ int smi_batch_save_state(smi_batch *b) {
 int smi_batch_restore_state(smi_batch *b) {
     SMI_REQUIRE(b && b->have_components, "components not set");
     SMI_REQUIRE(b->star.n_star == 0, "smi_batch_restore_state: starlet components are not supported");
+    SMI_REQUIRE(b->prof.n_prof == 0, "smi_batch_restore_state: profile components are not supported");
     SMI_HIP(hipSetDevice(b->device));
     void *ptr[12];
     size_t bytes[12];

@@ -379,6 +379,32 @@ int launch_starlet_step(const BatchView &v, const StarletView &sv, const float *
 int launch_starlet_forward(const BatchView &v, const StarletView &sv, int32_t respect_state,
                            hipStream_t s);
 
+// Profile components (profile_source.hip; SMI_COMPONENT_PROFILE): the morphology is a Gaussian or
+// Spergel radial profile of six doubles {centre y, x, radius, e1, e2, nu} (nu unused by a
+// Gaussian), kept with their AMSGrad moments in arrays of their own, component comp[s] at
+// 6 s; the component's `morph` slot holds the float32 image the model uses.  Four parameters --
+// centre, radius, ellipticity, nu -- each with a constant step, a relative_step factor (0: the
+// constant one) and a bit of the fixed mask.
+struct ProfileView {
+    int32_t n_prof = 0;
+    const int32_t *comp = nullptr;
+    const int32_t *kind = nullptr;   // 0 Gaussian, 1 Spergel
+    const int32_t *fixed = nullptr;  // bit g: Parameter(fixed=True) of group g
+    const double *step = nullptr, *rel = nullptr;  // [n_prof][4]
+    double *par = nullptr, *m = nullptr, *v = nullptr, *vh = nullptr;  // [n_prof][6]
+    double *grad = nullptr;  // [n_prof][6]: d(-logL) / d parameter of the last evaluation
+};
+// the six gradient sums; unless grad_only also the AMSGrad / proximal update of every parameter
+// (of blends that are still iterating)
+int launch_profile_step(const BatchView &v, const ProfileView &pv, const float *G, int32_t it,
+                        float e_rel, int32_t prox_max_iter, int32_t grad_only, hipStream_t s);
+// parameters -> the `morph` slots
+int launch_profile_forward(const BatchView &v, const ProfileView &pv, int32_t respect_state,
+                           hipStream_t s);
+// value and the six partials of one profile over a box: out[7][h][w] (device pointers)
+void launch_profile_probe(int32_t kind, const double *par, int32_t h, int32_t w, int32_t oy,
+                          int32_t ox, double *out, hipStream_t s);
+
 // ConvolutionRenderer(psf_shift=...) (renderer.py:175-177, 215-228): the difference kernel
 // carries a free sub-pixel Fourier shift, one per kernel set (the batch's kernel, or one
 // per blend), shared by the bands of the set

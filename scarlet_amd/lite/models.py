@@ -206,10 +206,24 @@ class LiteFactorizedComponent(LiteComponent):
             "scarlet_amd updates lite components on the GPU inside LiteBlend.fit")
 
 
+def _refuse_profile_sources(items):
+    """GaussianSource / SpergelSource are models of the main package: the reference's lite
+    package has no parametric profiles, and neither has this one."""
+    from ..component import FactorizedComponent
+    from ..morphology import ProfileMorphology
+
+    for item in items:
+        if isinstance(item, FactorizedComponent) and isinstance(item.children[1], ProfileMorphology):
+            raise NotImplementedError(
+                "{} in scarlet_amd.lite: profile sources (Gaussian, Spergel) are fitted by "
+                "scarlet_amd.Blend only".format(type(item).__name__))
+
+
 class LiteSource:
     """Components of one astrophysical object (lite/models.py:266-331)."""
 
     def __init__(self, components, dtype):
+        _refuse_profile_sources(components)
         self.components = components
         self.dtype = dtype
         self.flux = None
@@ -310,6 +324,7 @@ class LiteBlend:
     """Sources + observation, fitted jointly (lite/models.py:479-624)."""
 
     def __init__(self, sources, observation):
+        _refuse_profile_sources(sources)
         self.sources = sources
         self.components = [c for src in sources for c in src.components]
         self.observation = observation

@@ -1,6 +1,5 @@
-"""Image and starlet morphologies of factorized components (reference
-scarlet/morphology.py:26-207, 476-604, 607-688).  Parametric profiles (Gaussian,
-Spergel) are outside the scope of this package."""
+"""Image, starlet and profile (Gaussian, Spergel) morphologies of factorized components
+(reference scarlet/morphology.py:26-688)."""
 
 import numpy as np
 import numpy.ma as ma
@@ -8,6 +7,7 @@ import numpy.ma as ma
 from .bbox import Box, overlapped_slices
 from .constraint import (
     CenterOnConstraint,
+    Constraint,
     ConstraintChain,
     L0Constraint,
     MonotonicMaskConstraint,
@@ -351,3 +351,162 @@ class StarletMorphology(Morphology):
                            m=sliced(coeffs.m), v=sliced(coeffs.v), vhat=sliced(coeffs.vhat))
         self._parameters = (shrunk,) + self._parameters[1:]
         raise UpdateException
+
+
+class ProfileProx(Constraint):
+    """The proximal operator a ``ProfileMorphology`` puts on one of its parameters
+    (morphology.py:319-326, 472-473); ``kind`` names it, so that ``Blend.fit`` can tell the
+    stock rule -- which the device applies -- from a user's."""
+
+    def __init__(self, kind, f):
+        super().__init__(f)
+        self.kind = kind
+
+
+class ProfileMorphology(Morphology):
+    """Morphology from a radial profile ``func(R2, *parameters)`` of the squared elliptical
+    radius in units of the parameter "radius", about the parameter "center", sheared by the
+    parameter "ellipticity" (morphology.py:210-326).  The model is evaluated on the integer
+    pixel grid of the box in float64 and is not normalised.
+
+    The box is square: ``boxsize`` a side at construction, afterwards -- ``update()``, every
+    10 iterations of a fit -- the smallest standard size that holds ten radii, around the
+    pixel nearest to the centre.  It may overhang the frame.
+
+    ``Blend.fit`` runs ``GaussianMorphology`` and ``SpergelMorphology``; a subclass with a
+    profile function of its own has no gradient there and is refused."""
+
+    def __init__(self, frame, func, *parameters, boxsize=None, resize=True):
+        self.f = func
+        self.center = self.get_parameter("center", *parameters)
+        bbox = self.get_box(*parameters, boxsize=boxsize)
+        self.resizing = resize
+        self._set_grid(bbox)
+        self.get_parameter("radius", *parameters).constraint = ProfileProx("radius", self._radius_prox)
+        self.get_parameter("ellipticity", *parameters).constraint = ProfileProx(
+            "ellipticity", self._eps_prox)
+        super().__init__(frame, *parameters, bbox=bbox)
+
+    def _set_grid(self, bbox):
+        self._Y = np.arange(bbox.shape[-2], dtype="float") + bbox.origin[-2]
+        self._X = np.arange(bbox.shape[-1], dtype="float") + bbox.origin[-1]
+
+    def elliptical_radius2(self, *parameters):
+        """``R2`` of every pixel of the box: squared sheared distance over radius squared."""
+        center = self.get_parameter("center", *parameters)
+        y = (self._Y - center[-2])[:, None]
+        x = (self._X - center[-1])[None, :]
+        e1, e2 = self.get_parameter("ellipticity", *parameters)
+        shear = np.sqrt(1 - (e1 ** 2 + e2 ** 2))
+        xs = ((1 - e1) * x - e2 * y) / shear
+        ys = (-e2 * x + (1 + e1) * y) / shear
+        R2 = ys ** 2 + xs ** 2
+        radius = self.get_parameter("radius", *parameters)
+        return R2 / radius ** 2
+
+    def get_model(self, *parameters):
+        return self.f(self.elliptical_radius2(*parameters), *parameters)
+
+    def update(self):
+        """Move the box to ``get_box()`` if that differs (morphology.py:288-300); parameters
+        and their moments keep their shapes."""
+        if not self.resizing:
+            return
+        bbox = self.get_box()
+        if bbox != self.bbox:
+            self.bbox.origin = bbox.origin
+            self.bbox.shape = bbox.shape
+            self._set_grid(bbox)
+            raise UpdateException
+
+    def get_box(self, *parameters, boxsize=None):
+        if boxsize is None:
+            radius = np.asarray(self.get_parameter("radius", *parameters), dtype=float)
+            boxsize = get_minimal_boxsize(10 * float(radius.reshape(-1)[0]))
+        center = self.get_parameter("center", *parameters)
+        assert center is not None and len(center) >= 2
+        origin = (int(round(center[-2])) - (boxsize // 2), int(round(center[-1])) - (boxsize // 2))
+        return Box((boxsize, boxsize), origin=origin)
+
+    @staticmethod
+    def _radius_prox(x, step):
+        return np.maximum(x, 1e-2)
+
+    @staticmethod
+    def _eps_prox(x, step):
+        norm2 = (x ** 2).sum()
+        if norm2 > 1:
+            x /= np.sqrt(norm2) * 1.1  # back inside the unit circle
+        return x
+
+
+def _first_side(radius):
+    """``ceil(10 radius)`` of a number or a one-element array, as a plain int."""
+    return int(np.ceil(10 * float(np.asarray(radius, dtype=float).reshape(-1)[0])))
+
+
+class GaussianMorphology(ProfileMorphology):
+    """``exp(-R2 / 2)``: an elliptical Gaussian of standard deviation ``sigma`` pixels
+    (morphology.py:329-369).  Plain numbers become fixed parameters; pass ``Parameter``s named
+    "center", "radius" and "ellipticity" for what is to be fitted."""
+
+    def __init__(self, frame, center, sigma, ellipticity=(0, 0), boxsize=None):
+        assert len(center) == 2
+        self.center = prepare_param(center, name="center")
+        radius = prepare_param(sigma, name="radius")
+        assert len(ellipticity) == 2
+        ellipticity = prepare_param(ellipticity, name="ellipticity")
+        if boxsize is None:
+            boxsize = _first_side(sigma)
+        super().__init__(frame, self._f, self.center, radius, ellipticity, boxsize=boxsize)
+
+    def _f(self, R2, *parameters):
+        return np.exp(-R2 / 2)
+
+    @property
+    def integral(self):
+        return 2 * np.pi * self.get_parameter("radius") ** 2
+
+
+class SpergelMorphology(ProfileMorphology):
+    """The profile of Spergel (2010), ``f_nu(c_nu sqrt(R2 + 1e-4))`` with ``f_nu(u) = (u / 2)^nu
+    K_nu(u) / Gamma(nu + 1)``, half-light radius ``rhalf`` pixels and ``nu`` kept within
+    [-0.85, 4] (morphology.py:384-473).  ``c_nu`` is the reference's stored quartic fit."""
+
+    _minimum_nu, _maximum_nu = -0.85, 4.00
+    _z = np.array([-0.00788962, 0.0735303, -0.27770785, 0.99483285, 1.25227402])
+
+    def __init__(self, frame, center, nu, rhalf, ellipticity=(0, 0), boxsize=None):
+        assert len(center) == 2
+        self.center = prepare_param(center, name="center")
+        nu = prepare_param(nu, name="nu")
+        assert self._minimum_nu <= nu[0] <= self._maximum_nu
+        nu.constraint = ProfileProx("nu", self._nu_prox)
+        radius = prepare_param(rhalf, name="radius")
+        assert len(ellipticity) == 2
+        ellipticity = prepare_param(ellipticity, name="ellipticity")
+        if boxsize is None:
+            boxsize = _first_side(rhalf)
+        super().__init__(frame, self._f, self.center, nu, radius, ellipticity, boxsize=boxsize)
+
+    def _f(self, R2, *parameters):
+        nu = self.get_parameter("nu", *parameters)
+        return self._f_nu(np.sqrt(R2 + 1e-4) * self._cnu(nu), nu)
+
+    @property
+    def integral(self):
+        cnu = self._cnu(self.get_parameter("nu"))
+        return 2 * np.pi * self.get_parameter("radius") ** 2 / cnu ** 2
+
+    @staticmethod
+    def _f_nu(x, nu):
+        from scipy.special import gamma, kv
+
+        return (x / 2) ** nu * kv(nu, x) / gamma(nu + 1)
+
+    def _cnu(self, nu):
+        z = self._z
+        return z[0] * nu ** 4 + z[1] * nu ** 3 + z[2] * nu ** 2 + z[3] * nu + z[4]
+
+    def _nu_prox(self, x, step):
+        return np.maximum(np.minimum(self._maximum_nu, x), self._minimum_nu)

@@ -1,8 +1,8 @@
 """Extended-source models (reference scarlet/source.py:249-522, 615-807):
 ``ExtendedSource`` factory -> ``SingleExtendedSource`` / ``MultiExtendedSource`` /
 ``CompactExtendedSource``, ``PointSource`` (source.py:92-128), ``RandomSource``
-(source.py:61-89) and ``StarletSource`` (source.py:525-612).  Gaussian and Spergel sources
-are outside the scope of this package."""
+(source.py:61-89), ``StarletSource`` (source.py:525-612), ``GaussianSource`` and
+``SpergelSource`` (source.py:131-246)."""
 
 import logging
 from functools import partial
@@ -14,8 +14,8 @@ from . import operator
 from .bbox import Box, overlapped_slices
 from .component import CombinedComponent, FactorizedComponent
 from .constraint import CenterOnConstraint, PositivityConstraint
-from .morphology import (ExtendedSourceMorphology, ImageMorphology, PointSourceMorphology,
-                         StarletMorphology)
+from .morphology import (ExtendedSourceMorphology, GaussianMorphology, ImageMorphology,
+                         PointSourceMorphology, SpergelMorphology, StarletMorphology)
 from .parameter import Parameter, relative_step
 from .spectrum import TabulatedSpectrum
 
@@ -79,6 +79,69 @@ class PointSource(FactorizedComponent):
             TabulatedSpectrum(model_frame, amplitudes, min_step=_noise_rms(observations)),
             morphology)
         self.center = morphology.center
+
+
+def _ellipticity_parameter(ellipticity):
+    """The free "ellipticity" of a profile source.  Like the reference, only an ndarray is
+    taken; ``None`` and a tuple -- a ``TypeError`` and an ``AttributeError`` from deep inside
+    the reference -- are named here."""
+    if ellipticity is None:
+        raise TypeError("ellipticity=None: pass the two components (e1, e2) as an ndarray, "
+                        "np.zeros(2) for a round source")
+    if not isinstance(ellipticity, np.ndarray):
+        raise TypeError("ellipticity must be an ndarray of two floats, got {}".format(
+            type(ellipticity).__name__))
+    if ellipticity.shape != (2,):
+        raise ValueError("ellipticity must have shape (2,), got {}".format(ellipticity.shape))
+    return Parameter(ellipticity, name="ellipticity", step=0.01)
+
+
+class _ProfileSource(FactorizedComponent):
+    """What ``GaussianSource`` and ``SpergelSource`` share: the spectrum of the pixel under
+    the centre, not corrected for the PSF, over the peak value of the (unnormalised) profile,
+    with the noise level scaled alike as smallest step (source.py:166-185, 227-246)."""
+
+    def _finish(self, model_frame, sky_coord, observations, morphology):
+        peak = morphology.f(0)
+        amplitudes = init.get_pixel_spectrum(sky_coord, observations, correct_psf=False)
+        amplitudes /= peak
+        noise = _noise_rms(observations)
+        noise /= peak
+        super().__init__(model_frame, TabulatedSpectrum(model_frame, amplitudes, min_step=noise),
+                         morphology)
+        self.center = morphology.center
+
+
+class GaussianSource(_ProfileSource):
+    """An elliptical Gaussian of standard deviation ``sigma`` pixels at ``sky_coord``; centre
+    (step 0.01), sigma (a tenth of itself) and ``ellipticity`` (an ndarray (e1, e2), step
+    0.01) are fitted in float64."""
+
+    def __init__(self, model_frame, sky_coord, sigma, ellipticity, observations):
+        observations = _as_sequence(observations)
+        center = Parameter(np.array(model_frame.get_pixel(sky_coord), dtype=float),
+                           name="center", step=0.01)
+        radius = Parameter(np.array((sigma,), dtype=float), name="radius", step=relative_step)
+        morphology = GaussianMorphology(model_frame, center, radius,
+                                        ellipticity=_ellipticity_parameter(ellipticity))
+        self._finish(model_frame, sky_coord, observations, morphology)
+
+
+class SpergelSource(_ProfileSource):
+    """A Spergel (2010) profile of index ``nu`` and half-light radius ``rhalf`` pixels at
+    ``sky_coord``; centre, nu and ``ellipticity`` move in steps of 0.01, the radius in steps
+    of a hundredth of itself."""
+
+    def __init__(self, model_frame, sky_coord, nu, rhalf, ellipticity, observations):
+        observations = _as_sequence(observations)
+        center = Parameter(np.array(model_frame.get_pixel(sky_coord), dtype=float),
+                           name="center", step=0.01)
+        nu = Parameter(np.array((nu,), dtype=float), name="nu", step=0.01)
+        radius = Parameter(np.array((rhalf,), dtype=float), name="radius",
+                           step=partial(relative_step, factor=0.01))
+        morphology = SpergelMorphology(model_frame, center, nu, radius,
+                                       ellipticity=_ellipticity_parameter(ellipticity))
+        self._finish(model_frame, sky_coord, observations, morphology)
 
 
 class CompactExtendedSource(FactorizedComponent):
