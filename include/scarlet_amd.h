@@ -169,7 +169,8 @@ enum {
      * (StarletSource, source.py:525-612; StarletMorphology, morphology.py:516-604): see the
      * star_* fields of smi_components.  SMI_COMPONENT_FIXED_MORPH fixes the coefficients.
      * No other prox flag: the constraint is PositivityConstraint(pos_floor) followed by the
-     * per-plane hard threshold star_thresh. */
+     * per-plane hard threshold star_thresh, or -- StarletMorphology(monotonic=True), marked in
+     * star_monotonic -- MonotonicMaskConstraint about the middle of the box on every plane. */
     SMI_COMPONENT_STARLET = 1 << 20,
     /* the morphology is a radial profile of a few float64 numbers, which are the parameters
      * (GaussianSource / SpergelSource, source.py:131-246; ProfileMorphology, morphology.py:210-473):
@@ -280,6 +281,17 @@ typedef struct smi_components {
     const double *prof_rel_step; /* [n_components][4] relative_step factor (parameter.py:     */
                                  /* 126-129: max(minimum, factor * mean)); 0 = constant step  */
     const int32_t *prof_fixed;   /* [n_components] bit 1 << SMI_PROFILE_*: Parameter(fixed)   */
+    /* monotonic starlet components (StarletMorphology(monotonic=True), morphology.py:549-553);
+     * all NULL if none.  The constraint of such a component's coefficients is
+     * MonotonicMaskConstraint((box_h / 2, box_w / 2), center_radius, variance, max_iter)
+     * (constraint.py:237-259; operator.prox_monotonic_mask, operator.py:131-180) applied to
+     * every plane; its star_thresh entries (still `planes` of them) and pos_floor are ignored. */
+    const int32_t *star_monotonic;     /* [n_components] != 0: monotonic planes; entries of     */
+                                       /* components that are no starlet are ignored            */
+    const int32_t *star_center_radius; /* [n_components] half width of the window the centre is */
+                                       /* looked for in (get_center); 0: the middle itself      */
+    const double *star_variance;       /* [n_components] slack of the monotonicity test, >= 0   */
+    const int32_t *star_max_iter;      /* [n_components] interpolation passes at the most       */
 } smi_components;
 
 int smi_batch_create(const smi_batch_desc *desc, int device, smi_batch **out);
@@ -382,6 +394,12 @@ int smi_batch_set_parameters(smi_batch *b, const float *sed, const float *morph)
  * state-record / save-state calls refuse it. */
 int smi_batch_get_starlet(smi_batch *b, float *coeffs, float *m, float *v, float *vhat,
                           float *gradient);
+/* operator.prox_monotonic_mask about (h / 2, w / 2) (operator.py:131-180) on every plane of
+ * the HOST stack [planes][h][w], in place: the device function the step of a monotonic starlet
+ * component runs in its proximal sub-iterations, launched once on its own (one workgroup; for
+ * tests and parity checks). */
+int smi_starlet_monotonic_mask_f32(float *stack, int32_t planes, int32_t h, int32_t w,
+                                   int32_t center_radius, double variance, int32_t max_iter);
 int smi_batch_set_starlet_moments(smi_batch *b, const float *m, const float *v, const float *vhat);
 /* Profile components: the six doubles {centre y, x, radius, e1, e2, nu} of every component
  * ([n_components][6], zeros for the others), their AMSGrad moments and the gradient of -logL
@@ -416,6 +434,11 @@ int smi_batch_set_fista_state(smi_batch *b, const float *z_sed, const float *z_m
 /* AMSGrad constants forwarded by Blend.fit(**alg_kwargs) to adaprox (blend.py:165-180);
  * defaults b1 = 0.9, b2 = 0.999, eps = 1e-8 (lite/parameters.py:194) */
 int smi_batch_set_optimizer(smi_batch *b, float b1, float b2, float eps);
+/* The same, with b1 and b2 kept in double as well: every kernel goes on with the float32
+ * constants, but the moments of monotonic starlet components (star_monotonic) are taken with
+ * the doubles -- float32(0.999) alone is 1.3e-5 of v = (1 - b2) g^2.  After
+ * smi_batch_set_optimizer the doubles are the float32 values. */
+int smi_batch_set_optimizer_f64(smi_batch *b, double b1, double b2, double eps);
 
 /* scarlet.lite's loss has no normalisation term (lite/models.py:541): with
  * include = 0 the recorded loss is 1/2 sum w (m - d)^2 only (default 1: + log_norm,

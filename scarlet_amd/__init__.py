@@ -25,7 +25,8 @@ from .constraint import (  # noqa: F401
 from .parameter import Parameter, relative_step  # noqa: F401
 from .prior import Prior  # noqa: F401
 from .psf import PSF, ImagePSF, FunctionPSF, GaussianPSF, MoffatPSF  # noqa: F401
-from .batch import BlendBatch, ComponentSpec, PointSourceSpec  # noqa: F401
+from .batch import (BlendBatch, ComponentSpec, MonotonicPlanes, PointSourceSpec,  # noqa: F401
+                    monotonic_planes_prox)  # noqa: F401
 from .frame import Frame  # noqa: F401
 from .observation import Observation  # noqa: F401
 from .renderer import (  # noqa: F401

@@ -71,6 +71,8 @@ class Components(ctypes.Structure):
         ("sed_floor", c_f32p),
         ("prof_kind", c_i32p), ("prof_params", c_f64p), ("prof_step", c_f64p),
         ("prof_rel_step", c_f64p), ("prof_fixed", c_i32p),
+        ("star_monotonic", c_i32p), ("star_center_radius", c_i32p), ("star_variance", c_f64p),
+        ("star_max_iter", c_i32p),
     ]
 
 
@@ -179,6 +181,11 @@ SYMBOLS = {
     "smi_profile_probe": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, c_f64p] + [ctypes.c_int32] * 4
                           + [c_f64p]),
     "smi_batch_set_starlet_moments": (ctypes.c_int, [ctypes.c_void_p] + [c_f32p] * 3),
+    "smi_starlet_monotonic_mask_f32": (
+        ctypes.c_int,
+        [c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+         ctypes.c_int32],
+    ),
     "smi_batch_set_scheme": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "smi_batch_get_fista_state": (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, c_f64p]),
     "smi_batch_set_fista_state": (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, c_f64p]),
@@ -191,6 +198,9 @@ SYMBOLS = {
     "smi_batch_set_inline_render": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "smi_batch_set_optimizer": (
         ctypes.c_int, [ctypes.c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float]
+    ),
+    "smi_batch_set_optimizer_f64": (
+        ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double]
     ),
     "smi_batch_set_stream": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "smi_batch_forward": (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, c_f64p]),

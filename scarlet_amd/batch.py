@@ -6,11 +6,33 @@ one.  All arithmetic happens in ``libscarlet_amd.so`` (HIP); this class only
 packs NumPy arrays for the C ABI.
 """
 
+import collections
 import ctypes
 
 import numpy as np
 
 from . import _lib, operator
+
+
+MonotonicPlanes = collections.namedtuple("MonotonicPlanes", "center_radius variance max_iter")
+MonotonicPlanes.__doc__ = """The constraint of the coefficients of ``StarletMorphology(monotonic=True)`` as the device
+runs it: ``MonotonicMaskConstraint((h // 2, w // 2), center_radius, variance, max_iter)`` on
+every plane.  Given to ``ComponentSpec(starlet=(coefficients, MonotonicPlanes(...)))`` in the
+place of the thresholds."""
+
+
+def monotonic_planes_prox(stack, rule=MonotonicPlanes(1, 0.0, 3)):
+    """The proximal operator of monotonic starlet coefficients as the device loop applies it,
+    once: ``MonotonicMaskConstraint((h // 2, w // 2), *rule)`` on every plane of the
+    ``(planes, h, w)`` stack, in float32.  Returns the new stack.  (The step kernel's own
+    device function on one workgroup: for tests and parity checks, not for speed.)"""
+    out = np.array(stack, dtype=np.float32, order="C")
+    assert out.ndim == 3
+    planes, h, w = out.shape
+    _lib.check(_lib.load().smi_starlet_monotonic_mask_f32(
+        _lib.ptr(out, ctypes.c_float), planes, h, w, int(rule.center_radius),
+        float(rule.variance), int(rule.max_iter)))
+    return out
 
 
 class ComponentSpec:
@@ -58,12 +80,19 @@ class ComponentSpec:
         # StarletMorphology (morphology.py:516-604): ``starlet = (coefficients (planes, h, w),
         # absolute threshold per plane)``; the coefficients are the parameter, ``morph`` only
         # gives the box shape, ``morph_step`` / ``pos_floor`` are the coefficients' step and
-        # positivity floor.  Of ``prox_flags`` only the two FIXED bits are kept.
-        self.star_coeffs = self.star_thresh = None
+        # positivity floor.  Of ``prox_flags`` only the two FIXED bits are kept.  With a
+        # ``MonotonicPlanes`` in the place of the thresholds the planes are kept monotonic
+        # about the middle of the box instead (``pos_floor`` is then not used).
+        self.star_coeffs = self.star_thresh = self.star_monotonic = None
         if starlet is not None:
             coeffs, thresh = starlet
             self.star_coeffs = np.ascontiguousarray(coeffs, dtype=np.float32)
             assert self.star_coeffs.ndim == 3 and self.star_coeffs.shape[1:] == self.morph.shape
+            if isinstance(thresh, MonotonicPlanes):
+                self.star_monotonic = MonotonicPlanes(
+                    int(thresh.center_radius), float(thresh.variance), int(thresh.max_iter))
+                assert min(self.star_monotonic) >= 0
+                thresh = np.zeros(len(self.star_coeffs))
             self.star_thresh = np.ascontiguousarray(thresh, dtype=np.float32)
             assert self.star_thresh.shape == self.star_coeffs.shape[:1]
             fixed = _lib.COMPONENT_FIXED_SED | _lib.COMPONENT_FIXED_MORPH
@@ -315,6 +344,13 @@ class BlendBatch:
             [flat[k].star_coeffs.reshape(-1) for k in star]) if star and values else np.zeros(0))
         arrays["star_thresh"] = _lib.f32(np.concatenate(
             [flat[k].star_thresh for k in star]) if star and values else np.zeros(0))
+        # ... and the rules of the monotonic ones, sent only when there is one
+        mono = [getattr(c, "star_monotonic", None) for c in flat]
+        for j, name in enumerate(("star_center_radius", "star_variance", "star_max_iter")):
+            arrays[name] = np.ascontiguousarray(
+                [0 if r is None else r[j] for r in mono],
+                dtype=np.float64 if j == 1 else np.int32) if any(mono) else None
+        arrays["star_monotonic"] = _lib.i32([r is not None for r in mono]) if any(mono) else None
         # spectrum floors: sent only when some component asks for another one than 1e-20
         floors = None
         if any(c.sed_floor is not None for c in flat):
@@ -612,7 +648,7 @@ class BlendBatch:
 
     def set_optimizer(self, b1=0.9, b2=0.999, eps=1e-8):
         """AMSGrad constants (``proxmin.adaprox`` keywords b1, b2, eps)."""
-        _lib.check(self._lib.smi_batch_set_optimizer(self._h, b1, b2, eps))
+        _lib.check(self._lib.smi_batch_set_optimizer_f64(self._h, b1, b2, eps))
 
     def set_stream(self, stream_handle):
         """Launch on the given HIP stream (e.g. ``torch.cuda.current_stream().cuda_stream``)."""

@@ -15,10 +15,10 @@ from functools import partial
 import numpy as np
 
 from . import _lib, fft
-from .batch import BlendBatch, ComponentSpec, PointSourceSpec
+from .batch import BlendBatch, ComponentSpec, MonotonicPlanes, PointSourceSpec
 from .bbox import overlapped_slices
 from .component import CombinedComponent, FactorizedComponent
-from .constraint import PositivityConstraint, device_flags
+from .constraint import MonotonicMaskConstraint, PositivityConstraint, device_flags
 from .hoststep import HostBandSource, HostParameter, HostVector
 from .model import UpdateException
 from .morphology import (GaussianMorphology, PointSourceMorphology, ProfileMorphology, ProfileProx,
@@ -165,14 +165,12 @@ def _step_rule(step, what):
 # -- the rules of the adaprox round loop (blend.py:276-302), for every fit that runs one
 def _starlet_rules(morphology, scheme):
     """``(step, positivity floor, threshold per plane)`` of the coefficients of a
-    ``StarletMorphology`` as the device runs them; ``NotImplementedError`` for what it does
-    not: monotonic planes, another scheme than amsgrad, a prior, a step callable, another
-    constraint than ``ConstraintChain(PositivityConstraint, L0Constraint(absolute))``."""
+    ``StarletMorphology`` as the device runs them -- with ``monotonic`` planes ``(step, 0,
+    MonotonicPlanes)`` -- and ``NotImplementedError`` for what it does not: another scheme
+    than amsgrad, a prior, a step callable, another constraint than
+    ``ConstraintChain(PositivityConstraint, L0Constraint(absolute))`` or, if ``monotonic``, than
+    a ``MonotonicMaskConstraint`` about the middle of the box."""
     coeffs = morphology._parameters[0]
-    if morphology.monotonic:
-        raise NotImplementedError(
-            "StarletMorphology(monotonic=True) cannot be fitted yet: the per-plane "
-            "MonotonicMaskConstraint does not run in the device loop")
     if scheme != "amsgrad":
         raise NotImplementedError("starlet sources with another scheme than amsgrad")
     if coeffs.prior is not None:
@@ -183,12 +181,36 @@ def _starlet_rules(morphology, scheme):
         rule = _step_rule(coeffs.step, "morphology")
     if rule is None or rule[1]:
         raise NotImplementedError("starlet coefficients need a constant step (got a callable)")
+    if morphology.monotonic:
+        return float(rule[0]), 0.0, _monotonic_planes(coeffs)
     limits = plane_thresholds(coeffs.constraint)
     if limits is None or len(limits[1]) != coeffs.shape[0]:
         raise NotImplementedError(
             "starlet coefficients need the constraint ConstraintChain(PositivityConstraint, "
             "L0Constraint(per-plane thresholds, type='absolute'))")
     return float(rule[0]), limits[0], limits[1]
+
+
+def _monotonic_planes(coeffs):
+    """The ``MonotonicMaskConstraint`` of monotonic starlet coefficients as the device's
+    ``MonotonicPlanes``: about the middle of the current box, with whole non-negative numbers."""
+    c = coeffs.constraint
+    middle = tuple(n // 2 for n in coeffs.shape[-2:])
+
+    def whole(x):
+        return isinstance(x, (int, np.integer)) and not isinstance(x, bool) and x >= 0
+
+    ok = type(c) is MonotonicMaskConstraint
+    ok = ok and np.shape(c.center) == (2,) and all(
+        whole(a) and a == m for a, m in zip(c.center, middle))
+    ok = ok and whole(c.center_radius) and whole(c.max_iter)
+    ok = ok and isinstance(c.variance, (int, float, np.integer, np.floating)) and c.variance >= 0
+    if not ok:
+        raise NotImplementedError(
+            "monotonic starlet coefficients need the constraint MonotonicMaskConstraint((h // 2, "
+            "w // 2), center_radius >= 0, variance >= 0, max_iter >= 0) with whole numbers for "
+            "the centre, center_radius and max_iter")
+    return MonotonicPlanes(int(c.center_radius), float(c.variance), int(c.max_iter))
 
 
 def _refuse_unfittable_starlets(sources, scheme):

@@ -164,7 +164,8 @@ class MonotonicMaskConstraint(Constraint):
     """Monotonicity by branching out from ``center``: pixels that no monotonic path
     connects to the centre are interpolated (``operator.prox_monotonic_mask``; reference
     constraint.py:237-259).  A 3-D ``morph`` is treated image by image.  Inside
-    ``Blend.fit`` it runs on the host (hoststep.py)."""
+    ``Blend.fit`` it runs on the host (hoststep.py), but for the coefficients of a
+    ``StarletMorphology(monotonic=True)``, where the device loop applies it."""
 
     def __init__(self, center, center_radius=1, variance=0.0, max_iter=3):
         self.center = center

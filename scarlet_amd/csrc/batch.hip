@@ -232,6 +232,10 @@ struct smi_batch {
     float *st_thresh = nullptr, *st_coeffs = nullptr, *st_mom[3] = {nullptr, nullptr, nullptr},
           *st_grad = nullptr, *st_work = nullptr;
     int64_t n_star_coeffs = 0;
+    // ... of which the monotonic ones (all nullptr if the batch has none)
+    int32_t *st_mono = nullptr, *st_mono_radius = nullptr, *st_mono_iter = nullptr;
+    double *st_mono_var = nullptr;
+    float *st_zsave = nullptr;
     // profile components (profile_source.hip): the view and the arrays it points into
     smi::ProfileView prof{};
     int32_t *pf_comp = nullptr, *pf_kind = nullptr, *pf_fixed = nullptr;
@@ -298,6 +302,7 @@ struct smi_batch {
     int max_levels = 0;
     BatchView view{};
     float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
+    double b1_f64 = 0.9, b2_f64 = 0.999;  // as given (smi_batch_set_optimizer_f64)
     // timing
     bool timing = false;
     std::vector<hipEvent_t> events;
@@ -921,6 +926,7 @@ int smi_batch_destroy(smi_batch *b) {
                     b->loss_hist, b->last_loss, b->loss_partial, b->d_plans, b->work_items,
                     b->c_sed_floor, b->st_comp, b->st_planes, b->st_fixed, b->st_toff, b->st_coff, b->st_thresh,
                     b->st_coeffs, b->st_mom[0], b->st_mom[1], b->st_mom[2], b->st_grad, b->st_work,
+                    b->st_mono, b->st_mono_radius, b->st_mono_iter, b->st_mono_var, b->st_zsave,
                     b->pf_comp, b->pf_kind, b->pf_fixed, b->pf_step, b->pf_rel, b->pf_par, b->pf_grad,
                     b->pf_mom[0], b->pf_mom[1], b->pf_mom[2]};
     for (void *p : bufs)
@@ -1622,6 +1628,13 @@ static int set_components_impl(smi_batch *b, const smi_components *c, const int3
             SMI_REQUIRE(c->star_planes[k] >= 1 && c->star_planes[k] <= 31, "starlet planes out of range");
             SMI_REQUIRE(c->box_h[k] <= 4096 && c->box_w[k] <= 4096 && np * c->star_planes[k] < ((int64_t)1 << 31),
                         "starlet component box too large");
+            if (c->star_monotonic && c->star_monotonic[k]) {
+                SMI_REQUIRE(c->star_center_radius && c->star_variance && c->star_max_iter,
+                            "monotonic starlet component without star_center_radius / star_variance / star_max_iter");
+                SMI_REQUIRE(c->star_center_radius[k] >= 0 && c->star_max_iter[k] >= 0 &&
+                                c->star_variance[k] >= 0.0,  // (false for a NaN)
+                            "monotonic starlet component: center_radius, variance and max_iter must be >= 0");
+            }
             ++n_star;
         }
         if (c->prox_flags[k] & SMI_COMPONENT_PROFILE) {
@@ -1885,9 +1898,11 @@ static int set_components_impl(smi_batch *b, const smi_components *c, const int3
     }
     // starlet components: coefficients, thresholds and moments in arrays of their own
     {
-        std::vector<int32_t> comp, planes, fixed, toff(1, 0);
+        std::vector<int32_t> comp, planes, fixed, toff(1, 0), mono, mono_radius, mono_iter;
+        std::vector<double> mono_var;
         std::vector<int64_t> coff(1, 0);
         int star_pix = 0;
+        bool any_mono = false;
         for (int k = 0; k < n; ++k) {
             if (!(c->prox_flags[k] & SMI_COMPONENT_STARLET)) continue;
             comp.push_back(k);
@@ -1896,8 +1911,15 @@ static int set_components_impl(smi_batch *b, const smi_components *c, const int3
             toff.push_back(toff.back() + c->star_planes[k]);
             coff.push_back(coff.back() + (int64_t)c->star_planes[k] * (moff[k + 1] - moff[k]));
             star_pix = std::max(star_pix, (int)(moff[k + 1] - moff[k]));
+            const bool is_mono = c->star_monotonic && c->star_monotonic[k];
+            any_mono |= is_mono;
+            mono.push_back(is_mono ? 1 : 0);
+            mono_radius.push_back(is_mono ? c->star_center_radius[k] : 0);
+            mono_iter.push_back(is_mono ? c->star_max_iter[k] : 0);
+            mono_var.push_back(is_mono ? c->star_variance[k] : 0.0);
         }
-        for (float **p : {&b->st_coeffs, &b->st_mom[0], &b->st_mom[1], &b->st_mom[2], &b->st_grad, &b->st_work})
+        for (float **p : {&b->st_coeffs, &b->st_mom[0], &b->st_mom[1], &b->st_mom[2], &b->st_grad, &b->st_work,
+                          &b->st_zsave})
             if (*p) {
                 SMI_HIP(hipFree(*p));
                 *p = nullptr;
@@ -1934,6 +1956,18 @@ static int set_components_impl(smi_batch *b, const smi_components *c, const int3
             b->star.vh = b->st_mom[2];
             b->star.grad = b->st_grad;
             b->star.work = b->st_work;
+            if (any_mono) {
+                if ((rc = upload(&b->st_mono, mono.data(), mono.size()))) return rc;
+                if ((rc = upload(&b->st_mono_radius, mono_radius.data(), mono_radius.size()))) return rc;
+                if ((rc = upload(&b->st_mono_iter, mono_iter.data(), mono_iter.size()))) return rc;
+                if ((rc = upload(&b->st_mono_var, mono_var.data(), mono_var.size()))) return rc;
+                SMI_HIP(dev_alloc(&b->st_zsave, (size_t)b->n_morph));
+                b->star.mono = b->st_mono;
+                b->star.mono_radius = b->st_mono_radius;
+                b->star.mono_max_iter = b->st_mono_iter;
+                b->star.mono_variance = b->st_mono_var;
+                b->star.zsave = b->st_zsave;
+            }
         }
     }
     // profile components: six doubles of parameters, moments and gradient each
@@ -2469,6 +2503,17 @@ int smi_batch_get_starlet(smi_batch *b, float *coeffs, float *m, float *v, float
     return SMI_OK;
 }
 
+int smi_starlet_monotonic_mask_f32(float *stack, int32_t planes, int32_t h, int32_t w,
+                                   int32_t center_radius, double variance, int32_t max_iter) {
+    SMI_REQUIRE(stack, "null argument");
+    SMI_REQUIRE(planes >= 1 && h >= 1 && w >= 1 && h <= 4096 && w <= 4096 &&
+                    (int64_t)planes * h * w < ((int64_t)1 << 31),
+                "bad stack shape");
+    SMI_REQUIRE(center_radius >= 0 && max_iter >= 0 && variance >= 0.0,
+                "center_radius, variance and max_iter must be >= 0");
+    return starlet_monotonic_mask_host(stack, planes, h, w, center_radius, variance, max_iter);
+}
+
 int smi_batch_set_starlet_moments(smi_batch *b, const float *m, const float *v, const float *vhat) {
     SMI_REQUIRE(b && b->have_components, "components not set");
     SMI_HIP(hipSetDevice(b->device));
@@ -2491,9 +2536,19 @@ int smi_batch_set_optimizer(smi_batch *b, float b1, float b2, float eps) {
     b->b1 = b1;
     b->b2 = b2;
     b->eps = eps;
+    b->b1_f64 = (double)b1;
+    b->b2_f64 = (double)b2;
     const int keep = b->view.max_box_pixels;
     refresh_view(b);
     b->view.max_box_pixels = keep;
+    return SMI_OK;
+}
+
+int smi_batch_set_optimizer_f64(smi_batch *b, double b1, double b2, double eps) {
+    if (int rc = smi_batch_set_optimizer(b, (float)b1, (float)b2, (float)eps)) return rc;
+    SMI_REQUIRE(b1 >= 0.0 && b1 < 1.0 && b2 >= 0.0 && b2 < 1.0, "bad AMSGrad constants");
+    b->b1_f64 = b1;
+    b->b2_f64 = b2;
     return SMI_OK;
 }
 
@@ -2815,6 +2870,8 @@ int smi_batch_step(smi_batch *b, int32_t it0, int32_t n_iter, float e_rel, int32
         lowres_add_all(b);
         if ((rc = launch_shift_backward(v, b->Q, it, nullptr, 0, b->stream))) return rc;
         // (before the spectra move: the coefficient gradient belongs to this iteration's spectrum)
+        b->star.b1 = b->b1_f64;
+        b->star.b2 = b->b2_f64;
         if ((rc = launch_starlet_step(v, b->star, b->Q, it, e_rel, prox_max_iter, 0, b->stream)))
             return rc;
         if ((rc = launch_profile_step(v, b->prof, b->Q, it, e_rel, prox_max_iter, 0, b->stream)))

@@ -368,6 +368,18 @@ struct StarletView {
     // work planes of boxes beyond the LDS: 2 N floats per component at 2 c_moff[k] (nullptr:
     // every starlet box of the batch has at most kStarLdsPixels pixels and they live in LDS)
     float *work = nullptr;
+    // StarletMorphology(monotonic=True): mono[s] != 0 puts prox_monotonic_mask about the middle
+    // of the box, per plane, in the place of floor and threshold, with mono_radius[s] (the
+    // window of get_center), mono_variance[s] and mono_max_iter[s]; zsave holds one plane per
+    // component at c_moff[k].  All nullptr: no such component in the batch.
+    const int32_t *mono = nullptr;
+    const int32_t *mono_radius = nullptr;
+    const int32_t *mono_max_iter = nullptr;
+    const double *mono_variance = nullptr;
+    float *zsave = nullptr;
+    // b1, b2 of AMSGrad in double (smi_batch_set_optimizer_f64), for the moments of the
+    // monotonic components; set by the launch site
+    double b1 = 0.9, b2 = 0.999;
 };
 constexpr int kStarLdsPixels = 20000;  // two float planes + reduction scratch in 160 KiB
 bool starlet_needs_scratch(int max_pixels);
@@ -375,6 +387,10 @@ bool starlet_needs_scratch(int max_pixels);
 // coefficients (of blends that are still iterating)
 int launch_starlet_step(const BatchView &v, const StarletView &sv, const float *G, int32_t it,
                         float e_rel, int32_t prox_max_iter, int32_t grad_only, hipStream_t s);
+// prox_monotonic_mask about (h / 2, w / 2) on every plane of a host [planes][h][w] stack, in
+// place, by the device function of the step kernel
+int starlet_monotonic_mask_host(float *stack, int32_t planes, int32_t h, int32_t w,
+                                int32_t center_radius, double variance, int32_t max_iter);
 // coefficients -> the `morph` slots
 int launch_starlet_forward(const BatchView &v, const StarletView &sv, int32_t respect_state,
                            hipStream_t s);

@@ -20,84 +20,12 @@
 // conditions of the column branches, `i > 2` / `i < rows - 2`, the `else if` bound
 // updates; the unguarded i+-1 / j+-1 accesses of the non-recursive branch are guarded.
 #include "common.h"
+#include "mask_device.h"
 
 namespace smi {
 namespace {
 
-constexpr int kT = 1024;
-
-struct FillShared {
-    int changed;
-    int rmin, rmax, cmin, cmax;
-};
-
-template <typename T>
-__device__ void flood_fill(int start, const T *image, int rows, int cols, uint8_t *unchecked,
-                           uint8_t *orphans, int32_t *visited, int gen, double variance,
-                           double thresh, int32_t *bounds, FillShared *sh) {
-    const int tid = threadIdx.x, N = rows * cols;
-    if (tid == 0) {
-        visited[start] = gen;
-        sh->rmin = bounds[0];
-        sh->rmax = bounds[1];
-        sh->cmin = bounds[2];
-        sh->cmax = bounds[3];
-    }
-    __syncthreads();
-    for (;;) {
-        if (tid == 0) sh->changed = 0;
-        __syncthreads();
-        for (int p = tid; p < N; p += kT) {
-            if (!unchecked[p] || visited[p] == gen) continue;
-            const int r = p / cols, c = p - r * cols;
-            const double val = (double)image[p];
-            bool accept = false;
-            const int nb[4] = {r > 0 ? p - cols : -1, r < rows - 1 ? p + cols : -1,
-                               c > 0 ? p - 1 : -1, c < cols - 1 ? p + 1 : -1};
-            for (int k = 0; k < 4; ++k) {
-                const int q = nb[k];
-                if (q < 0 || visited[q] != gen) continue;
-                const double th = q == start ? thresh : 0.0;
-                if (val < (double)image[q] + variance && val > th) accept = true;
-            }
-            if (accept) {
-                visited[p] = gen;
-                unchecked[p] = 0;
-                sh->changed = 1;
-            }
-        }
-        __syncthreads();
-        const int again = sh->changed;
-        __syncthreads();
-        if (!again) break;
-    }
-    for (int p = tid; p < N; p += kT) {
-        const int r = p / cols, c = p - r * cols;
-        if (visited[p] == gen) {
-            if (p != start) {
-                orphans[p] = 0;
-                atomicMin(&sh->rmin, r);
-                atomicMax(&sh->rmax, r);
-                atomicMin(&sh->cmin, c);
-                atomicMax(&sh->cmax, c);
-            }
-        } else if (unchecked[p]) {
-            const bool touched = (r > 0 && visited[p - cols] == gen) ||
-                                 (r < rows - 1 && visited[p + cols] == gen) ||
-                                 (c > 0 && visited[p - 1] == gen) ||
-                                 (c < cols - 1 && visited[p + 1] == gen);
-            if (touched) orphans[p] = 1;
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        bounds[0] = sh->rmin;
-        bounds[1] = sh->rmax;
-        bounds[2] = sh->cmin;
-        bounds[3] = sh->cmax;
-    }
-    __syncthreads();
-}
+constexpr int kT = kMaskT;
 
 template <typename T>
 __global__ __launch_bounds__(kT) void valid_pixels_kernel(int i, int j, const T *image, int rows,
@@ -120,81 +48,20 @@ __global__ __launch_bounds__(kT) void interpolate_kernel(const int32_t *row_idx,
     __shared__ FillShared sh;
     __shared__ int fill;
     int gen = 0;
-#define AT(a, b) ((a) * cols + (b))
     for (int n = 0; n < n_idx; ++n) {
         const int i = row_idx[n], j = col_idx[n];
         if (threadIdx.x == 0) {
-            fill = 0;
-            if (unchecked[AT(i, j)]) {
-                T total = 0;
-                int valid = 0, pending = 0;
-                unchecked[AT(i, j)] = 0;
-                if (i < rows - 2 && model[AT(i + 2, j)] > model[AT(i + 1, j)]) {
-                    if (unchecked[AT(i + 2, j)] || unchecked[AT(i + 1, j)]) {
-                        pending = 1;
-                    } else {
-                        const T grad = model[AT(i + 2, j)] - model[AT(i + 1, j)];
-                        total += model[AT(i + 1, j)] - grad;
-                        valid += 1;
-                    }
-                }
-                if (i > 2 && model[AT(i - 2, j)] > model[AT(i - 1, j)]) {
-                    if (unchecked[AT(i - 2, j)] || unchecked[AT(i - 1, j)]) {
-                        pending = 1;
-                    } else {
-                        const T grad = model[AT(i - 2, j)] - model[AT(i - 1, j)];
-                        total += model[AT(i - 1, j)] - grad;
-                        valid += 1;
-                    }
-                }
-                if (j < cols - 2 && model[AT(i, j + 2)] > model[AT(i, j + 1)]) {
-                    if (unchecked[AT(i, j + 1)]) {  // `unchecked(i,j+2), unchecked(i,j+1)`
-                        pending = 1;
-                    } else {
-                        const T grad = model[AT(i, j + 2)] - model[AT(i, j + 1)];
-                        total += model[AT(i, j + 1)] - grad;
-                        valid += 1;
-                    }
-                }
-                if (j > 2 && model[AT(i, j - 2)] > model[AT(i, j - 1)]) {
-                    if (unchecked[AT(i, j - 1)]) {
-                        pending = 1;
-                    } else {
-                        const T grad = model[AT(i, j - 2)] - model[AT(i, j - 1)];
-                        total += model[AT(i, j - 1)] - grad;
-                        valid += 1;
-                    }
-                }
-                if (total > 0) {
-                    model[AT(i, j)] = total / valid;
-                    orphans[AT(i, j)] = 0;
-                    if (i < bounds[0]) bounds[0] = i;
-                    else if (i > bounds[1]) bounds[1] = i;
-                    if (j < bounds[2]) bounds[2] = j;
-                    else if (j > bounds[3]) bounds[3] = j;
-                    if (recursive) {
-                        fill = 1;
-                    } else {
-                        if (i > 0 && unchecked[AT(i - 1, j)]) orphans[AT(i - 1, j)] = 1;
-                        if (i < rows - 1 && unchecked[AT(i + 1, j)]) orphans[AT(i + 1, j)] = 1;
-                        if (j > 0 && unchecked[AT(i, j - 1)]) orphans[AT(i, j - 1)] = 1;
-                        if (j < cols - 1 && unchecked[AT(i, j + 1)]) orphans[AT(i, j + 1)] = 1;
-                    }
-                } else if (!pending) {
-                    orphans[AT(i, j)] = 1;
-                    model[AT(i, j)] = 0;
-                }
-            }
+            fill = interpolate_pixel<T>(i, j, unchecked, model, rows, cols, orphans, recursive,
+                                        bounds);
             __threadfence_block();
         }
         __syncthreads();
         const int do_fill = fill;
         __syncthreads();
         if (do_fill)
-            flood_fill<T>(AT(i, j), model, rows, cols, unchecked, orphans, visited, ++gen, variance,
-                          0.0, bounds, &sh);
+            flood_fill<T>(i * cols + j, model, rows, cols, unchecked, orphans, visited, ++gen,
+                          variance, 0.0, bounds, &sh);
     }
-#undef AT
 }
 
 template <typename T>

@@ -15,7 +15,9 @@
 //                           proximal sub-iterations z <- prox(z - psi / max(psi) (z - x)), prox =
 //                           max(., floor) then |.| < t_plane -> 0, stopped on the device by
 //                           ||z' - z||^2 <= e_rel^2 ||z||^2 over all planes
-//                           (oracle.pgm.adaprox_update);
+//                           (oracle.pgm.adaprox_update); for a component of
+//                           StarletMorphology(monotonic=True) prox is prox_monotonic_mask on
+//                           every plane instead (mask_device.h), see below;
 //   starlet_forward_kernel  the reconstruction of the coefficients into the component's `morph`
 //                           slot, which the render stage and the spectrum's gradient read.
 // The spectrum is stepped by the ordinary update kernel in between: it sees the component as an
@@ -29,15 +31,19 @@
 #include <algorithm>
 
 #include "common.h"
+#include "mask_device.h"
 
 namespace smi {
 namespace {
 
-constexpr int kT = 1024;
+constexpr int kT = kMaskT;
 constexpr int kWaves = kT / 64;
 constexpr float H0 = 1.0f / 16, H1 = 1.0f / 4, H2 = 3.0f / 8;
-// reduction scratch in front of the work planes: kWaves doubles x 2 + kWaves floats, padded
+// reduction scratch in front of the work planes: kWaves doubles x 2 + kWaves floats, then the
+// shared words of the monotonic mask operator, padded
 constexpr int kRedBytes = 512;
+constexpr int kMaskSharedAt = 2 * kWaves * sizeof(double) + kWaves * sizeof(float);
+static_assert(kMaskSharedAt % 8 == 0 && kMaskSharedAt + sizeof(MaskShared) <= kRedBytes, "");
 
 extern __shared__ __attribute__((aligned(16))) unsigned char star_lds[];
 
@@ -135,6 +141,25 @@ __device__ __forceinline__ StarCtx star_ctx(const BatchView &v, const StarletVie
     return c;
 }
 
+// The monotonic mask operator on the P planes of a stack, one after the other.  Its state lives
+// in the two work planes, which the B-spline passes have left by then: `visited` in the first,
+// the three byte maps in the second (3 N of its 4 N bytes) -- in LDS or in the global scratch,
+// wherever the work planes are.
+struct MonoRule {
+    int cy, cx, radius, max_iter;
+    double variance;
+};
+
+__device__ __forceinline__ void mono_plane(float *plane, const StarCtx &c, const MonoRule &r) {
+    monotonic_mask_plane(plane, c.h, c.w, r.cy, r.cx, r.radius, r.variance, r.max_iter,
+                         reinterpret_cast<int32_t *>(c.work0),
+                         reinterpret_cast<uint8_t *>(c.work1),
+                         reinterpret_cast<MaskShared *>(star_lds + kMaskSharedAt));
+}
+
+// MONO: the batch holds monotonic components (sv.mono); the instance without is the kernel as
+// it was before they existed, and batches without them keep launching it.
+template <bool MONO>
 __global__ __launch_bounds__(kT) void starlet_step_kernel(BatchView v, StarletView sv,
                                                           const float *G, int it, float e_rel,
                                                           int prox_max_iter, int grad_only) {
@@ -175,14 +200,24 @@ __global__ __launch_bounds__(kT) void starlet_step_kernel(BatchView v, StarletVi
     const int lit = v.local_it(c.b, it);
     const float alpha = v.c_morph_step[c.k];
     const float b1 = v.b1, b2 = v.b2, eps = v.eps;
+    // a monotonic component takes its moments with the constants as the caller gave them
+    // (float32(0.999) alone puts 1.3e-5 on v); the others keep the batch's float32 ones
+    const bool exact = MONO && sv.mono[blockIdx.x];
     float max_psi = 0.f;
     int bad = 0;
     for (int p = 0; p < c.P; ++p)
         for (int q = tid; q < N; q += kT) {
             const int64_t i = (int64_t)p * N + q;
             const float g = fixed ? 0.f : grad[i];
-            const float mi = (1.f - b1) * g + b1 * m[i];
-            const float vi = (1.f - b2) * (g * g) + b2 * vv[i];
+            float mi, vi;
+            if (MONO && exact) {
+                const double gd = (double)g;
+                mi = (float)((1.0 - sv.b1) * gd + sv.b1 * (double)m[i]);
+                vi = (float)((1.0 - sv.b2) * (gd * gd) + sv.b2 * (double)vv[i]);
+            } else {
+                mi = (1.f - b1) * g + b1 * m[i];
+                vi = (1.f - b2) * (g * g) + b2 * vv[i];
+            }
             const float vhi = lit == 0 ? vi : fmaxf(vh[i], vi);
             const float psi = eps > 0.f ? sqrtf(fmaxf(vhi, eps)) : sqrtf(vhi);
             float upd = alpha * mi / psi;
@@ -202,6 +237,51 @@ __global__ __launch_bounds__(kT) void starlet_step_kernel(BatchView v, StarletVi
     // 4. proximal sub-iterations in the metric psi; z lives in the coefficient array.  The
     //    first one starts at z = x, where z - psi / max(psi) (z - x) is x itself.
     const float e2 = e_rel * e_rel;
+    if (MONO && sv.mono[blockIdx.x]) {
+        // prox = prox_monotonic_mask per plane (MonotonicMaskConstraint.__call__ on a stack): the
+        // candidate y goes into the coefficient plane, the operator works on it in place with
+        // the whole workgroup, and z waits in the component's plane of sv.zsave for the norm
+        MonoRule rule;
+        rule.cy = c.h / 2;
+        rule.cx = c.w / 2;
+        rule.radius = sv.mono_radius[blockIdx.x];
+        rule.max_iter = sv.mono_max_iter[blockIdx.x];
+        rule.variance = sv.mono_variance[blockIdx.x];
+        float *zs = sv.zsave + v.c_moff[c.k];
+        for (int t = 1; t <= prox_max_iter; ++t) {
+            double d2 = 0.0, n2 = 0.0;
+            bad = 0;
+            for (int p = 0; p < c.P; ++p) {
+                float *plane = x + (int64_t)p * N;
+                for (int q = tid; q < N; q += kT) {
+                    const int64_t i = (int64_t)p * N + q;
+                    const float xi = grad[i];
+                    float z, y;
+                    if (t == 1) {
+                        z = y = xi;
+                    } else {
+                        z = plane[q];
+                        const float psi = eps > 0.f ? sqrtf(fmaxf(vh[i], eps)) : sqrtf(vh[i]);
+                        y = z - psi / max_psi * (z - xi);
+                    }
+                    bad |= !isfinite(y) || !isfinite(xi);
+                    zs[q] = z;
+                    plane[q] = y;
+                    n2 += (double)z * (double)z;
+                }
+                __syncthreads();
+                mono_plane(plane, c, rule);
+                for (int q = tid; q < N; q += kT) {
+                    const float dz = plane[q] - zs[q];
+                    d2 += (double)dz * (double)dz;
+                }
+            }
+            block_sum2(d2, n2, red);
+            if (d2 <= (double)e2 * n2) break;
+        }
+        if (__syncthreads_or(bad) && tid == 0) atomicExch(&v.state[c.b], v.fail_code);
+        return;
+    }
     for (int t = 1; t <= prox_max_iter; ++t) {
         double d2 = 0.0, n2 = 0.0;
         bad = 0;
@@ -257,13 +337,32 @@ __global__ __launch_bounds__(kT) void starlet_forward_kernel(BatchView v, Starle
     if (__syncthreads_or(bad) && threadIdx.x == 0) atomicExch(&v.state[c.b], v.fail_code);
 }
 
+// prox_monotonic_mask once on every plane of a [planes][h][w] stack: the operator of the step
+// kernel on its own, with the work planes where a component of that box would have them
+__global__ __launch_bounds__(kT) void starlet_mono_kernel(float *stack, int planes, int h, int w,
+                                                          MonoRule rule, float *work) {
+    StarCtx c;
+    c.h = h;
+    c.w = w;
+    c.N = h * w;
+    c.P = planes;
+    c.work0 = work ? work : reinterpret_cast<float *>(star_lds + kRedBytes);
+    c.work1 = c.work0 + ((c.N + 3) & ~3);
+    for (int p = 0; p < planes; ++p) mono_plane(stack + (int64_t)p * c.N, c, rule);
+}
+
 size_t star_lds_bytes(const StarletView &sv) {
     return kRedBytes + (sv.work ? 0 : 2 * (size_t)((sv.max_pixels + 3) & ~3) * sizeof(float));
 }
 
 int configure_starlet_kernels(size_t lds) {
     static size_t cfg_step[kMaxDevices] = {}, cfg_forward[kMaxDevices] = {};
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(starlet_step_kernel), lds, cfg_step))
+    static size_t cfg_mono[kMaxDevices] = {};
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(starlet_step_kernel<false>), lds,
+                                    cfg_step))
+        return rc;
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(starlet_step_kernel<true>), lds,
+                                    cfg_mono))
         return rc;
     return ensure_dynamic_lds(reinterpret_cast<const void *>(starlet_forward_kernel), lds,
                               cfg_forward);
@@ -279,9 +378,47 @@ int launch_starlet_step(const BatchView &v, const StarletView &sv, const float *
     const size_t lds = star_lds_bytes(sv);
     SMI_REQUIRE(lds <= 160 * 1024, "starlet component box too large for the LDS");
     if (int rc = configure_starlet_kernels(lds)) return rc;
-    hipLaunchKernelGGL(starlet_step_kernel, dim3(sv.n_star), dim3(kT), lds, s, v, sv, G, it, e_rel,
-                       prox_max_iter, grad_only);
+    if (sv.mono)
+        hipLaunchKernelGGL(starlet_step_kernel<true>, dim3(sv.n_star), dim3(kT), lds, s, v, sv, G,
+                           it, e_rel, prox_max_iter, grad_only);
+    else
+        hipLaunchKernelGGL(starlet_step_kernel<false>, dim3(sv.n_star), dim3(kT), lds, s, v, sv, G,
+                           it, e_rel, prox_max_iter, grad_only);
     return SMI_OK;
+}
+
+int starlet_monotonic_mask_host(float *stack, int32_t planes, int32_t h, int32_t w,
+                                int32_t center_radius, double variance, int32_t max_iter) {
+    const size_t N = (size_t)h * w, bytes = (size_t)planes * N * sizeof(float);
+    const bool scratch = starlet_needs_scratch((int)N);
+    float *d_stack = nullptr, *d_work = nullptr;
+    int rc = SMI_OK;
+    const size_t lds = kRedBytes + (scratch ? 0 : 2 * ((N + 3) & ~(size_t)3) * sizeof(float));
+    static size_t cfg[kMaxDevices] = {};
+    if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(starlet_mono_kernel), lds, cfg)))
+        return rc;
+    SMI_HIP(hipMalloc(reinterpret_cast<void **>(&d_stack), bytes));
+    hipError_t e = scratch ? hipMalloc(reinterpret_cast<void **>(&d_work),
+                                       2 * ((N + 3) & ~(size_t)3) * sizeof(float))
+                           : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpy(d_stack, stack, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        MonoRule rule;
+        rule.cy = h / 2;
+        rule.cx = w / 2;
+        rule.radius = center_radius;
+        rule.max_iter = max_iter;
+        rule.variance = variance;
+        hipLaunchKernelGGL(starlet_mono_kernel, dim3(1), dim3(kT), lds, 0, d_stack, planes, h, w,
+                           rule, d_work);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(stack, d_stack, bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(d_stack);
+    if (d_work) (void)hipFree(d_work);
+    SMI_HIP(e);
+    return rc;
 }
 
 int launch_starlet_forward(const BatchView &v, const StarletView &sv, int32_t respect_state,

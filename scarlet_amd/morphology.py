@@ -284,8 +284,8 @@ class StarletMorphology(Morphology):
 
     Not monotonic (the default): the coefficients are kept positive and every plane but the
     last is hard-thresholded at ``threshold`` times the norm of its wavelet.  ``monotonic``:
-    a ``MonotonicMaskConstraint`` about the middle of the box instead (constructed here;
-    ``Blend.fit`` does not run it).  The transform runs on the device, so the coefficients
+    a ``MonotonicMaskConstraint`` about the middle of the box instead, which ``Blend.fit`` runs
+    plane by plane in the device loop and which a shrink re-centres on the new box.  The transform runs on the device, so the coefficients
     are the reference's bit for bit.
 
     Unlike the reference, a shrink keeps the thresholds per plane: the reference's
