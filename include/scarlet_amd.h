@@ -750,6 +750,47 @@ int smi_get_footprints_f64(const double *image, int32_t H, int32_t W, double min
 int smi_footprints_fetch(int32_t *bounds, uint8_t *masks, int32_t *peak_start, int32_t *peak_yx,
                          double *peak_flux);
 
+/* The same footprints and peaks for P planes d_images[P][H][W] that live on the device
+ * (footprints.hip), in two steps; the results equal the host calls' exactly.  Device pointers
+ * carry a d_ prefix, everything else is host memory; the work is enqueued on `stream`
+ * (hipStream_t, NULL = default stream).  H*W <= INT32_MAX, P <= 65535.
+ *
+ * smi_footprints_device_label_* labels every plane (4-connected union-find, a label = the
+ * smallest pixel index of its footprint), applies the keep rule and counts, then waits once for
+ * counts[P][3] = per plane (footprints, mask bytes, strict maxima).  counts[..][2] counts the
+ * peaks BEFORE the min_separation filter, which the fetch applies: it is the capacity the peak
+ * arrays need, the number kept is peak_start[n] of the fetch.  d_work: scratch of
+ * smi_footprints_device_work_bytes(P, H, W) bytes (32 bytes per pixel and a little more), which
+ * holds the labels and records until the last fetch; SMI_ERR_INVALID when a plane has more than
+ * 2^31 - 1 mask bytes or maxima.
+ *
+ * smi_footprints_device_fetch_* fills the arrays of smi_footprints_fetch for one `plane` from
+ * d_work, d_images (unchanged since the labelling) and that plane's counts[3]: bounds[n][4],
+ * masks[counts[1]], peak_start[n+1], peak_yx[counts[2]][2], peak_flux[counts[2]]; the peaks are
+ * sorted and filtered by min_separation on the host as smi_get_footprints_* does.  d_scratch:
+ * smi_footprints_device_fetch_bytes(counts) bytes.  It waits for the stream once.
+ *
+ * The two *_bytes functions are arithmetic and need no device; the others return
+ * SMI_ERR_NO_DEVICE without one. */
+int smi_footprints_device_work_bytes(int32_t P, int32_t H, int32_t W, int64_t *bytes);
+int smi_footprints_device_fetch_bytes(const int32_t *counts, int64_t *bytes);
+int smi_footprints_device_label_f32(const float *d_images, int32_t P, int32_t H, int32_t W,
+                                    int32_t min_area, int32_t thresh, void *d_work,
+                                    int64_t work_bytes, int32_t *counts, void *stream);
+int smi_footprints_device_label_f64(const double *d_images, int32_t P, int32_t H, int32_t W,
+                                    int32_t min_area, int32_t thresh, void *d_work,
+                                    int64_t work_bytes, int32_t *counts, void *stream);
+int smi_footprints_device_fetch_f32(const float *d_images, int32_t P, int32_t H, int32_t W,
+                                    int32_t plane, double min_separation, const int32_t *counts,
+                                    const void *d_work, void *d_scratch, int64_t scratch_bytes,
+                                    int32_t *bounds, uint8_t *masks, int32_t *peak_start,
+                                    int32_t *peak_yx, double *peak_flux, void *stream);
+int smi_footprints_device_fetch_f64(const double *d_images, int32_t P, int32_t H, int32_t W,
+                                    int32_t plane, double min_separation, const int32_t *counts,
+                                    const void *d_work, void *d_scratch, int64_t scratch_bytes,
+                                    int32_t *bounds, uint8_t *masks, int32_t *peak_start,
+                                    int32_t *peak_yx, double *peak_flux, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,14 @@ c_f32p = ctypes.POINTER(ctypes.c_float)
 c_f64p = ctypes.POINTER(ctypes.c_double)
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 c_u8p = ctypes.POINTER(ctypes.c_uint8)
+c_i64p = ctypes.POINTER(ctypes.c_int64)
+# smi_footprints_device_label_* / _fetch_*: device pointers and the stream as void *
+_FP_LABEL = [ctypes.c_void_p] + [ctypes.c_int32] * 5 + [ctypes.c_void_p, ctypes.c_int64, c_i32p,
+                                                        ctypes.c_void_p]
+_FP_FETCH = ([ctypes.c_void_p] + [ctypes.c_int32] * 4 + [ctypes.c_double, c_i32p, ctypes.c_void_p,
+                                                         ctypes.c_void_p, ctypes.c_int64, c_i32p,
+                                                         c_u8p, c_i32p, c_i32p, c_f64p,
+                                                         ctypes.c_void_p])
 
 
 class BatchDesc(ctypes.Structure):
@@ -286,6 +294,13 @@ SYMBOLS = {
          ctypes.c_int32, c_i32p],
     ),
     "smi_footprints_fetch": (ctypes.c_int, [c_i32p, c_u8p, c_i32p, c_i32p, c_f64p]),
+    "smi_footprints_device_work_bytes": (
+        ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_i64p]),
+    "smi_footprints_device_fetch_bytes": (ctypes.c_int, [c_i32p, c_i64p]),
+    "smi_footprints_device_label_f32": (ctypes.c_int, _FP_LABEL),
+    "smi_footprints_device_label_f64": (ctypes.c_int, _FP_LABEL),
+    "smi_footprints_device_fetch_f32": (ctypes.c_int, _FP_FETCH),
+    "smi_footprints_device_fetch_f64": (ctypes.c_int, _FP_FETCH),
 }
 
 _lib = None

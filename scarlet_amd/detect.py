@@ -1,8 +1,10 @@
 """Source detection on starlet coefficients (reference scarlet/detect.py).
 
 The wavelet stages -- the coadd of the bands, the starlet transform and the multiresolution
-support -- run on the GPU in one device-resident chain; footprints and peaks are found on the
-host (``detect_pybind11``), and the structures that connect them across scales are plain
+support -- run on the GPU in one device-resident chain.  Footprints and peaks of coefficients
+that stay on the device (``get_detect_wavelets(..., device=True)``) are found there too
+(``detect_pybind11.get_footprints_device``); host arrays take the host code
+(``get_footprints``).  The structures that connect the footprints across scales are plain
 Python over ``Box``es, as in the reference.  ``QuadTreeRegion.query`` returns a ``set`` as the
 reference does, so the order in which ``get_peaks`` lists the peaks is the reference's.
 Display helpers (``draw_*``, matplotlib) are not part of this package.
@@ -11,7 +13,7 @@ Display helpers (``draw_*``, matplotlib) are not part of this package.
 import numpy as np
 
 from .bbox import Box, overlapped_slices
-from .detect_pybind11 import get_footprints
+from .detect_pybind11 import get_footprints, get_footprints_device, _is_device_tensor
 from . import wavelet
 
 
@@ -168,10 +170,12 @@ def get_wavelets(images, variance, scales=3):
     return Mw.transpose(0, 1).contiguous().cpu().numpy()
 
 
-def get_detect_wavelets(images, variance, scales=3):
+def get_detect_wavelets(images, variance, scales=3, device=False):
     """Significant starlet coefficients ``(scales+1, Ny, Nx)`` of the coadd
     ``np.sum(images, axis=0)``, with ``sigma = median(sqrt(variance))``: coadd, transform and
-    support on the device, one copy of the result to the host."""
+    support on the device, one copy of the result to the host.  ``device=True`` returns the
+    float64 device tensor instead, without the copy (``get_blend_trees``,
+    ``get_blend_structures`` and ``get_peaks`` accept it)."""
     images = np.asarray(images)
     sigma = np.median(np.sqrt(variance))
     scales = wavelet._checked_scales(images.shape, scales)
@@ -180,10 +184,12 @@ def get_detect_wavelets(images, variance, scales=3):
     dtype = np.float32 if images.dtype == np.float32 else np.float64
     s0, t0 = wavelet.initial_sigma(dtype, scales + 1, sigma, 3)
     _, Mw, _ = wavelet.support_device(d_coeffs, s0[None], t0[None], 3, 1e-1, 20)
-    return Mw[:, 0].cpu().numpy()
+    return Mw[:, 0] if device else Mw[:, 0].cpu().numpy()
 
 
 def _scale_footprints(detect):
+    if _is_device_tensor(detect):  # every scale but the last in one labelling call
+        return get_footprints_device(detect[:-1], min_separation=0, min_area=4, thresh=0)
     return [get_footprints(plane, min_separation=0, min_area=4, thresh=0) for plane in detect[:-1]]
 
 
@@ -212,11 +218,13 @@ def get_blend_structures(detect):
 def get_peaks(detect=None, images=None, variance=None, bbox=None, scales=3):
     """``(y, x)`` of the peaks of the second wavelet scale, in the order of the middle tree's
     query.  Without ``detect``, ``images``, ``variance`` and ``bbox`` are needed and the
-    detection coefficients come from ``get_detect_wavelets(images, variance, scales=3)``."""
+    detection coefficients come from ``get_detect_wavelets(images, variance, scales=3)`` and
+    stay on the device, footprints and peaks included.  ``detect`` may be a host array or a
+    device tensor."""
     if detect is None:
         if images is None or variance is None or bbox is None:
             raise ValueError("Must pass either 'detect' or 'images' and 'variance' and 'bbox'")
-        detect = get_detect_wavelets(images, variance, scales=3)
-    bbox = Box(detect.shape[1:]) if bbox is None else bbox[1:]
+        detect = get_detect_wavelets(images, variance, scales=3, device=True)
+    bbox = Box(tuple(detect.shape[1:])) if bbox is None else bbox[1:]
     _, tree = get_blend_structures(detect)
     return [(peak.y, peak.x) for box in tree.query(bbox) for peak in box.footprint.peaks]

@@ -1,8 +1,11 @@
 """Footprints and peaks: drop-in for the reference's compiled ``scarlet.detect_pybind11``.
 
 ``get_footprints`` runs in the library (``csrc/detect.cpp``, host code: a labelling pass
-with a branch at every pixel); ``get_connected_pixels`` and ``get_peaks`` are the
-single-footprint helpers of the same module, here in NumPy.
+with a branch at every pixel); ``get_footprints_device`` gives the same answer for planes
+that are on the GPU already (``csrc/footprints.hip``: union-find labelling, records, masks
+and peaks as kernels, only the footprints' records cross to the host);
+``get_connected_pixels`` and ``get_peaks`` are the single-footprint helpers of the same
+module, here in NumPy.
 
 Where the reference's behaviour is undefined, this module defines it: equal-flux peaks keep
 raster order (a stable sort), ``min_separation > 0`` keeps peaks brightest first and drops
@@ -85,9 +88,14 @@ def get_footprints(image, min_separation, min_area, thresh):
         _lib.ptr(bounds, ctypes.c_int32), _lib.ptr(masks, ctypes.c_uint8),
         _lib.ptr(start, ctypes.c_int32), _lib.ptr(yx, ctypes.c_int32),
         _lib.ptr(flux, ctypes.c_double)))
+    return _footprint_objects(bounds, masks, start, yx, flux)
+
+
+def _footprint_objects(bounds, masks, start, yx, flux):
+    """``Footprint``s from the arrays of ``smi_footprints_fetch``"""
     footprints = []
     offset = 0
-    for f in range(n):
+    for f in range(len(bounds)):
         y0, y1, x0, x1 = (int(v) for v in bounds[f])
         h, w = y1 - y0 + 1, x1 - x0 + 1
         mask = masks[offset:offset + h * w].reshape(h, w).astype(bool)
@@ -95,6 +103,97 @@ def get_footprints(image, min_separation, min_area, thresh):
         peaks = [Peak(yx[k, 0], yx[k, 1], flux[k]) for k in range(start[f], start[f + 1])]
         footprints.append(Footprint(mask, peaks, bounds[f]))
     return footprints
+
+
+def _is_device_tensor(x):
+    """True for a torch tensor on a GPU, without importing torch for anything else"""
+    mod = type(x).__module__
+    return (mod == "torch" or mod.startswith("torch.")) and hasattr(x, "data_ptr") \
+        and getattr(x, "is_cuda", False)
+
+
+def label_device(d_image, min_area, thresh):
+    """First step of :func:`get_footprints_device` on a contiguous ``(P, H, W)`` float32 /
+    float64 device tensor: one labelling call for all planes.  Returns ``(counts, work)``:
+    the ``(P, 3)`` int32 array (footprints, mask bytes, strict maxima) of every plane and the
+    device buffer :func:`fetch_device` reads."""
+    import torch
+
+    lib = _lib.load()
+    P, H, W = d_image.shape
+    nbytes = ctypes.c_int64(0)
+    _lib.check(lib.smi_footprints_device_work_bytes(P, H, W, ctypes.byref(nbytes)))
+    work = torch.empty(nbytes.value, dtype=torch.uint8, device=d_image.device)
+    counts = np.zeros((P, 3), dtype=np.int32)
+    fn = lib.smi_footprints_device_label_f32 if d_image.dtype == torch.float32 else \
+        lib.smi_footprints_device_label_f64
+    stream = ctypes.c_void_p(torch.cuda.current_stream(d_image.device).cuda_stream)
+    with torch.cuda.device(d_image.device):
+        _lib.check(fn(ctypes.c_void_p(d_image.data_ptr()), P, H, W, int(min_area), int(thresh),
+                      ctypes.c_void_p(work.data_ptr()), nbytes.value,
+                      _lib.ptr(counts, ctypes.c_int32), stream))
+    return counts, work
+
+
+def fetch_device(d_image, plane, min_separation, counts, work):
+    """Second step: the arrays ``(bounds, masks, peak_start, peak_yx, peak_flux)`` of one plane,
+    in the layout of ``smi_footprints_fetch``."""
+    import torch
+
+    lib = _lib.load()
+    P, H, W = d_image.shape
+    c = np.ascontiguousarray(counts[plane], dtype=np.int32)
+    n, n_mask, n_peaks = (int(v) for v in c)
+    bounds = np.zeros((n, 4), dtype=np.int32)
+    masks = np.zeros(n_mask, dtype=np.uint8)
+    start = np.zeros(n + 1, dtype=np.int32)
+    yx = np.zeros((n_peaks, 2), dtype=np.int32)
+    flux = np.zeros(n_peaks, dtype=np.float64)
+    if n:
+        nbytes = ctypes.c_int64(0)
+        _lib.check(lib.smi_footprints_device_fetch_bytes(_lib.ptr(c, ctypes.c_int32),
+                                                         ctypes.byref(nbytes)))
+        scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=d_image.device)
+        fn = lib.smi_footprints_device_fetch_f32 if d_image.dtype == torch.float32 else \
+            lib.smi_footprints_device_fetch_f64
+        stream = ctypes.c_void_p(torch.cuda.current_stream(d_image.device).cuda_stream)
+        with torch.cuda.device(d_image.device):
+            _lib.check(fn(ctypes.c_void_p(d_image.data_ptr()), P, H, W, int(plane),
+                          float(min_separation), _lib.ptr(c, ctypes.c_int32),
+                          ctypes.c_void_p(work.data_ptr()), ctypes.c_void_p(scratch.data_ptr()),
+                          nbytes.value, _lib.ptr(bounds, ctypes.c_int32),
+                          _lib.ptr(masks, ctypes.c_uint8), _lib.ptr(start, ctypes.c_int32),
+                          _lib.ptr(yx, ctypes.c_int32), _lib.ptr(flux, ctypes.c_double), stream))
+    kept = int(start[n])  # min_separation may have dropped some of the maxima counted
+    return bounds, masks, start, yx[:kept], flux[:kept]
+
+
+def get_footprints_device(d_image, min_separation, min_area, thresh):
+    """:func:`get_footprints` of a 2-D image, or of every plane of a 3-D stack, that lives on
+    the GPU: a float32 / float64 torch device tensor (made contiguous if it is not).  Labels,
+    bounds, masks and peaks are found on the device (``csrc/footprints.hip``); only the records
+    of the footprints come back.  Returns the list of ``Footprint``s of a 2-D image, a list of
+    such lists for a 3-D stack; all planes go through one labelling call.  The results equal
+    :func:`get_footprints` of the same pixels exactly.  Host arrays: :func:`get_footprints`."""
+    if not _is_device_tensor(d_image):
+        raise TypeError("get_footprints_device: a torch device tensor is needed, got %s "
+                        "(host arrays go through get_footprints)" % type(d_image).__name__)
+    if d_image.dim() not in (2, 3):
+        raise ValueError("get_footprints_device: a 2-D image or a 3-D stack is needed, got "
+                         "shape %s" % (tuple(d_image.shape),))
+    import torch
+
+    if d_image.dtype not in (torch.float32, torch.float64):
+        raise TypeError("get_footprints_device: float32 or float64 is needed, got %s"
+                        % d_image.dtype)
+    planes = (d_image if d_image.dim() == 3 else d_image[None]).contiguous()
+    if planes.numel() == 0:
+        raise ValueError("get_footprints_device: empty image of shape %s"
+                         % (tuple(d_image.shape),))
+    counts, work = label_device(planes, min_area, thresh)
+    found = [_footprint_objects(*fetch_device(planes, k, min_separation, counts, work))
+             for k in range(planes.shape[0])]
+    return found if d_image.dim() == 3 else found[0]
 
 
 def get_connected_pixels(i, j, image, unchecked, footprint, bounds, thresh=0):

@@ -1,13 +1,21 @@
 """Time the detection chain get_detect_wavelets + get_blend_structures on synthetic frames.
 
-Device stages (coadd, starlet transform, multiresolution support) with HIP events on the
-current stream, after a warm-up of every shape; then separately the device-to-host copy of the
-detection coefficients, the host footprints / structures, and the NumPy equivalent of the
-device stages (the reference's algorithm: float64 transform, masked standard deviations) on
-one core.  The bytes model beside the times counts the float64 plane streams each stage must
-move at least (unmeasured estimate, compared with the ~6.3 TB/s a float4 copy reaches).
+Device stages (coadd, starlet transform, multiresolution support) with HIP events on the current
+stream, after a warm-up of every shape; then separately the device-to-host copy of the detection
+coefficients, the host footprints / structures, and the NumPy equivalent of the device stages (the
+reference's algorithm: float64 transform, masked standard deviations) on one core; and the
+footprint stage both ways from coefficients that are on the device: the device-to-host copy plus
+the host ``get_footprints`` of three planes (the route of a host array) against
+``get_footprints_device`` (labelling call with HIP events for one and three planes, the library's
+fetch, the Python objects), and the quad trees / structures that remain on the host either way.
+``--golden`` does the footprint part on the recorded coefficients of the tutorial frame
+(tests/golden/detect.npz). A tree without ``get_footprints_device`` (an older commit under
+comparison) reports the host route only. The bytes model beside the times counts the float64 plane
+streams each stage must move at least (unmeasured estimate, compared with the ~6.3 TB/s a float4
+copy reaches).
 
-    python tools/detect_time.py [--sizes 2048 4096] [--bands 5] [--scales 5] [--out FILE]
+    python tools/detect_time.py [--sizes 2048 4096] [--bands 5] [--scales 5] [--golden]
+                                [--out FILE]
 """
 import argparse
 import json
@@ -79,6 +87,87 @@ def numpy_detect(images, variance, scales):
     return M * w
 
 
+def _median_ms(fn, reps):
+    """median wall time of fn() in ms between device synchronisations, after one warm-up"""
+    import torch
+
+    times = []
+    for rep in range(reps + 1):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        if rep:
+            times.append((time.perf_counter() - t) * 1e3)
+    return float(np.median(times)), float(np.min(times)), float(np.max(times))
+
+
+def footprint_stages(d_planes, reps):
+    """"coefficients on device -> list of Footprints" of the (3, H, W) device tensor both ways,
+    and where the rest of the host time goes.  Times in ms: median, or (median, min, max)."""
+    import torch
+    from scarlet_amd import Box, detect, detect_pybind11 as dp
+
+    d_planes = d_planes.contiguous()
+    out = {"planes": int(d_planes.shape[0]), "shape": list(d_planes.shape[1:])}
+
+    def host_route():
+        host = d_planes.cpu().numpy()
+        return [dp.get_footprints(p, 0, 4, 0) for p in host]
+
+    out["host_route_ms"] = _median_ms(host_route, reps)
+    out["d2h_ms"] = _median_ms(lambda: d_planes.cpu().numpy(), reps)[0]
+    footprints = host_route()
+    out["n_footprints"] = [len(f) for f in footprints]
+    if hasattr(dp, "get_footprints_device"):
+        out["device_route_ms"] = _median_ms(lambda: dp.get_footprints_device(d_planes, 0, 4, 0),
+                                            reps)
+        for name, planes in (("label_1_plane_ms", d_planes[:1]), ("label_3_planes_ms", d_planes)):
+            ev = []
+            for rep in range(reps + 1):
+                a, b = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+                a.record()
+                counts, work = dp.label_device(planes, 4, 0)
+                b.record()
+                torch.cuda.synchronize()
+                if rep:
+                    ev.append(a.elapsed_time(b))
+            out[name] = float(np.median(ev))
+        counts, work = dp.label_device(d_planes, 4, 0)
+        fetch = lambda: [dp.fetch_device(d_planes, k, 0, counts, work)  # noqa: E731
+                         for k in range(len(d_planes))]
+        out["fetch_ms"] = _median_ms(fetch, reps)[0]
+        arrays = fetch()
+        t = time.perf_counter()
+        for rep in range(reps):
+            got = [dp._footprint_objects(*a) for a in arrays]
+        out["python_objects_ms"] = (time.perf_counter() - t) * 1e3 / reps
+        pk = lambda fp: [(p.y, p.x, p.flux) for p in fp.peaks]  # noqa: E731
+        same = all(tuple(a.bounds) == tuple(b.bounds) and np.array_equal(a.footprint, b.footprint)
+                   and pk(a) == pk(b)
+                   for fa, fb in zip(got, footprints) for a, b in zip(fa, fb))
+        out["device_equals_host"] = bool(same and [len(f) for f in got] == out["n_footprints"])
+    shape = tuple(d_planes.shape[1:])
+    t = time.perf_counter()
+    for rep in range(reps):
+        low = detect.QuadTreeRegion(Box(shape), capacity=10).add_footprints(footprints[0])
+        middle = detect.QuadTreeRegion(Box(shape), capacity=10).add_footprints(footprints[1])
+        [detect.SingleScaleStructure(2, fp).add_scale_tree(0, low).add_scale_tree(1, middle)
+         for fp in footprints[2]]
+    out["trees_and_structures_ms"] = (time.perf_counter() - t) * 1e3 / reps
+    return out
+
+
+def run_golden(reps):
+    import torch
+
+    g = np.load(os.path.join(ROOT, "tests", "golden", "detect.npz"))
+    d = torch.from_numpy(np.ascontiguousarray(g["detect_s3"][:3])).to("cuda")
+    out = dict(size="tutorial", footprints=footprint_stages(d, reps))
+    print(json.dumps(out), flush=True)
+    return out
+
+
 def run(n, bands, scales, reps, numpy_ref):
     import torch
     from scarlet_amd import detect, wavelet
@@ -107,6 +196,7 @@ def run(n, bands, scales, reps, numpy_ref):
         if rep:
             for k, name in enumerate(stages):
                 stages[name].append(e[k].elapsed_time(e[k + 1]))
+        d_first = Mw[:3, 0].contiguous()
         del coeffs, Mw
     med = {k: float(np.median(v)) for k, v in stages.items()}
     # bytes each stage must move at least (float64 planes of n*n): coadd reads the float32 bands
@@ -123,7 +213,8 @@ def run(n, bands, scales, reps, numpy_ref):
     out = dict(size=n, bands=bands, scales=scales, reps=reps, support_iterations=int(iters[0]),
                device_ms=med, bytes=model,
                model_ms_at_copy_bw={k: v / COPY_BW * 1e3 for k, v in model.items() if k != "d2h"},
-               host_footprints_s=host_fp, n_structures=len(structures))
+               host_footprints_s=host_fp, n_structures=len(structures),
+               footprints=footprint_stages(d_first, reps))
     dev_total = (med["coadd"] + med["transform"] + med["support"] + med["d2h"]) / 1e3
     if numpy_ref:
         t = time.perf_counter()
@@ -143,6 +234,8 @@ def main():
     ap.add_argument("--scales", type=int, default=5)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-numpy", action="store_true")
+    ap.add_argument("--golden", action="store_true",
+                    help="also the footprint stages on the tutorial frame's coefficients")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -150,6 +243,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("detect_time.py measures the GPU: no GPU visible")
     results = [run(n, a.bands, a.scales, a.reps, not a.no_numpy) for n in a.sizes]
+    if a.golden:
+        results.append(run_golden(max(a.reps, 20)))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
