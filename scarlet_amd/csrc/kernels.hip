@@ -56,6 +56,17 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 // np.maximum semantics: a NaN in the data propagates (fmaxf would drop it)
 __device__ __forceinline__ float max_nan(float a, float b) { return a != a ? a : fmaxf(a, b); }
+// the bare hardware maximum (IEEE maxNum: a NaN operand is dropped): what fmaxf returns, without
+// the canonicalising v_max(x, x) the compiler puts in front of it for values out of memory.
+// That instruction only quiets signalling NaNs (denormals are kept in this mode), and v_max_f32
+// itself returns the other operand for any NaN: for non-NaN operands the two agree bit for
+// bit, and the caller votes on NaNs before it uses a result.  Inline assembly because no
+// builtin gives the maximum without the canonicalisation; both operands in vector registers
+__device__ __forceinline__ float max_num(float a, float b) {
+    float r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
 
 __device__ __forceinline__ int wave_or(int v) {
 #pragma unroll
@@ -305,14 +316,26 @@ struct Team {
         return t;
     }
     static __device__ __forceinline__ float max(float v) {
+        bool voted;
+        return max_vote(v, false, voted);
+    }
+    // max() together with a vote: `voted` is true when a wavefront of the team passes `vote`
+    // (wave-uniform) -- the result is then meaningless.  No barrier beyond those of max(): the
+    // wavefront that votes hands a NaN to the others in place of its maximum.
+    static __device__ __forceinline__ float max_vote(float v, bool vote, bool &voted) {
         v = wave_max(v);
+        voted = vote;
         if (T == 64) return v;
         __shared__ float red[kWaves];
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = vote ? __builtin_nanf("") : v;
         __syncthreads();
         float t = red[0];
+        voted = t != t;
 #pragma unroll
-        for (int i = 1; i < kWaves; ++i) t = fmaxf(t, red[i]);
+        for (int i = 1; i < kWaves; ++i) {
+            voted = voted || red[i] != red[i];
+            t = fmaxf(t, red[i]);
+        }
         __syncthreads();
         return t;
     }
@@ -1137,6 +1160,15 @@ __device__ __forceinline__ void buf_store(rsrc_t r, uint32_t byte_off, float x) 
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, x), r, byte_off, 0, 0);
 }
 constexpr uint32_t kOutOfRange = 0x80000000u;
+// Byte offset of a lane's first pixel, opaque to the optimiser: a slot's offset is then this
+// register plus a constant, which goes into the instruction's 12-bit immediate (plus one more
+// register per 4 KiB) -- folded into one expression every slot keeps an address register of
+// its own alive from the AMSGrad pass to the final store.
+__device__ __forceinline__ uint32_t lane_byte_offset(int lane) {
+    uint32_t b = (uint32_t)lane * 4u;
+    asm("" : "+v"(b));
+    return b;
+}
 
 __device__ __forceinline__ CompCtx comp_ctx(const BatchView &v, int k, int lane) {
     CompCtx c;
@@ -1561,6 +1593,7 @@ struct UpdState {
     bool fista_prox;  // XP, FISTA: the candidate is z itself
     float alpha, pmax, t_old;
     bool monotonic, fit_center;
+    bool std_chain;  // positivity, centre-on, max normalisation and nothing else after the sweep
     const SweepSlotEntry *slots;
     const SweepPlanDev *ring;  // the plan when it has a ring schedule
     const SweepPlanDev *staged;  // the plan whose ring stream the workgroup holds in LDS ...
@@ -1570,6 +1603,18 @@ struct UpdState {
     float *us, *sed_new;
 };
 
+// The instances that take the one-pixel centre floor, the specialised standard chain and the
+// base-plus-immediate slot addresses: where they cost no register and no scratch (gfx950 ISA
+// table).  FISTA applies the prox once per iteration and its teams need a base register per
+// four slots; the 31^2 teams gain nothing.  The others run the code they always ran.
+constexpr bool update_lean(int npl, int mode, int team) {
+    return mode != 2 && !(team == 256 && npl == 16);
+}
+// byte offset of slot j of a lane
+template <int T, bool LEAN>
+__device__ __forceinline__ uint32_t slot_offset(int lane, uint32_t lane4, int j) {
+    return LEAN ? lane4 + (uint32_t)(T * j) * 4u : (uint32_t)(lane + T * j) * 4u;
+}
 // every box of this size class has more than T * kFull pixels (common.h)
 template <int NPL>
 struct UpdFull {
@@ -1585,9 +1630,11 @@ __device__ __forceinline__ void upd_step(const BatchView &v, const float *G, int
     constexpr bool fista = MODE == 2;
     constexpr bool XP = update_xp(T);
     constexpr int kFull = UpdFull<NPL>::value;
+    constexpr bool LEAN = update_lean(NPL, MODE, T);
     const CompCtx &c = S.c;
     it = v.local_it(c.b, it);
     const int lane = c.lane, k = S.k, N = c.N;
+    const uint32_t lane4 = lane_byte_offset(lane);
     float *us = S.us;
     // (XP: xs holds the gradient, then x, and is dead after this phase)
     float xs_local[NPL], rs_local[NPL];
@@ -1609,13 +1656,13 @@ __device__ __forceinline__ void upd_step(const BatchView &v, const float *G, int
     {
         const rsrc_t r_morph = make_rsrc(c.morph, nbytes);
 #pragma unroll
-        for (int j = 0; j < NPL; ++j) zs[j] = buf_load(r_morph, (uint32_t)(lane + T * j) * 4u);
+        for (int j = 0; j < NPL; ++j) zs[j] = buf_load(r_morph, slot_offset<T, LEAN>(lane, lane4, j));
     }
     float g_sed = 0.f;
     if (c.pre) {
         const rsrc_t r_g = make_rsrc(v.g_morph_buf + c.moff, nbytes);
 #pragma unroll
-        for (int j = 0; j < NPL; ++j) xs[j] = buf_load(r_g, (uint32_t)(lane + T * j) * 4u);
+        for (int j = 0; j < NPL; ++j) xs[j] = buf_load(r_g, slot_offset<T, LEAN>(lane, lane4, j));
         g_sed = lane < c.C ? v.g_sed_buf[(int64_t)k * c.C + lane] : 0.f;
     } else {
         // byte offset of each of the lane's pixels inside a band plane of G (or out of
@@ -1689,12 +1736,12 @@ __device__ __forceinline__ void upd_step(const BatchView &v, const float *G, int
         if constexpr (XP) {
             // (candidate = z - 0 * (z - x) = z: nothing to keep beside z)
 #pragma unroll
-            for (int j = 0; j < NPL; ++j) zs[j] = buf_load(r_m, (uint32_t)(lane + T * j) * 4u);
+            for (int j = 0; j < NPL; ++j) zs[j] = buf_load(r_m, slot_offset<T, LEAN>(lane, lane4, j));
 #pragma unroll
             for (int j = 0; j < NPL; ++j) zs[j] = zs[j] - step * xs[j];
         } else {
 #pragma unroll
-            for (int j = 0; j < NPL; ++j) rs[j] = buf_load(r_m, (uint32_t)(lane + T * j) * 4u);
+            for (int j = 0; j < NPL; ++j) rs[j] = buf_load(r_m, slot_offset<T, LEAN>(lane, lane4, j));
 #pragma unroll
             for (int j = 0; j < NPL; ++j) {
                 xs[j] = rs[j] - step * xs[j];
@@ -1713,7 +1760,7 @@ __device__ __forceinline__ void upd_step(const BatchView &v, const float *G, int
         float cm[CH], cv[CH], cvh[CH];
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
-            const uint32_t off = (uint32_t)(lane + T * u) * 4u;
+            const uint32_t off = slot_offset<T, LEAN>(lane, lane4, u);
             cm[u] = buf_load(r_m, off);
             cv[u] = buf_load(r_v, off);
             cvh[u] = buf_load(r_vh, off);
@@ -1725,7 +1772,7 @@ __device__ __forceinline__ void upd_step(const BatchView &v, const float *G, int
             for (int u = 0; u < CH; ++u) {
                 nm[u] = nv[u] = nvh[u] = 0.f;
                 if (j0 + CH + u < NPL) {
-                    const uint32_t off = (uint32_t)(lane + T * (j0 + CH + u)) * 4u;
+                    const uint32_t off = slot_offset<T, LEAN>(lane, lane4, (j0 + CH + u));
                     nm[u] = buf_load(r_m, off);
                     nv[u] = buf_load(r_v, off);
                     nvh[u] = buf_load(r_vh, off);
@@ -1735,7 +1782,7 @@ __device__ __forceinline__ void upd_step(const BatchView &v, const float *G, int
             for (int u = 0; u < CH; ++u) {
                 const int j = j0 + u;
                 if (j < NPL) {
-                    const uint32_t off = (uint32_t)(lane + T * j) * 4u;
+                    const uint32_t off = slot_offset<T, LEAN>(lane, lane4, j);
                     const float g = xs[j];
                     const float m = (1.f - b1) * g + b1 * cm[u];
                     const float vv = (1.f - b2) * g * g + b2 * cv[u];
@@ -1791,6 +1838,11 @@ __device__ __forceinline__ void upd_step(const BatchView &v, const float *G, int
         S.n_slots = v.plans[plan_id].n_slots;
         S.ring = v.plans[plan_id].ring ? &v.plans[plan_id] : nullptr;
     }
+    constexpr int kChainLinks = SMI_PROX_SYMMETRY | SMI_PROX_POSITIVE | SMI_PROX_CENTER_ON |
+                                SMI_PROX_NORM_MAX | SMI_PROX_NORM_SUM | SMI_PROX_L1 | SMI_PROX_L0 |
+                                SMI_PROX_BG_THRESH;
+    S.std_chain = LEAN && (flags & kChainLinks) ==
+                              (SMI_PROX_POSITIVE | SMI_PROX_CENTER_ON | SMI_PROX_NORM_MAX);
     S.one_minus_g = 1.f - v.c_min_grad[k];
     S.ctr = (c.h / 2) * c.w + (c.w / 2);
     S.lthresh = v.c_lthresh[k] * ((flags & SMI_PROX_L_RELATIVE) ? alpha / pmax : 1.f);
@@ -1800,10 +1852,12 @@ __device__ __forceinline__ void upd_step(const BatchView &v, const float *G, int
 }
 
 // candidate of a proximal sub-iteration into the LDS image
-template <int NPL, int T>
+template <int NPL, int MODE, int T>
 __device__ __forceinline__ void upd_prox_begin(const BatchView &v, UpdState<NPL, update_xp(T)> &S) {
+    constexpr bool LEAN = update_lean(NPL, MODE, T);
     const int lane = S.c.lane;
     if constexpr (update_xp(T)) {
+        const uint32_t lane4 = lane_byte_offset(lane);
         if (S.fista_prox) {
 #pragma unroll
             for (int j = 0; j < NPL; ++j) S.us[lane + T * j] = S.zs[j];
@@ -1819,7 +1873,7 @@ __device__ __forceinline__ void upd_prox_begin(const BatchView &v, UpdState<NPL,
         float cx[CH], cp[CH];
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
-            const uint32_t off = (uint32_t)(lane + T * u) * 4u;
+            const uint32_t off = slot_offset<T, LEAN>(lane, lane4, u);
             cx[u] = buf_load(r_x, off);
             cp[u] = buf_load(r_p, off);
         }
@@ -1830,7 +1884,7 @@ __device__ __forceinline__ void upd_prox_begin(const BatchView &v, UpdState<NPL,
             for (int u = 0; u < CH; ++u) {
                 nx[u] = np[u] = 0.f;
                 if (j0 + CH + u < NPL) {
-                    const uint32_t off = (uint32_t)(lane + T * (j0 + CH + u)) * 4u;
+                    const uint32_t off = slot_offset<T, LEAN>(lane, lane4, (j0 + CH + u));
                     nx[u] = buf_load(r_x, off);
                     np[u] = buf_load(r_p, off);
                 }
@@ -1875,19 +1929,75 @@ __device__ __forceinline__ bool upd_prox_end(const BatchView &v, float e2,
     constexpr bool LITE = MODE != 0;
     constexpr int kFull = UpdFull<NPL>::value;
     const CompCtx &c = S.c;
-    const int lane = c.lane, N = c.N, flags = S.flags, ctr = S.ctr;
+    constexpr bool LEAN = update_lean(NPL, MODE, T);
+    const int lane = c.lane, flags = S.flags, ctr = S.ctr;
+    // (LEAN, an opaque copy: the `i < N` of the tail slots are one comparison each where they
+    // are used; hoisted out of the sub-iteration loop they are 2 * (NPL - kFull) scalar
+    // registers that do not fit and come back through v_readlane)
+    int N = c.N;
+    if constexpr (LEAN) asm volatile("" : "+s"(N));
     const float pfloor = S.pfloor, cfloor = S.cfloor;
     float *us = S.us;
-    chain_symmetry_threshold<T>(us, c, LITE ? flags : (flags & ~SMI_PROX_BG_THRESH), S.lthresh,
-                                S.sed_new, S.bg_level,
-                                (flags & SMI_PROX_SYMMETRY) ? v.c_sym_strength[S.k] : 1.f);
+    // (the standard chain has none of these links)
+    if (!S.std_chain)
+        chain_symmetry_threshold<T>(us, c, LITE ? flags : (flags & ~SMI_PROX_BG_THRESH), S.lthresh,
+                                    S.sed_new, S.bg_level,
+                                    (flags & SMI_PROX_SYMMETRY) ? v.c_sym_strength[S.k] : 1.f);
+    // LEAN: CenterOnConstraint acts on one pixel: the lane that owns it floors it in the image,
+    // once, and the loops below know nothing of it (positivity first, as in the chain; applying
+    // positivity to that pixel again is the identity, and a NaN stays a NaN).  No fence: pixel i
+    // belongs to lane i mod T in every loop of this function (i = lane + T * j), so only this
+    // lane reads the pixel again, and the LDS operations of a lane stay in order.  A change of
+    // that mapping needs a team_fence<T>() here.
+    if (LEAN && (flags & SMI_PROX_CENTER_ON) && lane == (ctr & (T - 1))) {
+        float u = us[ctr];
+        if (flags & SMI_PROX_POSITIVE) u = max_nan(u, pfloor);
+        us[ctr] = max_nan(u, cfloor);
+    }
+    if (LEAN && S.std_chain) {
+        // positivity, maximum normalisation.  max_i max(u_i, floor) = max(floor, max_i u_i), so
+        // the first pass needs one maximum per pixel and no floor, the second applies the floor
+        // once; v_max drops a NaN where np.maximum keeps it, so the pixels vote, and a team
+        // that saw one takes the exact code below for this sub-iteration.
+        // (the vote reads the tail slots beyond the box too: upd_prox_begin writes them from
+        // z = x = 0, r = 0, so they are zeros and never vote; a NaN there would only cost the
+        // exact code, not a wrong result)
+        float mx = -INFINITY;
+        uint64_t nan = 0;
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) {
+            const int i = lane + T * j;
+            const float u = us[i];
+            nan |= __builtin_amdgcn_ballot_w64(u != u);
+            mx = max_num(mx, (j < kFull || i < N) ? u : -INFINITY);
+        }
+        bool any_nan;
+        const float div = Team<T>::max_vote(max_num(mx, pfloor), nan != 0, any_nan);
+        if (!any_nan) {
+            const float rdiv = 1.f / div;
+            float d2 = 0.f, z2 = 0.f;
+#pragma unroll
+            for (int j = 0; j < NPL; ++j) {
+                const int i = lane + T * j;
+                float u = max_num(us[i], pfloor);
+                u = u == div ? 1.f : u * rdiv;
+                if (!(j < kFull || i < N)) u = 0.f;
+                d2 += (u - S.zs[j]) * (u - S.zs[j]);
+                z2 += S.zs[j] * S.zs[j];
+                S.zs[j] = u;
+            }
+            d2 = Team<T>::sum(d2);
+            z2 = Team<T>::sum(z2);
+            return d2 <= e2 * z2;
+        }
+    }
     float mx = -INFINITY, sm = 0.f;
 #pragma unroll
     for (int j = 0; j < NPL; ++j) {
         const int i = lane + T * j;
         float u = us[i];
         if (flags & SMI_PROX_POSITIVE) u = max_nan(u, pfloor);
-        if ((flags & SMI_PROX_CENTER_ON) && i == ctr) u = max_nan(u, cfloor);
+        if (!LEAN && (flags & SMI_PROX_CENTER_ON) && i == ctr) u = max_nan(u, cfloor);
         mx = (j < kFull || i < N) ? fmaxf(mx, u) : mx;
         sm += (j < kFull || i < N) ? u : 0.f;
     }
@@ -1904,7 +2014,7 @@ __device__ __forceinline__ bool upd_prox_end(const BatchView &v, float e2,
         const int i = lane + T * j;
         float u = us[i];  // second read instead of NPL more registers
         if (flags & SMI_PROX_POSITIVE) u = max_nan(u, pfloor);
-        if ((flags & SMI_PROX_CENTER_ON) && i == ctr) u = max_nan(u, cfloor);
+        if (!LEAN && (flags & SMI_PROX_CENTER_ON) && i == ctr) u = max_nan(u, cfloor);
         if (flags & (SMI_PROX_NORM_MAX | SMI_PROX_NORM_SUM))
             u = (u == div && (flags & SMI_PROX_NORM_MAX)) ? 1.f : u * rdiv;
         if (!(j < kFull || i < N)) u = 0.f;  // slots beyond the box stay zero
@@ -1921,8 +2031,10 @@ __device__ __forceinline__ bool upd_prox_end(const BatchView &v, float e2,
 template <int NPL, int MODE, int T>
 __device__ __forceinline__ void upd_store(const BatchView &v, UpdState<NPL, update_xp(T)> &S) {
     constexpr bool fista = MODE == 2;
+    constexpr bool LEAN = update_lean(NPL, MODE, T);
     const CompCtx &c = S.c;
     const int lane = c.lane;
+    const uint32_t lane4 = lane_byte_offset(lane);
     const uint32_t nbytes = (uint32_t)c.N * 4u;
     float omega = 0.f;
     if (fista) {
@@ -1936,15 +2048,15 @@ __device__ __forceinline__ void upd_store(const BatchView &v, UpdState<NPL, upda
         const rsrc_t r_m = make_rsrc(v.m_morph + c.moff, nbytes);
         float xo[NPL];
 #pragma unroll
-        for (int j = 0; j < NPL; ++j) xo[j] = buf_load(r_out, (uint32_t)(lane + T * j) * 4u);
+        for (int j = 0; j < NPL; ++j) xo[j] = buf_load(r_out, slot_offset<T, LEAN>(lane, lane4, j));
 #pragma unroll
         for (int j = 0; j < NPL; ++j)
-            buf_store(r_m, (uint32_t)(lane + T * j) * 4u, xo[j] + omega * (S.zs[j] - xo[j]));
+            buf_store(r_m, slot_offset<T, LEAN>(lane, lane4, j), xo[j] + omega * (S.zs[j] - xo[j]));
     }
     int bad = S.bad;
 #pragma unroll
     for (int j = 0; j < NPL; ++j) {
-        buf_store(r_out, (uint32_t)(lane + T * j) * 4u, S.zs[j]);
+        buf_store(r_out, slot_offset<T, LEAN>(lane, lane4, j), S.zs[j]);
         bad |= !isfinite(S.zs[j]);
     }
     if (Team<T>::any(bad) && lane == 0) atomicExch(&v.state[c.b], v.fail_code);  // model.py:153-165
@@ -1972,7 +2084,7 @@ __device__ __forceinline__ void update_component(const BatchView &v, const float
     upd_step<NPL, MODE, T, EXT>(v, G, it, e2, prox_max_iter, S);
     team_fence<T>();  // the offsets parked in `us` have been consumed
     for (int tau = 0; tau < prox_max_iter; ++tau) {
-        upd_prox_begin<NPL, T>(v, S);
+        upd_prox_begin<NPL, MODE, T>(v, S);
         team_fence<T>();
         upd_prox_plan(v, S);
         if (S.monotonic) {
