@@ -95,6 +95,55 @@ int smi_apply_filter_f64(const double *image, int32_t H, int32_t W,
                          const int32_t *x_start, const int32_t *x_end,
                          double *result);
 
+/* scarlet/lite/measure.py:39-91 (weight_sources) for a catalogue of blends that share the
+ * number of bands C and the (kh, kw) difference-kernel stamp: per blend the frame-clipped
+ * scene, per source its own model, both convolved with the tap loop of apply_filter above
+ * and clamped at 0; then out = min(model / total, 1) (0 where total == 0) * images on the
+ * part of every source's grown box that lies in the frame.  Host buffers in, host buffer out;
+ * all coordinates relative to the frame's corner; offsets and sizes count elements.
+ *
+ *   images[blend.image_off .. + C h w]   the (masked) images the ratio multiplies
+ *   stamps[blend.stamp_off .. + C kh kw] the blend's stamp, one per band
+ *   seds[component.sed_off .. + C], morphs[component.morph_off + y stride + x]
+ *   out[source.out_off .. + C h w]       the source's result, [C][h][w]
+ *
+ * A blend's components [comp0, comp0 + n_comp) make its scene and must lie inside its frame
+ * (the caller clips them: y0 / x0 / h / w describe the clipped rectangle, morph_off its first
+ * pixel, stride the row length of the morphology); a source's components make its model
+ * and may overhang.  The plan is validated before anything is launched: a bad one returns
+ * SMI_ERR_INVALID.  Bit-identical to the per-band apply_filter chain of the reference. */
+typedef struct smi_reweight_blend {
+    int32_t h, w;           /* frame */
+    int32_t comp0, n_comp;  /* components of the scene, in the order they are added */
+    int64_t image_off, stamp_off;
+} smi_reweight_blend;
+typedef struct smi_reweight_source {
+    int32_t blend;
+    int32_t comp0, n_comp;  /* components of the source, in the order they are added */
+    int32_t y0, x0, h, w;   /* output rectangle, inside the frame, not empty */
+    int32_t reserved;
+    int64_t out_off;
+} smi_reweight_source;
+typedef struct smi_reweight_component {
+    int32_t y0, x0, h, w;   /* rectangle the component covers */
+    int32_t stride, reserved;
+    int64_t sed_off, morph_off;
+} smi_reweight_component;
+int smi_reweight_f32(int32_t device, int32_t C, int32_t kh, int32_t kw, int32_t n_blends,
+                     const smi_reweight_blend *blends, int32_t n_sources,
+                     const smi_reweight_source *sources, int32_t n_components,
+                     const smi_reweight_component *components, const float *images,
+                     int64_t n_image, const float *stamps, int64_t n_stamp, const float *seds,
+                     int64_t n_sed, const float *morphs, int64_t n_morph, float *out,
+                     int64_t n_out);
+int smi_reweight_f64(int32_t device, int32_t C, int32_t kh, int32_t kw, int32_t n_blends,
+                     const smi_reweight_blend *blends, int32_t n_sources,
+                     const smi_reweight_source *sources, int32_t n_components,
+                     const smi_reweight_component *components, const double *images,
+                     int64_t n_image, const double *stamps, int64_t n_stamp, const double *seds,
+                     int64_t n_sed, const double *morphs, int64_t n_morph, double *out,
+                     int64_t n_out);
+
 /* get_valid_monotonic_pixels / linear_interpolate_invalid_pixels
  * (operators_pybind11.cc:61-232, float32 and float64 overload sets; callers
  * operator.py:155-176).  Row-major (rows, cols) images; `unchecked` / `orphans` are the

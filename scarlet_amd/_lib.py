@@ -54,6 +54,14 @@ _FP_FETCH = ([ctypes.c_void_p] + [ctypes.c_int32] * 4 + [ctypes.c_double, c_i32p
                                                          ctypes.c_void_p])
 
 
+def _REWEIGHT(fp):
+    """smi_reweight_*: device, C, kh, kw, then (count, table) of the blend, source and
+    component descriptors (numpy records of lite/measure.py, passed as void *), then the
+    (buffer, size) pairs images, stamps, seds, morphs, out."""
+    return ([ctypes.c_int32] * 4 + [ctypes.c_int32, ctypes.c_void_p] * 3
+            + [fp, ctypes.c_int64] * 5)
+
+
 class BatchDesc(ctypes.Structure):
     _fields_ = [
         (name, ctypes.c_int32)
@@ -119,6 +127,8 @@ SYMBOLS = {
         [c_f64p, ctypes.c_int32, ctypes.c_int32, c_f64p, ctypes.c_int32, c_i32p, c_i32p,
          c_i32p, c_i32p, c_f64p],
     ),
+    "smi_reweight_f32": (ctypes.c_int, _REWEIGHT(c_f32p)),
+    "smi_reweight_f64": (ctypes.c_int, _REWEIGHT(c_f64p)),
     "smi_get_valid_monotonic_pixels_f32": (
         ctypes.c_int,
         [ctypes.c_int32, ctypes.c_int32, c_f32p, ctypes.c_int32, ctypes.c_int32, c_u8p, c_u8p,

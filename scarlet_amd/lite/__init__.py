@@ -15,7 +15,7 @@ from .initialization import (  # noqa: F401
     parameterize_sources,
     WaveletInitParameters,
 )
-from .measure import calculate_snr, weight_sources  # noqa: F401
+from .measure import calculate_snr, weight_blends, weight_sources  # noqa: F401
 from .models import (  # noqa: F401
     LiteBlend,
     LiteComponent,

@@ -199,9 +199,11 @@ def _fit_group(blends, key, max_iter, e_rel, min_iter, resize, device):
     return failed
 
 
-def _fit_on(blends, keys, device, max_iter, e_rel, min_iter, resize):
-    """Groups the blends of one shard and fits every group on ``device``.  Returns the
-    positions (within the shard) of the blends that failed."""
+def _fit_on(blends, keys, device, max_iter, e_rel, min_iter, resize, reweight=False):
+    """Groups the blends of one shard and fits every group on ``device``; with ``reweight``
+    the blends that did not fail -- those with nothing to fit included -- are then reweighted
+    there (``weight_blends``).  Returns the positions (within the shard) of the blends that
+    failed."""
     groups = {}
     for i, key in enumerate(keys):
         if key is not None:
@@ -218,6 +220,10 @@ def _fit_on(blends, keys, device, max_iter, e_rel, min_iter, resize):
             if lock is not None:
                 lock.release()
         failed.update(idx[j] for j in bad)
+    if reweight:
+        from .measure import weight_blends
+
+        weight_blends([b for i, b in enumerate(blends) if i not in failed], device=device)
     return failed
 
 
@@ -243,7 +249,8 @@ def fit_blends(blends, max_iter, e_rel=1e-4, min_iter=1, resize=10, reweight=Tru
     number of bands, the difference-kernel stamp shape, the iteration counter and the FFT
     shape of their own frame run in one device batch, whatever their frame sizes (ragged
     frames: ``BlendBatch(frame_shapes=...)``).  Box resizing stays per blend, every
-    ``resize`` iterations, on the host.
+    ``resize`` iterations, on the host.  With ``reweight`` the blends are then reweighted
+    together (``weight_blends``: what ``weight_sources`` sets, one device batch per group).
 
     ``devices``: ``None`` / an int: one GPU; a list of GPU indices: contiguous shards
     (``dist.shard_range``), one host thread each.  Results do not depend on the partition.
@@ -265,7 +272,7 @@ def fit_blends(blends, max_iter, e_rel=1e-4, min_iter=1, resize=10, reweight=Tru
     devices = [int(d) for d in devices]
     failed = set()
     if len(devices) == 1:
-        failed = _fit_on(blends, keys, devices[0], max_iter, e_rel, min_iter, resize)
+        failed = _fit_on(blends, keys, devices[0], max_iter, e_rel, min_iter, resize, reweight)
     elif blends:
         from concurrent.futures import ThreadPoolExecutor
 
@@ -274,12 +281,10 @@ def fit_blends(blends, max_iter, e_rel=1e-4, min_iter=1, resize=10, reweight=Tru
         cuts = [shard_range(len(blends), i, len(devices)) for i in range(len(devices))]
         with ThreadPoolExecutor(len(devices)) as pool:
             jobs = [pool.submit(_fit_on, blends[lo:hi], keys[lo:hi], dev, max_iter, e_rel,
-                                min_iter, resize)
+                                min_iter, resize, reweight)
                     for (lo, hi), dev in zip(cuts, devices)]
             for (lo, _), job in zip(cuts, jobs):
                 failed.update(lo + i for i in job.result())
-    from .measure import weight_sources
-
     out = []
     for i, (b, key) in enumerate(zip(blends, keys)):
         if i in failed:
@@ -288,11 +293,9 @@ def fit_blends(blends, max_iter, e_rel=1e-4, min_iter=1, resize=10, reweight=Tru
             out.append((b.it, float("nan")))
         elif key is None:
             # nothing to run on the device (no components, or the counter is at max_iter):
-            # LiteBlend.fit only reweights and reports then
-            out.append(b.fit(max_iter, e_rel, min_iter, resize, reweight))
+            # LiteBlend.fit only reports then (the reweighting is done, with its shard)
+            out.append(b.fit(max_iter, e_rel, min_iter, resize, reweight=False))
         else:
-            if reweight:
-                weight_sources(b)
             out.append((b.it, b.loss[-1]))
     return out
 
