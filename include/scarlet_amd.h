@@ -726,6 +726,28 @@ int smi_resampler_destroy(smi_resampler *r);
 int smi_resampler_get_path(smi_resampler *r, int32_t *path);
 int smi_resampler_set_path(smi_resampler *r, int32_t path);
 
+/* Test entry points of the multi-resolution products (tests/test_resample_host.py,
+ * tests/test_gpu_resample.py); not part of the rendering interface.
+ *
+ * smi_gemm_plan (host only, no GPU): what the matrix product behind both paths launches for
+ * C[n_batch][M][N] = A[M][K] . B[K][N] with scratch_elems doubles for slice partials --
+ * plan = {tm, tn, bk, kslice, n_slices}: the kernel variant (64 tm x 64 tn block tile, k
+ * depth bk), the terms per slice and the number of slices of K.  A plan whose n_slices *
+ * n_batch exceeds the grid's z limit of 65535 is an error (the product returns it too).
+ *
+ * smi_gemm_test: that product on host operands (batch strides in floats, 0 = shared).  C
+ * and the scratch are filled with NaNs before the launch; 256 guard floats before and after
+ * C and 256 guard doubles after the scratch must come back untouched (*guard_ok = 1).
+ *
+ * smi_resampler_adjoint: the transposed map of smi_resampler_render on the resampler's
+ * current path, resid[C][n_a][n_b] -> gpad[C][Fy][Fx] (host pointers). */
+int smi_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t n_batch, int64_t scratch_elems,
+                  int32_t plan[5]);
+int smi_gemm_test(const float *A, int64_t strideA, const float *B, int64_t strideB, float *C,
+                  int64_t strideC, int32_t n_batch, int32_t M, int32_t N, int32_t K,
+                  int64_t scratch_elems, int32_t plan[5], int32_t *guard_ok);
+int smi_resampler_adjoint(smi_resampler *r, const float *resid, float *gpad);
+
 /* The low-resolution observation as a further term of a fit (Blend._loss_func sums the
  * log-likelihoods of all observations, blend.py:265-271; Observation.get_log_likelihood,
  * observation.py:147-170).  `channels[C]` gives the model channel of every band of the

@@ -160,6 +160,13 @@ SYMBOLS = {
     "smi_resampler_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "smi_resampler_get_path": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     "smi_resampler_set_path": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "smi_resampler_adjoint": (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p]),
+    "smi_gemm_plan": (ctypes.c_int, [ctypes.c_int32] * 4 + [ctypes.c_int64, c_i32p]),
+    "smi_gemm_test": (
+        ctypes.c_int,
+        [c_f32p, ctypes.c_int64, c_f32p, ctypes.c_int64, c_f32p, ctypes.c_int64]
+        + [ctypes.c_int32] * 4 + [ctypes.c_int64, c_i32p, c_i32p],
+    ),
     "smi_batch_attach_lowres": (
         ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32p, c_f32p, c_f32p, ctypes.c_double]
     ),

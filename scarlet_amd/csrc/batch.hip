@@ -692,6 +692,37 @@ int smi_resampler_set_path(smi_resampler *r, int32_t path) {
     return resampler_set_path(r->impl, path);
 }
 
+int smi_resampler_adjoint(smi_resampler *r, const float *resid, float *gpad) {
+    SMI_REQUIRE(r && r->impl && resid && gpad, "null argument");
+    return resampler_adjoint_host(r->impl, resid, gpad);
+}
+
+int smi_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t n_batch, int64_t scratch_elems,
+                  int32_t plan[5]) {
+    SMI_REQUIRE(plan && scratch_elems >= 0, "bad argument");
+    GemmPlan p;
+    const int rc = gemm_plan(M, N, K, n_batch, (size_t)scratch_elems, &p);
+    plan[0] = p.tm; plan[1] = p.tn; plan[2] = p.bk; plan[3] = p.kslice; plan[4] = p.n_slices;
+    return rc;
+}
+
+int smi_gemm_test(const float *A, int64_t strideA, const float *B, int64_t strideB, float *C,
+                  int64_t strideC, int32_t n_batch, int32_t M, int32_t N, int32_t K,
+                  int64_t scratch_elems, int32_t plan[5], int32_t *guard_ok) {
+    SMI_REQUIRE(A && B && C && plan && guard_ok && scratch_elems >= 0, "bad argument");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        set_error("no HIP device available");
+        return SMI_ERR_NO_DEVICE;
+    }
+    GemmPlan p;
+    *guard_ok = 0;
+    const int rc = gemm_test(A, strideA, B, strideB, C, strideC, n_batch, M, N, K,
+                             (size_t)scratch_elems, &p, guard_ok);
+    plan[0] = p.tm; plan[1] = p.tn; plan[2] = p.bk; plan[3] = p.kslice; plan[4] = p.n_slices;
+    return rc;
+}
+
 static constexpr int kMaxLowRes = 8;
 
 int smi_batch_attach_lowres(smi_batch *b, smi_resampler *r, const int32_t *channels,

@@ -464,6 +464,16 @@ int resampler_time(Resampler *r, int n_rep, double *ms_per_render);
 int resampler_get_path(const Resampler *r);
 int resampler_set_path(Resampler *r, int path);
 void resampler_destroy(Resampler *r);
+int resampler_adjoint_host(Resampler *r, const float *resid, float *gpad);
+// the launch gemm() (resample.hip) makes of a product: gemm_mfma_kernel<tm, tn, bk>, slices of
+// kslice terms
+struct GemmPlan {
+    int32_t tm = 0, tn = 0, bk = 0, kslice = 0, n_slices = 0;
+};
+int gemm_plan(int M, int N, int K, int n_batch, size_t scratch_elems, GemmPlan *p);
+int gemm_test(const float *A, int64_t strideA, const float *B, int64_t strideB, float *C,
+              int64_t strideC, int n_batch, int M, int N, int K, size_t scratch_elems,
+              GemmPlan *plan, int32_t *guard_ok);
 struct LowRes;
 int lowres_create(Resampler *r, const int32_t *channels, const float *data, const float *weights,
                   double log_norm, int H, int W, double *term_slot, LowRes **out);

@@ -21,6 +21,7 @@
 // to fill the chip.  The bands of an observation are one batched launch.
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <type_traits>
 #include <vector>
 
@@ -199,20 +200,24 @@ __global__ __launch_bounds__(1024) void reduce_slices_kernel(const double *Cpart
     }
 }
 
-int gemm(const float *A, int64_t strideA, const float *B, int64_t strideB, float *C,
-         int64_t strideC, int n_batch, double *scratch, size_t scratch_elems, int M, int N, int K,
-         hipStream_t s) {
+}  // namespace
+
+// What gemm() launches for an M x N x K product of n_batch matrices with `scratch_elems`
+// doubles for the slice partials (host only): the variant gemm_mfma_kernel<tm, tn, bk>, the
+// terms per slice (a multiple of kBK) and the number of slices.  Refuses a grid the device
+// cannot launch.
+int gemm_plan(int M, int N, int K, int n_batch, size_t scratch_elems, GemmPlan *p) {
+    SMI_REQUIRE(M > 0 && N > 0 && K > 0 && n_batch > 0 && p, "gemm: bad sizes");
     // one MFMA tile per wavefront along a dimension of up to 96 (see the kernel)
     int tm = M <= 96 ? 1 : 2, tn = N <= 96 ? 1 : 2;
     auto n_tiles = [&](int a, int b) {
-        return ((M + 64 * a - 1) / (64 * a)) * ((N + 64 * b - 1) / (64 * b)) * n_batch;
+        return (int64_t)((M + 64 * a - 1) / (64 * a)) * ((N + 64 * b - 1) / (64 * b)) * n_batch;
     };
     // (a product of a few hundred rows and columns -- the transforms of the spectral path --
     // is 45 workgroups in 128 x 128 tiles and 125 in 64 x 64 tiles)
     const bool few = n_tiles(tm, tn) * std::max(1, (K + kSliceTerms - 1) / kSliceTerms) < 200;
     if (few) tm = tn = 1;
-    const int bm = 64 * tm, bn = 64 * tn;
-    const int tiles = n_tiles(tm, tn);
+    const int64_t tiles = n_tiles(tm, tn);
     // slices of ~kSliceTerms terms (float32 accumulation length); fewer when the tiles
     // alone fill the chip several times over and the partials would not fit the scratch.
     // (Round 4: fewer, longer slices -- 18 instead of 47 for the 300 x 300 x 15 000 product, 61
@@ -226,20 +231,38 @@ int gemm(const float *A, int64_t strideA, const float *B, int64_t strideB, float
     int kslice = (K + n_slices - 1) / n_slices;
     kslice = (kslice + kBK - 1) / kBK * kBK;
     n_slices = (K + kslice - 1) / kslice;
-    const dim3 grid((N + bn - 1) / bn, (M + bm - 1) / bm, n_slices * n_batch);
-    double *part = n_slices > 1 ? scratch : nullptr;
-#define SMI_GEMM(TM, TN)                                                                         \
-    hipLaunchKernelGGL((gemm_mfma_kernel<TM, TN>), grid, dim3(256), 0, s, A, strideA, B, strideB, \
-                       C, strideC, part, M, N, K, kslice, n_slices)
     // (a workgroup alone on its CU waits for every k-tile's loads: twice the depth per tile
     // where the grid does not fill the chip)
-    if (few)
-        hipLaunchKernelGGL((gemm_mfma_kernel<1, 1, 2 * kBK>), grid, dim3(256), 0, s, A, strideA, B,
-                           strideB, C, strideC, part, M, N, K, kslice, n_slices);
-    else if (tm == 1 && tn == 1) SMI_GEMM(1, 1);
-    else if (tm == 1) SMI_GEMM(1, 2);
-    else if (tn == 1) SMI_GEMM(2, 1);
-    else SMI_GEMM(2, 2);
+    p->tm = tm;
+    p->tn = tn;
+    p->bk = few ? 2 * kBK : kBK;
+    p->kslice = kslice;
+    p->n_slices = n_slices;
+    SMI_REQUIRE((int64_t)n_slices * n_batch <= 65535,
+                "gemm: slices x batch exceed the grid's z limit");
+    return SMI_OK;
+}
+
+namespace {
+
+int gemm(const float *A, int64_t strideA, const float *B, int64_t strideB, float *C,
+         int64_t strideC, int n_batch, double *scratch, size_t scratch_elems, int M, int N, int K,
+         hipStream_t s) {
+    GemmPlan p;
+    const int rc = gemm_plan(M, N, K, n_batch, scratch_elems, &p);
+    if (rc) return rc;
+    const int bm = 64 * p.tm, bn = 64 * p.tn, kslice = p.kslice, n_slices = p.n_slices;
+    const size_t MN = (size_t)M * N;
+    const dim3 grid((N + bn - 1) / bn, (M + bm - 1) / bm, n_slices * n_batch);
+    double *part = n_slices > 1 ? scratch : nullptr;
+#define SMI_GEMM(TM, TN, BK)                                                                   \
+    hipLaunchKernelGGL((gemm_mfma_kernel<TM, TN, BK>), grid, dim3(256), 0, s, A, strideA, B,   \
+                       strideB, C, strideC, part, M, N, K, kslice, n_slices)
+    if (p.bk == 2 * kBK) SMI_GEMM(1, 1, 2 * kBK);
+    else if (p.tm == 1 && p.tn == 1) SMI_GEMM(1, 1, kBK);
+    else if (p.tm == 1) SMI_GEMM(1, 2, kBK);
+    else if (p.tn == 1) SMI_GEMM(2, 1, kBK);
+    else SMI_GEMM(2, 2, kBK);
 #undef SMI_GEMM
     if (n_slices > 1)
         hipLaunchKernelGGL(reduce_slices_kernel, dim3((unsigned)((MN + 63) / 64), n_batch),
@@ -667,6 +690,91 @@ int resampler_render(Resampler *r, const float *model, float *out) {
     SMI_HIP(hipDeviceSynchronize());
     SMI_HIP(hipMemcpy(out, r->out, (size_t)r->C * r->n_a * r->n_b * sizeof(float),
                       hipMemcpyDeviceToHost));
+    return SMI_OK;
+}
+
+// the transposed chain on host buffers: resid [C][n_a][n_b] -> gpad [C][Fy][Fx], on the
+// resampler's current path (the counterpart of resampler_render; test entry point)
+int resampler_adjoint_host(Resampler *r, const float *resid, float *gpad) {
+    const size_t n = (size_t)r->C * r->n_a * r->n_b, plane = (size_t)r->Fy * r->Fx;
+    float *d_resid = nullptr, *d_gpad = nullptr;
+    auto run = [&]() -> int {
+        SMI_HIP(hipMalloc((void **)&d_resid, n * sizeof(float)));
+        SMI_HIP(hipMalloc((void **)&d_gpad, r->C * plane * sizeof(float)));
+        SMI_HIP(hipMemcpy(d_resid, resid, n * sizeof(float), hipMemcpyHostToDevice));
+        const int rc = resampler_adjoint(r, d_resid, d_gpad, nullptr);
+        if (rc) return rc;
+        SMI_HIP(hipGetLastError());
+        SMI_HIP(hipDeviceSynchronize());
+        SMI_HIP(hipMemcpy(gpad, d_gpad, r->C * plane * sizeof(float), hipMemcpyDeviceToHost));
+        return SMI_OK;
+    };
+    const int rc = run();
+    if (d_resid) (void)hipFree(d_resid);
+    if (d_gpad) (void)hipFree(d_gpad);
+    return rc;
+}
+
+// gemm() on host operands, for the tests: C and the scratch hold NaNs before the launch, a
+// guard band of kGuard floats lies before and after C and one of kGuard doubles after the
+// scratch; *guard_ok tells whether all three came back untouched.
+int gemm_test(const float *A, int64_t strideA, const float *B, int64_t strideB, float *C,
+              int64_t strideC, int n_batch, int M, int N, int K, size_t scratch_elems,
+              GemmPlan *plan, int32_t *guard_ok) {
+    constexpr size_t kGuard = 256;
+    const int rc0 = gemm_plan(M, N, K, n_batch, scratch_elems, plan);
+    if (rc0) return rc0;
+    SMI_REQUIRE(strideA >= 0 && strideB >= 0 && (n_batch == 1 || strideC >= (int64_t)M * N),
+                "gemm_test: bad strides");
+    const size_t nA = (size_t)(n_batch - 1) * strideA + (size_t)M * K;
+    const size_t nB = (size_t)(n_batch - 1) * strideB + (size_t)K * N;
+    const size_t nC = (size_t)(n_batch - 1) * strideC + (size_t)M * N;
+    uint32_t fbits = 0x7fc00000u, gbits = 0xa5a5a5a5u;
+    uint64_t dbits = 0x7ff8000000000000ull, gdbits = 0xa5a5a5a5a5a5a5a5ull;
+    float fnan, fguard;
+    double dnan, dguard;
+    memcpy(&fnan, &fbits, 4);
+    memcpy(&fguard, &gbits, 4);
+    memcpy(&dnan, &dbits, 8);
+    memcpy(&dguard, &gdbits, 8);
+    std::vector<float> hC(nC + 2 * kGuard, fnan);
+    std::vector<double> hS(scratch_elems + kGuard, dnan);
+    for (size_t i = 0; i < kGuard; ++i) {
+        hC[i] = hC[kGuard + nC + i] = fguard;
+        hS[scratch_elems + i] = dguard;
+    }
+    float *dA = nullptr, *dB = nullptr, *dC = nullptr;
+    double *dS = nullptr;
+    auto run = [&]() -> int {
+        SMI_HIP(hipMalloc((void **)&dA, nA * sizeof(float)));
+        SMI_HIP(hipMalloc((void **)&dB, nB * sizeof(float)));
+        SMI_HIP(hipMalloc((void **)&dC, hC.size() * sizeof(float)));
+        SMI_HIP(hipMalloc((void **)&dS, hS.size() * sizeof(double)));
+        SMI_HIP(hipMemcpy(dA, A, nA * sizeof(float), hipMemcpyHostToDevice));
+        SMI_HIP(hipMemcpy(dB, B, nB * sizeof(float), hipMemcpyHostToDevice));
+        SMI_HIP(hipMemcpy(dC, hC.data(), hC.size() * sizeof(float), hipMemcpyHostToDevice));
+        SMI_HIP(hipMemcpy(dS, hS.data(), hS.size() * sizeof(double), hipMemcpyHostToDevice));
+        const int rc = gemm(dA, strideA, dB, strideB, dC + kGuard, strideC, n_batch, dS,
+                            scratch_elems, M, N, K, nullptr);
+        if (rc) return rc;
+        SMI_HIP(hipGetLastError());
+        SMI_HIP(hipDeviceSynchronize());
+        SMI_HIP(hipMemcpy(hC.data(), dC, hC.size() * sizeof(float), hipMemcpyDeviceToHost));
+        SMI_HIP(hipMemcpy(hS.data() + scratch_elems, dS + scratch_elems, kGuard * sizeof(double),
+                          hipMemcpyDeviceToHost));
+        return SMI_OK;
+    };
+    const int rc = run();
+    for (void *p : {(void *)dA, (void *)dB, (void *)dC, (void *)dS})
+        if (p) (void)hipFree(p);
+    if (rc) return rc;
+    bool ok = true;
+    for (size_t i = 0; i < kGuard; ++i) {
+        ok = ok && memcmp(&hC[i], &fguard, 4) == 0 && memcmp(&hC[kGuard + nC + i], &fguard, 4) == 0;
+        ok = ok && memcmp(&hS[scratch_elems + i], &dguard, 8) == 0;
+    }
+    *guard_ok = ok ? 1 : 0;
+    memcpy(C, hC.data() + kGuard, nC * sizeof(float));
     return SMI_OK;
 }
 
