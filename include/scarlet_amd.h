@@ -144,6 +144,100 @@ int smi_reweight_f64(int32_t device, int32_t C, int32_t kh, int32_t kw, int32_t 
                      int64_t n_sed, const double *morphs, int64_t n_morph, double *out,
                      int64_t n_out);
 
+/* lite.init_blends: the wavelet initialisation of scarlet.lite (reference
+ * lite/initialization.py:422-605) for a catalogue of blends.  Six steps, each one launch
+ * over a table of tasks; the caller owns every buffer (`d_*`: device memory) and orders the
+ * calls on `stream`.  A table is passed twice: in host memory, where it is validated before
+ * anything is launched (a bad one returns SMI_ERR_INVALID), and as the copy on the device the
+ * kernel reads.  Offsets and sizes count elements of the buffer they refer to.
+ *   coadd  three sums of clipped wavelet planes per blend (detectlets, bulgelets, disklets):
+ *          planes first[k], first[k] + step[k], ... (count[k] of them) added in that order
+ *   snr    per source the two float64 sums of calculate_snr, PSF stamp on the centre
+ *   taps   per task the centre pixel of apply_filter in every band (C values) and the plane's
+ *          value at the centre (one more), bit-identical to the reference's tap loop
+ *   masks  prox_monotonic_mask(X, 0, centre, max_iter=0): valid map, bounds (min row, max
+ *          row, min col, max col), and per task the value at the seed
+ *   crop   where(valid, plane, 0) on a box that may leave the frame, divided by its maximum
+ *   fit    per source and band a.a, a.b, b.b, a.img, b.img over the union box of two
+ *          morphologies (a, b: the morphologies convolved with the band's stamp) */
+typedef struct smi_lite_init_coadd {
+    int32_t n_planes;
+    int32_t first[3], count[3], step[3];
+    int32_t reserved[2];
+    int64_t n_pix, wavelet_off, coadd_off;  /* coadds: 3 planes of n_pix */
+} smi_lite_init_coadd;
+typedef struct smi_lite_init_snr {
+    int32_t h, w, cy, cx, ph, pw;
+    int64_t image_off, psf_off;
+} smi_lite_init_snr;
+typedef struct smi_lite_init_taps {
+    int32_t h, w, cy, cx, kh, kw;
+    int64_t plane_off, stamp_off, out_off;  /* out: C + 1 values */
+} smi_lite_init_taps;
+typedef struct smi_lite_init_mask {
+    int32_t h, w, cy, cx;
+    int64_t plane_off, pix_off, valid_off;  /* pix_off: the task's h * w of the scratch */
+} smi_lite_init_mask;
+typedef struct smi_lite_init_crop {
+    int32_t h, w;            /* plane */
+    int32_t y0, x0, bh, bw;  /* box, in plane coordinates */
+    int64_t plane_off, valid_off, out_off;
+} smi_lite_init_crop;
+typedef struct smi_lite_init_fit {
+    int32_t h, w;                    /* frame */
+    int32_t y0, x0, fh, fw;          /* union box, in frame coordinates */
+    int32_t a_y0, a_x0, a_h, a_w;    /* boxes of the two morphologies, inside the union */
+    int32_t b_y0, b_x0, b_h, b_w;
+    int32_t kh, kw;
+    int64_t image_off, stamp_off, a_off, b_off;
+} smi_lite_init_fit;
+int smi_lite_init_coadd_f32(int32_t n, const smi_lite_init_coadd *tasks, const void *d_tasks,
+                            const float *d_wavelets, int64_t n_wavelets, float *d_coadds,
+                            int64_t n_coadds, void *stream);
+int smi_lite_init_snr_f32(int32_t C, int32_t n, const smi_lite_init_snr *tasks, const void *d_tasks,
+                          const float *d_images, const float *d_variance, int64_t n_image,
+                          const float *d_psfs, int64_t n_psf, double *d_out, int64_t n_out,
+                          void *stream);
+int smi_lite_init_taps_f32(int32_t C, int32_t n, const smi_lite_init_taps *tasks,
+                           const void *d_tasks, const float *d_planes, int64_t n_plane,
+                           const float *d_stamps, int64_t n_stamp, float *d_out, int64_t n_out,
+                           void *stream);
+int smi_lite_init_masks_f32(int32_t n, const smi_lite_init_mask *tasks, const void *d_tasks,
+                            const float *d_planes, int64_t n_plane, int32_t *d_visited,
+                            uint8_t *d_unchecked, uint8_t *d_orphans, int64_t n_scratch,
+                            uint8_t *d_valid, int64_t n_valid, int32_t *d_bounds, float *d_values,
+                            int64_t n_results, void *stream);
+int smi_lite_init_crop_f32(int32_t n, const smi_lite_init_crop *tasks, const void *d_tasks,
+                           const float *d_planes, int64_t n_plane, const uint8_t *d_valid,
+                           int64_t n_valid, float *d_out, int64_t n_out, void *stream);
+int smi_lite_init_fit_f32(int32_t C, int32_t n, const smi_lite_init_fit *tasks, const void *d_tasks,
+                          const float *d_morphs, int64_t n_morph, const void *d_images,
+                          int32_t images_f64, int64_t n_image, const double *d_stamps,
+                          int64_t n_stamp, double *d_out, int64_t n_out, void *stream);
+int smi_lite_init_coadd_f64(int32_t n, const smi_lite_init_coadd *tasks, const void *d_tasks,
+                            const double *d_wavelets, int64_t n_wavelets, double *d_coadds,
+                            int64_t n_coadds, void *stream);
+int smi_lite_init_snr_f64(int32_t C, int32_t n, const smi_lite_init_snr *tasks, const void *d_tasks,
+                          const double *d_images, const double *d_variance, int64_t n_image,
+                          const double *d_psfs, int64_t n_psf, double *d_out, int64_t n_out,
+                          void *stream);
+int smi_lite_init_taps_f64(int32_t C, int32_t n, const smi_lite_init_taps *tasks,
+                           const void *d_tasks, const double *d_planes, int64_t n_plane,
+                           const double *d_stamps, int64_t n_stamp, double *d_out, int64_t n_out,
+                           void *stream);
+int smi_lite_init_masks_f64(int32_t n, const smi_lite_init_mask *tasks, const void *d_tasks,
+                            const double *d_planes, int64_t n_plane, int32_t *d_visited,
+                            uint8_t *d_unchecked, uint8_t *d_orphans, int64_t n_scratch,
+                            uint8_t *d_valid, int64_t n_valid, int32_t *d_bounds, double *d_values,
+                            int64_t n_results, void *stream);
+int smi_lite_init_crop_f64(int32_t n, const smi_lite_init_crop *tasks, const void *d_tasks,
+                           const double *d_planes, int64_t n_plane, const uint8_t *d_valid,
+                           int64_t n_valid, double *d_out, int64_t n_out, void *stream);
+int smi_lite_init_fit_f64(int32_t C, int32_t n, const smi_lite_init_fit *tasks, const void *d_tasks,
+                          const double *d_morphs, int64_t n_morph, const void *d_images,
+                          int32_t images_f64, int64_t n_image, const double *d_stamps,
+                          int64_t n_stamp, double *d_out, int64_t n_out, void *stream);
+
 /* get_valid_monotonic_pixels / linear_interpolate_invalid_pixels
  * (operators_pybind11.cc:61-232, float32 and float64 overload sets; callers
  * operator.py:155-176).  Row-major (rows, cols) images; `unchecked` / `orphans` are the

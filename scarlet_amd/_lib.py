@@ -62,6 +62,23 @@ def _REWEIGHT(fp):
             + [fp, ctypes.c_int64] * 5)
 
 
+def _LITE_INIT():
+    """smi_lite_init_*: every entry takes (count, host table, device table), then device
+    buffers as void * with their sizes in elements, then the stream (lite/initialization.py)."""
+    v, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+    table = [i32, v, v]
+    steps = {
+        "coadd": table + [v, i64, v, i64, v],
+        "snr": [i32] + table + [v, v, i64, v, i64, v, i64, v],
+        "taps": [i32] + table + [v, i64, v, i64, v, i64, v],
+        "masks": table + [v, i64, v, v, v, i64, v, i64, v, v, i64, v],
+        "crop": table + [v, i64, v, i64, v, i64, v],
+        "fit": [i32] + table + [v, i64, v, i32, i64, v, i64, v, i64, v],
+    }
+    return {"smi_lite_init_%s_%s" % (step, tag): (ctypes.c_int, args)
+            for step, args in steps.items() for tag in ("f32", "f64")}
+
+
 class BatchDesc(ctypes.Structure):
     _fields_ = [
         (name, ctypes.c_int32)
@@ -319,6 +336,7 @@ SYMBOLS = {
     "smi_footprints_device_fetch_f32": (ctypes.c_int, _FP_FETCH),
     "smi_footprints_device_fetch_f64": (ctypes.c_int, _FP_FETCH),
 }
+SYMBOLS.update(_LITE_INIT())
 
 _lib = None
 

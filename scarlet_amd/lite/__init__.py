@@ -7,12 +7,14 @@ from .initialization import (  # noqa: F401
     init_adaprox_component,
     init_all_sources_main,
     init_all_sources_wavelets,
+    init_blends,
     init_fista_component,
     init_main_parameters,
     init_monotonic_morph,
     init_wavelet_source,
     multifit_seds,
     parameterize_sources,
+    plan_init_blends,
     WaveletInitParameters,
 )
 from .measure import calculate_snr, weight_blends, weight_sources  # noqa: F401
