@@ -900,6 +900,48 @@ int smi_coadd_f32(const float *d_images, int32_t bands, int32_t H, int32_t W, fl
 int smi_coadd_f64(const double *d_images, int32_t bands, int32_t H, int32_t W, double *d_out,
                   void *stream);
 
+/* get_detect_wavelets (detect.py:362-399) for a catalogue of blends whose frames, band counts
+ * and scale counts differ (detect_batch.hip): coadd, starlet transform, multiresolution support
+ * and M * w of every blend, each bit for bit what smi_coadd_* -> smi_starlet_transform_* ->
+ * smi_multiresolution_support_f64 give for that blend alone (n = 1).  The table convention is
+ * the one of smi_lite_init_*: the tasks are passed in host memory, where they are validated
+ * before anything is launched (a bad table returns SMI_ERR_INVALID), and as the copy on the
+ * device the kernels read; offsets and sizes count elements; the caller owns every buffer.
+ * One task per blend:
+ *   bands, h, w   its images [bands][h][w] at image_off of d_images
+ *   scales        as given to the transform: planes = scales + 1 coefficient planes [h][w] at
+ *                 coeff_off of d_coeffs, d_masked and d_support (ranges in table order, not
+ *                 overlapping)
+ *   work_off      its plane [h][w] of d_work (ranges in table order, not overlapping)
+ *   sigma0, thresh0  the initial sigma_j and K * sigma_j of every plane, as the caller's dtype
+ *                 rounded them
+ * 1 <= h * w <= 65536 (one workgroup runs all support iterations of a blend; larger frames
+ * belong to the per-image entry points above), 0 <= scales <= 30, n <= 65535.
+ * Outputs, all in device memory: d_masked = M * w (-0.0 for a negative w outside the support),
+ * d_support = M as 0 / 1 (may be NULL), d_iterations[n] = support iterations run.  d_coeffs
+ * keeps the unmasked coefficients.  d_scratch: smi_detect_wavelets_scratch_bytes(n) bytes (the
+ * final thresholds).  The calls allocate nothing, copy nothing and wait for nothing: they
+ * enqueue 1 + 4 * S + 2 launches (generation 2; 1 + 2 * S + 2 for generation 1), S the largest
+ * `scales` of the table, on `stream`, whatever n. */
+typedef struct smi_detect_task {
+    int32_t bands, h, w, scales;
+    int64_t image_off, coeff_off, work_off;
+    double sigma0, thresh0;
+} smi_detect_task;
+int smi_detect_wavelets_scratch_bytes(int32_t n, int64_t *bytes);
+int smi_detect_wavelets_f32(int32_t n, const smi_detect_task *tasks, const void *d_tasks, double K,
+                            double epsilon, int32_t max_iter, int32_t generation,
+                            const float *d_images, int64_t n_images, double *d_coeffs,
+                            int64_t n_coeffs, double *d_work, int64_t n_work, double *d_masked,
+                            int32_t *d_support, int32_t *d_iterations, void *d_scratch,
+                            int64_t scratch_bytes, void *stream);
+int smi_detect_wavelets_f64(int32_t n, const smi_detect_task *tasks, const void *d_tasks, double K,
+                            double epsilon, int32_t max_iter, int32_t generation,
+                            const double *d_images, int64_t n_images, double *d_coeffs,
+                            int64_t n_coeffs, double *d_work, int64_t n_work, double *d_masked,
+                            int32_t *d_support, int32_t *d_iterations, void *d_scratch,
+                            int64_t scratch_bytes, void *stream);
+
 /* get_footprints (detect_pybind11.cc) on the host, in two calls.  The first finds the
  * footprints of image[H][W] -- 4-connected pixels > thresh, seeds in raster order, kept when
  * the box has more than min_area pixels and the footprint at least min_area -- with their

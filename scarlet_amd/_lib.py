@@ -79,6 +79,17 @@ def _LITE_INIT():
             for step, args in steps.items() for tag in ("f32", "f64")}
 
 
+def _DETECT_BATCH():
+    """smi_detect_wavelets_*: (count, host table, device table), K, epsilon, max_iter,
+    generation, then device buffers as void * (images, coefficients and work with their sizes
+    in elements), the outputs, the scratch with its bytes, the stream (wavelet.py)."""
+    v, i32, i64, f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
+    args = [i32, v, v, f64, f64, i32, i32, v, i64, v, i64, v, i64, v, v, v, v, i64, v]
+    out = {"smi_detect_wavelets_%s" % tag: (ctypes.c_int, args) for tag in ("f32", "f64")}
+    out["smi_detect_wavelets_scratch_bytes"] = (ctypes.c_int, [i32, c_i64p])
+    return out
+
+
 class BatchDesc(ctypes.Structure):
     _fields_ = [
         (name, ctypes.c_int32)
@@ -337,6 +348,7 @@ SYMBOLS = {
     "smi_footprints_device_fetch_f64": (ctypes.c_int, _FP_FETCH),
 }
 SYMBOLS.update(_LITE_INIT())
+SYMBOLS.update(_DETECT_BATCH())
 
 _lib = None
 

@@ -1,7 +1,9 @@
 """Source detection on starlet coefficients (reference scarlet/detect.py).
 
 The wavelet stages -- the coadd of the bands, the starlet transform and the multiresolution
-support -- run on the GPU in one device-resident chain.  Footprints and peaks of coefficients
+support -- run on the GPU in one device-resident chain; ``get_detect_wavelets_batch`` runs
+them for a catalogue of blends of different frames in one chain per dtype
+(``csrc/detect_batch.hip``).  Footprints and peaks of coefficients
 that stay on the device (``get_detect_wavelets(..., device=True)``) are found there too
 (``detect_pybind11.get_footprints_device``); host arrays take the host code
 (``get_footprints``).  The structures that connect the footprints across scales are plain
@@ -185,6 +187,121 @@ def get_detect_wavelets(images, variance, scales=3, device=False):
     s0, t0 = wavelet.initial_sigma(dtype, scales + 1, sigma, 3)
     _, Mw, _ = wavelet.support_device(d_coeffs, s0[None], t0[None], 3, 1e-1, 20)
     return Mw[:, 0] if device else Mw[:, 0].cpu().numpy()
+
+
+# ---------------------------------------------------------------------------
+# get_detect_wavelets for a catalogue: one device chain per group of blends
+# ---------------------------------------------------------------------------
+# Device bytes of one chunk (images, coefficients, M * w, work planes): a group whose blends
+# need more is cut into chunks.
+BATCH_BYTES = 1 << 30
+
+
+def _batch_dtype(images):
+    """dtype of the device copy ``wavelet._upload`` makes of ``images``."""
+    return np.dtype(np.float32 if images.dtype == np.float32 else np.float64)
+
+
+def plan_detect_wavelets_batch(images, variance, scales=3, _max_tasks=None, _max_bytes=None):
+    """``(groups, fallback)`` of ``get_detect_wavelets_batch``, without touching the GPU.
+    ``groups``: per image dtype on the device (float32, or float64 for everything else, as
+    ``wavelet._upload`` converts), in order of first appearance, the chunks of one device
+    call each -- lists of input positions in input order, at most 65535 blends and
+    ``BATCH_BYTES`` of device buffers (a blend beyond the budget is a chunk of its own).
+    ``fallback``: ``(position, reason)`` of the blends that go through
+    ``get_detect_wavelets``: a frame of more than ``wavelet.DETECT_BATCH_MAX_PIXELS`` =
+    65536 pixels -- one workgroup runs all support iterations of a blend, and beyond 32 blocks
+    of pixels per plane the per-blend call's many workgroups are the better shape -- or images
+    that are not a ``(bands, Ny, Nx)`` cube with a band.  Raises ``ValueError`` for lists of
+    different lengths and for a frame one pixel high or wide."""
+    images, variance = list(images), list(variance)
+    if len(images) != len(variance):
+        raise ValueError("images and variance must have one entry per blend, got {} and {}"
+                         .format(len(images), len(variance)))
+    max_tasks = wavelet.DETECT_BATCH_MAX_TASKS if _max_tasks is None else _max_tasks
+    max_bytes = BATCH_BYTES if _max_bytes is None else _max_bytes
+    groups, fallback, used = {}, [], {}
+    for i, im in enumerate(images):
+        im = np.asarray(im)
+        if im.ndim != 3 or im.shape[0] < 1:
+            fallback.append((i, "images are not a (bands, Ny, Nx) cube"))
+            continue
+        planes = wavelet._checked_scales(im.shape, scales) + 1
+        bands, h, w = im.shape
+        if h * w > wavelet.DETECT_BATCH_MAX_PIXELS:
+            fallback.append((i, "frame of more than %d pixels" % wavelet.DETECT_BATCH_MAX_PIXELS))
+            continue
+        dtype = _batch_dtype(im)
+        need = h * w * (bands * dtype.itemsize + (2 * planes + 1) * 8)
+        chunks = groups.setdefault(dtype, [[]])
+        if chunks[-1] and (len(chunks[-1]) >= max_tasks or used[dtype] + need > max_bytes):
+            chunks.append([])
+            used[dtype] = 0
+        chunks[-1].append(i)
+        used[dtype] = used.get(dtype, 0) + need
+    return groups, fallback
+
+
+def _batch_sigmas(variance):
+    """``median(sqrt(variance))`` of every blend, on the host as ``get_detect_wavelets``."""
+    return [np.median(np.sqrt(var)) for var in variance]
+
+
+def _batch_table(images, sigmas, scales):
+    """Task table of the blends of one chunk (``images``: arrays of one device dtype)."""
+    dtype = _batch_dtype(images[0]).type
+    first = [wavelet.initial_sigma(dtype, 1, sigma, 3) for sigma in sigmas]
+    return wavelet.detect_task_table(
+        [im.shape for im in images], [wavelet._checked_scales(im.shape, scales) for im in images],
+        [s0[0] for s0, _ in first], [t0[0] for _, t0 in first])
+
+
+def _batch_upload(images):
+    """The images of one chunk, packed one after another, in one copy to the device."""
+    torch = wavelet._torch()
+    dtype = _batch_dtype(images[0])
+    packed = np.empty(sum(im.size for im in images), dtype)
+    at = 0
+    for im in images:
+        packed[at:at + im.size] = im.reshape(-1)
+        at += im.size
+    return torch.from_numpy(packed).to("cuda")
+
+
+def _batch_views(flat, table):
+    """Blend by blend ``(planes, H, W)`` views of the flat coefficient buffer."""
+    out = []
+    for t in table:
+        planes, h, w = int(t["scales"]) + 1, int(t["h"]), int(t["w"])
+        at = int(t["coeff_off"])
+        out.append(flat[at:at + planes * h * w].reshape(planes, h, w))
+    return out
+
+
+def get_detect_wavelets_batch(images, variance, scales=3, device=False):
+    """``[get_detect_wavelets(im, var, scales, device) for im, var in zip(images, variance)]``
+    for a catalogue of blends whose frames, band counts and dtypes may differ, bit for bit:
+    per group of ``plan_detect_wavelets_batch`` one packed upload and one device chain
+    (csrc/detect_batch.hip) whose number of launches does not depend on the number of blends,
+    the convergence test of every blend's support included.  ``sigma = median(sqrt(variance))``
+    of every blend stays on the host.  Returns the list of ``(scales_i + 1, Ny_i, Nx_i)``
+    float64 arrays -- with ``device=True`` float64 device tensors, views into their group's
+    buffer, without the copy to the host."""
+    images = [np.asarray(im) for im in images]
+    variance = list(variance)
+    groups, fallback = plan_detect_wavelets_batch(images, variance, scales)
+    out = [None] * len(images)
+    for chunks in groups.values():
+        for chunk in chunks:
+            ims = [images[i] for i in chunk]
+            table = _batch_table(ims, _batch_sigmas([variance[i] for i in chunk]), scales)
+            masked, _, _ = wavelet.detect_wavelets_batch_device(_batch_upload(ims), table)
+            flat = masked if device else masked.cpu().numpy()
+            for i, view in zip(chunk, _batch_views(flat, table)):
+                out[i] = view
+    for i, _ in fallback:
+        out[i] = get_detect_wavelets(images[i], variance[i], scales, device)
+    return out
 
 
 def _scale_footprints(detect):

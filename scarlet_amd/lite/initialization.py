@@ -14,7 +14,7 @@ from functools import partial
 import numpy as np
 
 from ..bbox import Box, overlapped_slices
-from ..detect import get_detect_wavelets
+from ..detect import get_detect_wavelets, get_detect_wavelets_batch
 from ..initialization import get_minimal_boxsize, trim_morphology
 from ..operator import prox_monotonic_mask, prox_uncentered_symmetry, prox_weighted_monotonic
 from ..parameter import relative_step
@@ -557,16 +557,21 @@ def _run_init_chunk(blends, key, opts, device):
 
 def _chunk_wavelets(ch, blends, opts):
     """The detection coefficients of the chunk's blends, one after another in one device
-    buffer (those not passed in come from ``get_detect_wavelets`` and never visit the host),
-    and the number of planes of every blend.  Passed arrays and tensors are only read."""
+    buffer (those not passed in come from one ``get_detect_wavelets_batch`` call for all of
+    them and never visit the host), and the number of planes of every blend.  Passed arrays
+    and tensors are only read."""
     n_planes = [_n_planes(obs, wav, opts["scales"]) for obs, _, wav in blends]
     sizes = [p * obs.images.shape[1] * obs.images.shape[2]
              for p, (obs, _, _) in zip(n_planes, blends)]
     off, total = _offsets(sizes)
     d_wavelets = ch.empty(total, ch.wdtype)
+    missing = [obs for obs, _, wav in blends if wav is None]
+    computed = iter(get_detect_wavelets_batch([obs.images for obs in missing],
+                                              [obs.variance for obs in missing],
+                                              scales=opts["scales"], device=True))
     for (obs, _, wav), at, n in zip(blends, off, sizes):
         if wav is None:
-            wav = get_detect_wavelets(obs.images, obs.variance, scales=opts["scales"], device=True)
+            wav = next(computed)
         elif not _is_tensor(wav):
             wav = ch.torch.from_numpy(np.ascontiguousarray(wav))
         d_wavelets[at:at + n].copy_(wav.reshape(-1))

@@ -147,6 +147,86 @@ def initial_sigma(dtype, planes, sigma, K):
 
 
 # ---------------------------------------------------------------------------
+# the detection chain of a ragged catalogue (csrc/detect_batch.hip)
+# ---------------------------------------------------------------------------
+# smi_detect_task: one blend of smi_detect_wavelets_*
+DETECT_TASK = np.dtype([("bands", "i4"), ("h", "i4"), ("w", "i4"), ("scales", "i4"),
+                        ("image_off", "i8"), ("coeff_off", "i8"), ("work_off", "i8"),
+                        ("sigma0", "f8"), ("thresh0", "f8")], align=True)
+# limits of detect_batch.hip: pixels of a frame one workgroup takes through its support
+# iterations, tasks of one call
+DETECT_BATCH_MAX_PIXELS = 1 << 16
+DETECT_BATCH_MAX_TASKS = 65535
+
+
+def detect_task_table(shapes, scales, sigma0, thresh0):
+    """The task table of ``detect_wavelets_batch_device`` for blends of ``shapes``
+    ``(bands, H, W)`` packed one after another: images, coefficients ``(scales_i + 1, H, W)``
+    and work planes each in their own buffer, in input order.  ``scales``: as given to the
+    transform, per blend; ``sigma0`` / ``thresh0``: per blend, as ``initial_sigma`` rounds
+    them (all planes of a blend start equal)."""
+    table = np.zeros(len(shapes), DETECT_TASK)
+    image_off = coeff_off = work_off = 0
+    for k, ((bands, h, w), s) in enumerate(zip(shapes, scales)):
+        table[k] = (bands, h, w, s, image_off, coeff_off, work_off, sigma0[k], thresh0[k])
+        image_off += bands * h * w
+        coeff_off += (s + 1) * h * w
+        work_off += h * w
+    return table
+
+
+def detect_table_sizes(table):
+    """Elements of the image, coefficient and work buffers the tasks of ``table`` reach."""
+    if not len(table):
+        return 0, 0, 0
+    npix = table["h"].astype(np.int64) * table["w"]
+    return (int((table["image_off"] + table["bands"] * npix).max()),
+            int((table["coeff_off"] + (table["scales"] + 1) * npix).max()),
+            int((table["work_off"] + npix).max()))
+
+
+def detect_wavelets_batch_device(d_images, table, K=3, epsilon=1e-1, max_iter=20, generation=2,
+                                 support=False):
+    """Coadd, starlet transform and multiresolution support of every blend of ``table``
+    (``DETECT_TASK`` records, see ``detect_task_table``) whose images lie packed in the flat
+    float32 / float64 device tensor ``d_images``: a fixed number of launches whatever the
+    number of blends, nothing waited for.  Returns ``(masked, support, iterations)``: the flat
+    float64 device tensor of ``M * w`` (blend ``i`` holds ``(scales_i + 1, H_i, W_i)`` at
+    ``table["coeff_off"][i]``), ``M`` as int32 in the same layout (None unless ``support``)
+    and the int32 device tensor of the iterations every blend's support took."""
+    torch = _torch()
+    lib = _lib.load()
+    table = np.ascontiguousarray(table, DETECT_TASK)
+    n = len(table)
+    n_images, n_coeffs, n_work = detect_table_sizes(table)
+    dev = d_images.device
+    if d_images.dtype not in (torch.float32, torch.float64) or d_images.dim() != 1:
+        raise ValueError("d_images must be a flat float32 or float64 device tensor")
+    if d_images.numel() < n_images:
+        raise ValueError("the tasks reach beyond the packed images")
+    masked = torch.empty(max(n_coeffs, 1), dtype=torch.float64, device=dev)
+    iters = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    M = torch.empty(max(n_coeffs, 1), dtype=torch.int32, device=dev) if support else None
+    if n == 0:
+        return masked, M, iters
+    coeffs = torch.empty(max(n_coeffs, 1), dtype=torch.float64, device=dev)
+    work = torch.empty(max(n_work, 1), dtype=torch.float64, device=dev)
+    nbytes = ctypes.c_int64(0)
+    _lib.check(lib.smi_detect_wavelets_scratch_bytes(n, ctypes.byref(nbytes)))
+    scratch = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+    d_table = torch.from_numpy(table.view(np.uint8)).to(dev)
+    fn = lib.smi_detect_wavelets_f32 if d_images.dtype == torch.float32 else \
+        lib.smi_detect_wavelets_f64
+    with torch.cuda.device(dev):
+        _lib.check(fn(n, table.ctypes.data, _vp(d_table), float(K), float(epsilon),
+                      int(max_iter), int(generation), _vp(d_images), d_images.numel(),
+                      _vp(coeffs), coeffs.numel(), _vp(work), work.numel(), _vp(masked),
+                      _vp(M) if support else None, _vp(iters), _vp(scratch), scratch.numel(),
+                      _stream(torch)))
+    return masked, M, iters
+
+
+# ---------------------------------------------------------------------------
 # the reference's interface
 # ---------------------------------------------------------------------------
 def bspline_convolve(image, scale):
