@@ -998,6 +998,63 @@ int smi_footprints_device_fetch_f64(const double *d_images, int32_t P, int32_t H
                                     int32_t *bounds, uint8_t *masks, int32_t *peak_start,
                                     int32_t *peak_yx, double *peak_flux, void *stream);
 
+/* The same footprints and peaks for a ragged list of n_planes device planes whose frames differ
+ * and that may lie anywhere in device memory (footprints_batch.hip): one chain of launches and
+ * one wait per call, whatever n_planes; every plane's results equal those of
+ * smi_footprints_device_* for that plane alone, exactly.  `table` is host memory, one record per
+ * plane:
+ *   address     device address of the plane's first pixel, [h][w] contiguous
+ *   h, w        > 0, h * w <= INT32_MAX
+ *   pixel_off   exclusive prefix over the planes of h * w
+ *   tile0       ... of ceil(h / 64) * ceil(w / 64)
+ *   chunk0      ... of ceil(h * w / 2048)
+ * The prefixes are checked against the shapes (SMI_ERR_INVALID), so are a NULL table, an empty
+ * plane and totals beyond INT32_MAX.
+ *
+ * smi_footprints_batch_label_*: counts[n_planes][3] = per plane (footprints, mask bytes, strict
+ * maxima), as the per-frame call.  d_work: smi_footprints_batch_work_bytes(n_planes, table)
+ * bytes; the call uploads the table into it, and it holds labels and records until the fetch.
+ * Eight launches (seven when every plane is a single 64 x 64 tile), one wait.
+ *
+ * smi_footprints_batch_fetch_* fills, for all planes at once and in plane order, the arrays of
+ * smi_footprints_fetch: bounds[n][4] and masks[] with n = the sum of counts[..][0];
+ * fp_start[n_planes + 1] = first footprint of every plane; peak_start[n + 1] = first peak of
+ * every footprint in peak_yx[..][2] / peak_flux[..] (capacity: the sum of counts[..][2];
+ * peak_start[n] are kept after the min_separation filter).  d_scratch:
+ * smi_footprints_batch_fetch_bytes(n_planes, counts) bytes.  Three launches, one wait.
+ *
+ * stats (may be NULL): stats[0] = kernel launches, stats[1] = stream synchronisations the call
+ * made.  The two *_bytes functions are arithmetic and need no device; the others return
+ * SMI_ERR_NO_DEVICE without one. */
+typedef struct smi_footprint_plane {
+    uint64_t address;
+    int32_t h, w;
+    int64_t pixel_off, tile0, chunk0;
+} smi_footprint_plane;
+int smi_footprints_batch_work_bytes(int32_t n_planes, const smi_footprint_plane *table,
+                                    int64_t *bytes);
+int smi_footprints_batch_fetch_bytes(int32_t n_planes, const int32_t *counts, int64_t *bytes);
+int smi_footprints_batch_label_f32(const smi_footprint_plane *table, int32_t n_planes,
+                                   int32_t min_area, int32_t thresh, void *d_work,
+                                   int64_t work_bytes, int32_t *counts, int32_t *stats,
+                                   void *stream);
+int smi_footprints_batch_label_f64(const smi_footprint_plane *table, int32_t n_planes,
+                                   int32_t min_area, int32_t thresh, void *d_work,
+                                   int64_t work_bytes, int32_t *counts, int32_t *stats,
+                                   void *stream);
+int smi_footprints_batch_fetch_f32(const smi_footprint_plane *table, int32_t n_planes,
+                                   double min_separation, const int32_t *counts,
+                                   const void *d_work, void *d_scratch, int64_t scratch_bytes,
+                                   int32_t *bounds, uint8_t *masks, int32_t *fp_start,
+                                   int32_t *peak_start, int32_t *peak_yx, double *peak_flux,
+                                   int32_t *stats, void *stream);
+int smi_footprints_batch_fetch_f64(const smi_footprint_plane *table, int32_t n_planes,
+                                   double min_separation, const int32_t *counts,
+                                   const void *d_work, void *d_scratch, int64_t scratch_bytes,
+                                   int32_t *bounds, uint8_t *masks, int32_t *fp_start,
+                                   int32_t *peak_start, int32_t *peak_yx, double *peak_flux,
+                                   int32_t *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,14 @@ _FP_FETCH = ([ctypes.c_void_p] + [ctypes.c_int32] * 4 + [ctypes.c_double, c_i32p
                                                          c_u8p, c_i32p, c_i32p, c_f64p,
                                                          ctypes.c_void_p])
 
+# smi_footprints_batch_label_* / _fetch_*: the plane table (numpy records of
+# detect_pybind11.FOOTPRINT_PLANE) as void *, stats as int32[2] or None
+_FPB_LABEL = [ctypes.c_void_p] + [ctypes.c_int32] * 3 + [ctypes.c_void_p, ctypes.c_int64, c_i32p,
+                                                         c_i32p, ctypes.c_void_p]
+_FPB_FETCH = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, c_i32p, ctypes.c_void_p,
+              ctypes.c_void_p, ctypes.c_int64, c_i32p, c_u8p, c_i32p, c_i32p, c_i32p, c_f64p,
+              c_i32p, ctypes.c_void_p]
+
 
 def _REWEIGHT(fp):
     """smi_reweight_*: device, C, kh, kw, then (count, table) of the blend, source and
@@ -346,6 +354,12 @@ SYMBOLS = {
     "smi_footprints_device_label_f64": (ctypes.c_int, _FP_LABEL),
     "smi_footprints_device_fetch_f32": (ctypes.c_int, _FP_FETCH),
     "smi_footprints_device_fetch_f64": (ctypes.c_int, _FP_FETCH),
+    "smi_footprints_batch_work_bytes": (ctypes.c_int, [ctypes.c_int32, ctypes.c_void_p, c_i64p]),
+    "smi_footprints_batch_fetch_bytes": (ctypes.c_int, [ctypes.c_int32, c_i32p, c_i64p]),
+    "smi_footprints_batch_label_f32": (ctypes.c_int, _FPB_LABEL),
+    "smi_footprints_batch_label_f64": (ctypes.c_int, _FPB_LABEL),
+    "smi_footprints_batch_fetch_f32": (ctypes.c_int, _FPB_FETCH),
+    "smi_footprints_batch_fetch_f64": (ctypes.c_int, _FPB_FETCH),
 }
 SYMBOLS.update(_LITE_INIT())
 SYMBOLS.update(_DETECT_BATCH())

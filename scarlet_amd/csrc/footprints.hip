@@ -1,6 +1,8 @@
 // Footprints and peaks of device-resident detection planes: what csrc/detect.cpp computes on the
 // host, for a batch of P planes [P][H][W] (float32 or float64) that never leave the device.
-// Everything is integer-exact, so the results equal the host code's bit for bit.
+// Everything is integer-exact, so the results equal the host code's bit for bit.  The device
+// code of the rules is footprints_device.h; footprints_batch.hip runs it for planes of
+// different frames.
 //
 // The rules, per pixel (no patch of a footprint is ever formed):
 //   label    a footprint's label is the smallest linear index y*W + x among its pixels
@@ -45,17 +47,10 @@
 #include <vector>
 
 #include "common.h"
+#include "footprints_device.h"  // the rules themselves, shared with footprints_batch.hip
 
 namespace smi {
 namespace {
-
-constexpr int kTile = 64;           // tile side = wavefront width
-constexpr int kRows = 4;            // wavefronts per workgroup
-constexpr int kT = 64 * kRows;      // threads per workgroup
-constexpr int kChunk = kT * 8;      // pixels per scan chunk
-constexpr int kMaxGrid = 65535;
-constexpr int kRec = 7;             // int32 arrays per plane beside the labels
-enum { R_Y0 = 0, R_Y1, R_X0, R_X1, R_AREA, R_RANK, R_MOFF };
 
 struct PeakDev {
     int32_t rank, lin;
@@ -69,9 +64,6 @@ struct Work {
     long long *part;  // [P][nchunk][2]: kept roots, box pixels of a chunk (then their prefixes)
     long long *tot;   // [P][4]: kept, mask bytes, peaks
 };
-
-__host__ __device__ inline int64_t nchunks(int64_t N) { return (N + kChunk - 1) / kChunk; }
-inline int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 
 int64_t work_bytes(int64_t P, int64_t N) {
     return align16(P * N * 4) + align16(P * kRec * N * 4) + align16(P * nchunks(N) * 16) + P * 32;
@@ -90,140 +82,27 @@ Work carve(void *d_work, int64_t P, int64_t N) {
     return w;
 }
 
-__device__ __forceinline__ int ld_agent(const int32_t *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// root of i on the global parent array: parents are strictly smaller, a root is its own
-__device__ __forceinline__ int find_global(const int32_t *par, int i) {
-    int p;
-    while ((p = ld_agent(par + i)) != i) i = p;
-    return i;
-}
-
-// unite the sets of a and b; the larger root is hung under the smaller.  When the atomic min
-// returns something other than the root we held, another union got there first and its value
-// still has to be united with ours: max(a, b) is smaller at every retry.
-__device__ void union_global(int32_t *par, int a, int b) {
-    for (;;) {
-        a = find_global(par, a);
-        b = find_global(par, b);
-        if (a == b) return;
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = __hip_atomic_fetch_min(par + a, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == a) return;
-        a = old;
-    }
-}
-
-__device__ __forceinline__ int ld_lds(const int *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-__device__ __forceinline__ int find_lds(int *lab, int i) {
-    const int start = i;
-    int p;
-    while ((p = ld_lds(lab + i)) != i) i = p;
-    // shorten the next walk; a min, so that a concurrent union's smaller parent stays
-    if (start != i) atomicMin(lab + start, i);
-    return i;
-}
-
-__device__ void union_lds(int *lab, int a, int b) {
-    for (;;) {
-        a = find_lds(lab, a);
-        b = find_lds(lab, b);
-        if (a == b) return;
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = atomicMin(lab + a, b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
 // pass 1.  grid (tiles_x, min(tiles_y, kMaxGrid), P), block (64, kRows)
 template <typename T>
 __global__ __launch_bounds__(kT) void tile_label_kernel(const T *images, int H, int W, double th,
                                                         int32_t *parent, int tiles_y) {
     __shared__ int lab[kTile * kTile];
-    const int lane = threadIdx.x, wy = threadIdx.y;
     const int64_t N = (int64_t)H * W;
     const T *im = images + (int64_t)blockIdx.z * N;
     int32_t *par = parent + (int64_t)blockIdx.z * N;
-    const int x = blockIdx.x * kTile + lane;
-    constexpr int kPer = kTile / kRows;
-    for (int ty = blockIdx.y; ty < tiles_y; ty += gridDim.y) {
-        const int ybase = ty * kTile;
-        for (int r = 0; r < kPer; ++r) {
-            const int ly = wy * kPer + r, y = ybase + ly;
-            const bool fg = x < W && y < H && ((double)im[(int64_t)y * W + x] > th);
-            const unsigned long long m = __ballot(fg);
-            // first pixel of this lane's horizontal run: one past the highest clear bit below
-            const unsigned long long below = ~m & ((1ull << lane) - 1ull);
-            const int s = below ? 64 - __clzll((long long)below) : 0;
-            lab[ly * kTile + lane] = fg ? ly * kTile + s : -1;
-        }
-        __syncthreads();
-        for (int r = 0; r < kPer; ++r) {
-            const int ly = wy * kPer + r, i = ly * kTile + lane;
-            if (ly == 0) continue;
-            // the sign of a label never changes, so these reads need no ordering
-            const bool fg = ld_lds(lab + i) >= 0, up = ld_lds(lab + i - kTile) >= 0;
-            const bool left = lane > 0 && ld_lds(lab + i - 1) >= 0 &&
-                              ld_lds(lab + i - kTile - 1) >= 0;
-            if (fg && up && !left) union_lds(lab, i, i - kTile);
-        }
-        __syncthreads();
-        for (int r = 0; r < kPer; ++r) {
-            const int ly = wy * kPer + r, y = ybase + ly, i = ly * kTile + lane;
-            if (x >= W || y >= H) continue;
-            int out = -1;
-            if (lab[i] >= 0) {
-                int root = i, p;
-                while ((p = lab[root]) != root) root = p;
-                out = (ybase + root / kTile) * W + blockIdx.x * kTile + root % kTile;
-            }
-            par[(int64_t)y * W + x] = out;
-        }
-        __syncthreads();
-    }
+    for (int ty = blockIdx.y; ty < tiles_y; ty += gridDim.y)
+        label_tile<T>(im, par, H, W, th, blockIdx.x, ty, lab);
 }
 
-// pass 2.  Border pixels of a plane: first the (tiles_x - 1) * H pixels left of which a tile
-// ends, then the (tiles_y - 1) * W pixels above which one ends.  grid (blocks, P)
+// pass 2.  grid (blocks, P)
 __global__ __launch_bounds__(kT) void merge_borders_kernel(int32_t *parent, int H, int W,
                                                            int tiles_x, int tiles_y) {
     const int64_t N = (int64_t)H * W;
     int32_t *par = parent + (int64_t)blockIdx.y * N;
     const int64_t nv = (int64_t)(tiles_x - 1) * H, nh = (int64_t)(tiles_y - 1) * W;
     for (int64_t k = (int64_t)blockIdx.x * kT + threadIdx.x; k < nv + nh;
-         k += (int64_t)gridDim.x * kT) {
-        int x, y, q;
-        bool first;
-        if (k < nv) {
-            x = (int)(k / H + 1) * kTile;
-            y = (int)(k % H);
-            q = y * W + x - 1;
-            // the pixel above belongs to the same two tiles unless a tile row starts here
-            first = y % kTile == 0 || ld_agent(par + q + 1 - W) < 0 || ld_agent(par + q - W) < 0;
-        } else {
-            const int64_t j = k - nv;
-            y = (int)(j / W + 1) * kTile;
-            x = (int)(j % W);
-            q = (y - 1) * W + x;
-            first = x % kTile == 0 || ld_agent(par + y * W + x - 1) < 0 || ld_agent(par + q - 1) < 0;
-        }
-        const int p = y * W + x;
-        if (first && ld_agent(par + p) >= 0 && ld_agent(par + q) >= 0) union_global(par, p, q);
-    }
+         k += (int64_t)gridDim.x * kT)
+        merge_border_pixel(par, H, W, nv, k);
 }
 
 // pass 3.  2-D mapping of passes 3, 4, 8 and the peak kernels: grid (ceil(W / 64),
@@ -234,22 +113,8 @@ __global__ __launch_bounds__(kT) void flatten_kernel(int32_t *label, int32_t *re
     int32_t *rc = rec + (int64_t)blockIdx.z * kRec * N;
     const int x = blockIdx.x * 64 + threadIdx.x;
     if (x >= W) return;
-    for (int y = blockIdx.y * kRows + threadIdx.y; y < H; y += gridDim.y * kRows) {
-        const int p = y * W + x;
-        if (ld_agent(lab + p) < 0) continue;
-        const int root = find_global(lab, p);
-        // any value a concurrent find reads here, old or new, is an ancestor of p
-        __hip_atomic_store(lab + p, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (root == p) {
-            rc[R_Y0 * N + p] = H;
-            rc[R_Y1 * N + p] = -1;
-            rc[R_X0 * N + p] = W;
-            rc[R_X1 * N + p] = -1;
-            rc[R_AREA * N + p] = 0;
-            rc[R_RANK * N + p] = -1;
-            rc[R_MOFF * N + p] = 0;
-        }
-    }
+    for (int y = blockIdx.y * kRows + threadIdx.y; y < H; y += gridDim.y * kRows)
+        flatten_pixel(lab, rc, N, H, W, y * W + x);
 }
 
 // pass 4
@@ -258,145 +123,26 @@ __global__ __launch_bounds__(kT) void records_kernel(const int32_t *label, int32
     const int64_t N = (int64_t)H * W;
     const int32_t *lab = label + (int64_t)blockIdx.z * N;
     int32_t *rc = rec + (int64_t)blockIdx.z * kRec * N;
-    const int lane = threadIdx.x, xbase = blockIdx.x * 64, x = xbase + lane;
-    // no lane leaves early: the ballots below need the whole wavefront
-    for (int y = blockIdx.y * kRows + threadIdx.y; y < H; y += gridDim.y * kRows) {
-        const int L = x < W ? lab[(int64_t)y * W + x] : -1;
-        unsigned long long rem = __ballot(L >= 0);
-        while (rem) {  // one round per distinct label of the wavefront
-            const int leader = __ffsll((long long)rem) - 1;
-            const int Ll = __shfl(L, leader, 64);
-            const unsigned long long m = __ballot(L == Ll);
-            if (lane == leader) {
-                atomicMin(rc + R_Y0 * N + Ll, y);
-                atomicMax(rc + R_Y1 * N + Ll, y);
-                atomicMin(rc + R_X0 * N + Ll, xbase + leader);
-                atomicMax(rc + R_X1 * N + Ll, xbase + 63 - __clzll((long long)m));
-                atomicAdd(rc + R_AREA * N + Ll, __popcll(m));
-            }
-            rem &= ~m;
-        }
-    }
+    // no lane leaves early: the ballots of record_row need the whole wavefront
+    for (int y = blockIdx.y * kRows + threadIdx.y; y < H; y += gridDim.y * kRows)
+        record_row(lab, rc, N, W, y, blockIdx.x * 64);
 }
 
-__device__ __forceinline__ bool kept_root(const int32_t *rc, int64_t N, int p, int min_area,
-                                          long long *box) {
-    const long long h = rc[R_Y1 * N + p] - rc[R_Y0 * N + p] + 1;
-    const long long w = rc[R_X1 * N + p] - rc[R_X0 * N + p] + 1;
-    *box = h * w;
-    return h * w > (long long)min_area && rc[R_AREA * N + p] >= min_area;
-}
-
-// exclusive scan of one value per thread over the workgroup, in thread order; *total = the sum
-__device__ long long block_scan(long long v, long long *sh, long long *total) {
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    long long inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long u = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += u;
-    }
-    if (lane == 63) sh[wave] = inc;
-    __syncthreads();
-    long long base = 0, tot = 0;
-    for (int k = 0; k < kT / 64; ++k) {
-        if (k < wave) base += sh[k];
-        tot += sh[k];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
-// passes 5 and 7.  grid (nchunk, P), block kT (1-D); thread t owns 8 consecutive pixels.
-// FINAL 0: part[chunk] = (kept roots, their box pixels).  FINAL 1: part holds the exclusive
-// prefixes; rank and mask offset of every kept root.
+// passes 5 and 7.  grid (nchunk, P), block kT (1-D)
 template <int FINAL>
 __global__ __launch_bounds__(kT) void rank_kernel(const int32_t *label, int32_t *rec, int64_t N,
                                                   int min_area, long long *part) {
     __shared__ long long sh[kT / 64];
-    const int32_t *lab = label + (int64_t)blockIdx.y * N;
-    int32_t *rc = rec + (int64_t)blockIdx.y * kRec * N;
-    long long *pt = part + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 2;
-    const int64_t p0 = (int64_t)blockIdx.x * kChunk + threadIdx.x * 8;
-    long long cnt = 0, pix = 0, box[8];
-    bool keep[8];
-    for (int k = 0; k < 8; ++k) {
-        const int64_t p = p0 + k;
-        keep[k] = p < N && lab[p] == (int)p && kept_root(rc, N, (int)p, min_area, &box[k]);
-        if (keep[k]) {
-            ++cnt;
-            pix += box[k];
-        }
-    }
-    long long tc, tp;
-    long long ec = block_scan(cnt, sh, &tc);
-    long long ep = block_scan(pix, sh, &tp);
-    if (!FINAL) {
-        if (threadIdx.x == 0) {
-            pt[0] = tc;
-            pt[1] = tp;
-        }
-        return;
-    }
-    ec += pt[0];
-    ep += pt[1];
-    for (int k = 0; k < 8; ++k)
-        if (keep[k]) {
-            rc[R_RANK * N + p0 + k] = (int32_t)ec++;
-            // wraps only when the plane's total does, which the caller refuses
-            rc[R_MOFF * N + p0 + k] = (int32_t)(uint32_t)ep;
-            ep += box[k];
-        }
+    rank_chunk<FINAL>(label + (int64_t)blockIdx.y * N, rec + (int64_t)blockIdx.y * kRec * N, N,
+                      min_area, part + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 2,
+                      blockIdx.x, sh);
 }
 
-// pass 6.  One workgroup per plane: the chunk sums become exclusive prefixes, the totals go
-// to tot[plane][0..1]; tot[plane][2] (peaks) is zeroed for pass 8
+// pass 6.  One workgroup per plane
 __global__ __launch_bounds__(kT) void chunk_scan_kernel(long long *part, int64_t nchunk,
                                                         long long *tot) {
     __shared__ long long sh[kT / 64];
-    long long *pt = part + (int64_t)blockIdx.x * nchunk * 2;
-    const int64_t seg = (nchunk + kT - 1) / kT;
-    int64_t a = threadIdx.x * seg, b = a + seg;
-    if (a > nchunk) a = nchunk;
-    if (b > nchunk) b = nchunk;
-    long long cnt = 0, pix = 0;
-    for (int64_t c = a; c < b; ++c) {
-        cnt += pt[2 * c];
-        pix += pt[2 * c + 1];
-    }
-    long long tc, tp;
-    long long ec = block_scan(cnt, sh, &tc);
-    long long ep = block_scan(pix, sh, &tp);
-    for (int64_t c = a; c < b; ++c) {
-        const long long vc = pt[2 * c], vp = pt[2 * c + 1];
-        pt[2 * c] = ec;
-        pt[2 * c + 1] = ep;
-        ec += vc;
-        ep += vp;
-    }
-    if (threadIdx.x == 0) {
-        tot[4 * blockIdx.x] = tc;
-        tot[4 * blockIdx.x + 1] = tp;
-        tot[4 * blockIdx.x + 2] = 0;
-    }
-}
-
-// the peak rule for pixel (y, x) of footprint L (a kept root)
-template <typename T>
-__device__ __forceinline__ bool is_peak(const T *im, const int32_t *lab, const int32_t *rc,
-                                        int64_t N, int W, int y, int x, int L, T v) {
-    const int y0 = rc[R_Y0 * N + L], y1 = rc[R_Y1 * N + L];
-    const int x0 = rc[R_X0 * N + L], x1 = rc[R_X1 * N + L];
-    for (int dy = -1; dy <= 1; ++dy)
-        for (int dx = -1; dx <= 1; ++dx) {
-            if (!dy && !dx) continue;
-            const int a = y + dy, b = x + dx;
-            if (a < y0 || a > y1 || b < x0 || b > x1) continue;  // the box lies in the image
-            const int64_t q = (int64_t)a * W + b;
-            const T n = lab[q] == L ? im[q] : T(0);
-            if (!(v > n)) return false;
-        }
-    return true;
+    scan_chunk_sums(part + (int64_t)blockIdx.x * nchunk * 2, nchunk, tot + 4 * blockIdx.x, sh);
 }
 
 // pass 8 (EMIT 0): tot[plane][2] += peaks, one add per wavefront.  Fetch (EMIT 1), one plane:
@@ -413,17 +159,9 @@ __global__ __launch_bounds__(kT) void peaks_kernel(const T *images, const int32_
     const int32_t *rc = rec + (int64_t)blockIdx.z * kRec * N;
     const int lane = threadIdx.x, x = blockIdx.x * 64 + lane;
     for (int y = blockIdx.y * kRows + threadIdx.y; y < H; y += gridDim.y * kRows) {
-        bool peak = false;
         int rank = -1;
         T v = T(0);
-        if (x < W) {
-            const int64_t p = (int64_t)y * W + x;
-            const int L = lab[p];
-            if (L >= 0 && (rank = rc[R_RANK * N + L]) >= 0) {
-                v = im[p];
-                peak = is_peak<T>(im, lab, rc, N, W, y, x, L, v);
-            }
-        }
+        const bool peak = x < W && peak_at<T>(im, lab, rc, N, W, y, x, &rank, &v);
         const unsigned long long m = __ballot(peak);
         if (!m) continue;
         const int leader = __ffsll((long long)m) - 1;
@@ -474,20 +212,7 @@ __global__ __launch_bounds__(kT) void masks_kernel(const int32_t *lab, int W, co
         if ((int64_t)moff[mid] <= k) lo = mid;
         else hi = mid - 1;
     }
-    const int y0 = bounds[4 * lo], x0 = bounds[4 * lo + 2];
-    const int w = bounds[4 * lo + 3] - x0 + 1;
-    const int64_t j = k - moff[lo];
-    const int y = y0 + (int)(j / w), x = x0 + (int)(j % w);
-    masks[k] = lab[(int64_t)y * W + x] == roots[lo] ? 1 : 0;
-}
-
-int have_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        set_error("no HIP device available");
-        return SMI_ERR_NO_DEVICE;
-    }
-    return SMI_OK;
+    masks[k] = mask_byte(lab, W, bounds + 4 * lo, roots[lo], k - moff[lo]);
 }
 
 dim3 grid2d(int P, int H, int W) {
@@ -622,36 +347,14 @@ int fetch_plane(const T *d_images, int32_t P, int32_t H, int32_t W, int32_t plan
     SMI_HIP(hipStreamSynchronize(st));
     SMI_REQUIRE(emitted == (unsigned int)np, "footprints: the images changed since they were labelled");
 
-    // the order of detect.cpp: per footprint brightest first, equal fluxes in raster order
+    // the order of detect.cpp, then its min_separation filter (footprints_device.h)
     std::sort(pk.begin(), pk.end(), [](const PeakDev &a, const PeakDev &b) {
         if (a.rank != b.rank) return a.rank < b.rank;
-        if (a.flux != b.flux) return a.flux > b.flux;
-        return a.lin < b.lin;
+        return peak_before(a, b);
     });
-    const double min2 = min_separation * min_separation;
-    int32_t k = 0;
-    size_t i = 0;
-    for (int32_t f = 0; f < n; ++f) {
-        peak_start[f] = k;
-        size_t e = i;
-        while (e < pk.size() && pk[e].rank == f) ++e;
-        const bool filter = min_separation > 0 && e - i > 1;
-        for (; i < e; ++i) {
-            const int32_t y = pk[i].lin / W, x = pk[i].lin - y * W;
-            bool ok = true;
-            if (filter)
-                for (int32_t j = peak_start[f]; j < k && ok; ++j) {
-                    const double dy = (double)peak_yx[2 * j] - y, dx = (double)peak_yx[2 * j + 1] - x;
-                    if (dy * dy + dx * dx < min2) ok = false;
-                }
-            if (!ok) continue;
-            peak_yx[2 * k] = y;
-            peak_yx[2 * k + 1] = x;
-            peak_flux[k] = pk[i].flux;
-            ++k;
-        }
-    }
-    peak_start[n] = k;
+    select_peaks(
+        pk, n, [](const PeakDev &p) { return p.rank; }, [W](const PeakDev &) { return W; },
+        min_separation, peak_start, peak_yx, peak_flux);
     return SMI_OK;
 }
 

@@ -5,7 +5,9 @@ support -- run on the GPU in one device-resident chain; ``get_detect_wavelets_ba
 them for a catalogue of blends of different frames in one chain per dtype
 (``csrc/detect_batch.hip``).  Footprints and peaks of coefficients
 that stay on the device (``get_detect_wavelets(..., device=True)``) are found there too
-(``detect_pybind11.get_footprints_device``); host arrays take the host code
+(``detect_pybind11.get_footprints_device``), and ``get_peaks_batch`` /
+``get_blend_structures_batch`` find them for a whole catalogue in one chain
+(``get_footprints_batch``, ``csrc/footprints_batch.hip``); host arrays take the host code
 (``get_footprints``).  The structures that connect the footprints across scales are plain
 Python over ``Box``es, as in the reference.  ``QuadTreeRegion.query`` returns a ``set`` as the
 reference does, so the order in which ``get_peaks`` lists the peaks is the reference's.
@@ -15,7 +17,8 @@ Display helpers (``draw_*``, matplotlib) are not part of this package.
 import numpy as np
 
 from .bbox import Box, overlapped_slices
-from .detect_pybind11 import get_footprints, get_footprints_device, _is_device_tensor
+from .detect_pybind11 import (get_footprints, get_footprints_device, get_footprints_batch,
+                              _is_device_tensor)
 from . import wavelet
 
 
@@ -319,17 +322,74 @@ def get_blend_trees(detect):
     return trees, all_footprints
 
 
+def _structures(all_footprints, frame):
+    """``get_blend_structures`` from the footprints of the first three scales of a ``frame``"""
+    low, middle = all_footprints[:2]
+    low_tree = QuadTreeRegion(Box(frame), capacity=10).add_footprints(low)
+    middle_tree = QuadTreeRegion(Box(frame), capacity=10).add_footprints(middle)
+    structures = [SingleScaleStructure(2, fp).add_scale_tree(0, low_tree)
+                  .add_scale_tree(1, middle_tree) for fp in all_footprints[2]]
+    return structures, middle_tree
+
+
 def get_blend_structures(detect):
     """Structures of the third wavelet scale, each with the overlapping footprints of the first
     two scales, and the quad tree of the second scale.  Returns
     ``(high_structures, middle_tree)`` (the reference's effective definition)."""
-    all_footprints = _scale_footprints(detect)
-    low, middle = all_footprints[:2]
-    low_tree = QuadTreeRegion(Box(detect.shape[-2:]), capacity=10).add_footprints(low)
-    middle_tree = QuadTreeRegion(Box(detect.shape[-2:]), capacity=10).add_footprints(middle)
-    structures = [SingleScaleStructure(2, fp).add_scale_tree(0, low_tree)
-                  .add_scale_tree(1, middle_tree) for fp in all_footprints[2]]
-    return structures, middle_tree
+    return _structures(_scale_footprints(detect), detect.shape[-2:])
+
+
+def _checked_blends(detects, name):
+    """The list of a catalogue's detection coefficients, refused before any device work when
+    one is no device tensor or has fewer than the four planes the structures need."""
+    detects = list(detects)
+    for i, d in enumerate(detects):
+        if not _is_device_tensor(d):
+            raise TypeError("%s: the blend at position %d is no torch device tensor but %s "
+                            "(host arrays go through get_peaks, blend by blend)"
+                            % (name, i, type(d).__name__))
+    for i, d in enumerate(detects):
+        shape = tuple(d.shape)
+        if len(shape) != 3 or shape[0] < 4:
+            raise ValueError("%s: the blend at position %d has shape %s; (planes, Ny, Nx) with "
+                             "at least four planes is needed (scales=3 of a frame that allows "
+                             "them)" % (name, i, shape))
+    return detects
+
+
+def get_blend_structures_batch(detects):
+    """``[get_blend_structures(d) for d in detects]`` for a catalogue of device tensors
+    ``(planes, Ny, Nx)`` whose frames may differ: the footprints of scales 0 .. 2 of every
+    blend come from one ``get_footprints_batch``; the quad trees and structures are built on
+    the host from the same footprints in the same order, so every structure, peak and query
+    order is the per-blend call's.  Raises ``TypeError`` for host arrays and ``ValueError``,
+    naming the position, for a blend with fewer than four planes."""
+    detects = _checked_blends(detects, "get_blend_structures_batch")
+    found = get_footprints_batch([d[s] for d in detects for s in range(3)],
+                                 min_separation=0, min_area=4, thresh=0)
+    return [_structures(found[3 * k:3 * k + 3], tuple(d.shape[-2:]))
+            for k, d in enumerate(detects)]
+
+
+def get_peaks_batch(detects, bboxes=None):
+    """``[get_peaks(d, bbox=b) for d, b in zip(detects, bboxes)]`` for a catalogue of device
+    tensors ``(planes, Ny, Nx)`` whose frames may differ (``bboxes``: one entry per blend, or
+    ``None`` for every blend's whole frame).  ``get_peaks`` reads the middle tree only, so one
+    ``get_footprints_batch`` labels scale 1 of every blend and nothing else.  Raises as
+    ``get_blend_structures_batch``."""
+    detects = _checked_blends(detects, "get_peaks_batch")
+    bboxes = [None] * len(detects) if bboxes is None else list(bboxes)
+    if len(bboxes) != len(detects):
+        raise ValueError("get_peaks_batch: {} blends and {} boxes".format(len(detects),
+                                                                          len(bboxes)))
+    found = get_footprints_batch([d[1] for d in detects], min_separation=0, min_area=4, thresh=0)
+    out = []
+    for d, bbox, middle in zip(detects, bboxes, found):
+        frame = tuple(d.shape[1:])
+        tree = QuadTreeRegion(Box(frame), capacity=10).add_footprints(middle)
+        bbox = Box(frame) if bbox is None else bbox[1:]
+        out.append([(peak.y, peak.x) for box in tree.query(bbox) for peak in box.footprint.peaks])
+    return out
 
 
 def get_peaks(detect=None, images=None, variance=None, bbox=None, scales=3):

@@ -4,8 +4,9 @@
 with a branch at every pixel); ``get_footprints_device`` gives the same answer for planes
 that are on the GPU already (``csrc/footprints.hip``: union-find labelling, records, masks
 and peaks as kernels, only the footprints' records cross to the host);
-``get_connected_pixels`` and ``get_peaks`` are the single-footprint helpers of the same
-module, here in NumPy.
+``get_footprints_batch`` does so for a list of device planes of different shapes in one chain
+of launches (``csrc/footprints_batch.hip``); ``get_connected_pixels`` and ``get_peaks`` are
+the single-footprint helpers of the same module, here in NumPy.
 
 Where the reference's behaviour is undefined, this module defines it: equal-flux peaks keep
 raster order (a stable sort), ``min_separation > 0`` keeps peaks brightest first and drops
@@ -194,6 +195,180 @@ def get_footprints_device(d_image, min_separation, min_area, thresh):
     found = [_footprint_objects(*fetch_device(planes, k, min_separation, counts, work))
              for k in range(planes.shape[0])]
     return found if d_image.dim() == 3 else found[0]
+
+
+# ---------------------------------------------------------------------------
+# get_footprints_device for a ragged list of planes: one device chain per chunk
+# ---------------------------------------------------------------------------
+# Bytes of one chunk's work buffer (labels, records, scan sums: 32 bytes per pixel and a little
+# more): a group whose planes need more is cut into chunks.
+FOOTPRINT_BATCH_BYTES = 1 << 30
+_TILE, _CHUNK = 64, 2048  # kTile and kChunk of csrc/footprints_device.h
+
+# one plane of smi_footprints_batch_*: ``smi_footprint_plane`` of include/scarlet_amd.h
+FOOTPRINT_PLANE = np.dtype([("address", np.uint64), ("h", np.int32), ("w", np.int32),
+                            ("pixel_off", np.int64), ("tile0", np.int64), ("chunk0", np.int64)])
+
+
+def footprint_plane_table(shapes, addresses):
+    """The plane table of ``smi_footprints_batch_*`` for planes of ``shapes`` = ``(h, w)`` at
+    the device ``addresses``: the exclusive prefixes over the planes of their pixels, 64 x 64
+    tiles and scan chunks of 2048 pixels."""
+    shapes = [(int(h), int(w)) for h, w in shapes]
+    table = np.zeros(len(shapes), dtype=FOOTPRINT_PLANE)
+    table["address"] = np.asarray(list(addresses), dtype=np.uint64)
+    pixels = tiles = chunks = 0
+    for k, (h, w) in enumerate(shapes):
+        table[k]["h"], table[k]["w"] = h, w
+        table[k]["pixel_off"], table[k]["tile0"], table[k]["chunk0"] = pixels, tiles, chunks
+        pixels += h * w
+        tiles += -(-h // _TILE) * -(-w // _TILE)
+        chunks += -(-h * w // _CHUNK)
+    return table
+
+
+def _plane_work_bytes(h, w):
+    """bytes one plane adds to the work buffer: eight int32 per pixel, its chunk sums, its table
+    record, border prefix and totals"""
+    return 32 * h * w + 16 * -(-h * w // _CHUNK) + 80
+
+
+_CHUNK_BYTES = 80  # of a chunk whatever it holds: roundings to 16 bytes, the prefix's last entry
+
+
+def _plane_dtype(plane):
+    name = str(plane.dtype).replace("torch.", "")
+    if name not in ("float32", "float64"):
+        raise TypeError("footprints: float32 or float64 planes are needed, got %s" % plane.dtype)
+    return np.dtype(name)
+
+
+def plan_footprints_batch(planes, _max_bytes=None):
+    """``groups`` of ``get_footprints_batch``, without touching the GPU: per dtype of the planes
+    (float32, float64), in order of first appearance, the chunks of one device chain each --
+    lists of input positions in input order whose work buffer stays within
+    ``FOOTPRINT_BATCH_BYTES`` (a plane beyond the budget is a chunk of its own).  ``planes``:
+    anything with ``.shape``, ``.dtype`` and ``.device``.  Raises ``TypeError`` for host arrays
+    and other dtypes, ``ValueError`` for planes that are not 2-D, empty planes and planes on
+    different devices."""
+    max_bytes = FOOTPRINT_BATCH_BYTES if _max_bytes is None else _max_bytes
+    groups, used, device = {}, {}, None
+    for i, p in enumerate(planes):
+        if isinstance(p, np.ndarray) or not all(hasattr(p, a) for a in ("shape", "dtype", "device")) \
+                or str(p.device).startswith("cpu"):
+            raise TypeError("footprints: plane %d is no device tensor but %s (host arrays go "
+                            "through get_footprints)" % (i, type(p).__name__))
+        dtype = _plane_dtype(p)
+        shape = tuple(int(v) for v in p.shape)
+        if len(shape) != 2:
+            raise ValueError("footprints: plane %d is not 2-D, its shape is %s" % (i, shape))
+        if shape[0] == 0 or shape[1] == 0:
+            raise ValueError("footprints: plane %d is empty, its shape is %s" % (i, shape))
+        if device is None:
+            device = str(p.device)
+        elif str(p.device) != device:
+            raise ValueError("footprints: plane %d is on %s, the planes before it on %s"
+                             % (i, p.device, device))
+        need = _plane_work_bytes(*shape)
+        chunks = groups.setdefault(dtype, [[]])
+        if chunks[-1] and used[dtype] + need > max_bytes:
+            chunks.append([])
+            used[dtype] = _CHUNK_BYTES
+        chunks[-1].append(i)
+        used[dtype] = used.get(dtype, _CHUNK_BYTES) + need
+    return groups
+
+
+def label_batch_device(planes, min_area, thresh):
+    """First step of :func:`get_footprints_batch` for the contiguous 2-D device tensors
+    ``planes`` of one dtype: one labelling chain for all of them.  Returns ``(table, counts,
+    work, stats)``: the plane table, the ``(len(planes), 3)`` int32 array (footprints, mask
+    bytes, strict maxima), the device buffer :func:`fetch_batch_device` reads and ``(kernel
+    launches, stream synchronisations)`` of the call."""
+    import torch
+
+    lib = _lib.load()
+    table = footprint_plane_table([p.shape for p in planes], [p.data_ptr() for p in planes])
+    n, device = len(planes), planes[0].device
+    nbytes = ctypes.c_int64(0)
+    _lib.check(lib.smi_footprints_batch_work_bytes(n, ctypes.c_void_p(table.ctypes.data),
+                                                   ctypes.byref(nbytes)))
+    work = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    counts = np.zeros((n, 3), dtype=np.int32)
+    stats = np.zeros(2, dtype=np.int32)
+    fn = lib.smi_footprints_batch_label_f32 if planes[0].dtype == torch.float32 else \
+        lib.smi_footprints_batch_label_f64
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    with torch.cuda.device(device):
+        _lib.check(fn(ctypes.c_void_p(table.ctypes.data), n, int(min_area), int(thresh),
+                      ctypes.c_void_p(work.data_ptr()), nbytes.value,
+                      _lib.ptr(counts, ctypes.c_int32), _lib.ptr(stats, ctypes.c_int32), stream))
+    return table, counts, work, (int(stats[0]), int(stats[1]))
+
+
+def fetch_batch_device(planes, table, min_separation, counts, work):
+    """Second step: ``(per_plane, stats)`` -- for every plane the arrays ``(bounds, masks,
+    peak_start, peak_yx, peak_flux)`` in the layout of ``smi_footprints_fetch`` (``peak_start``
+    indexes the arrays all planes share) -- from one fetch chain for all planes."""
+    import torch
+
+    lib = _lib.load()
+    n, device = len(planes), planes[0].device
+    n_fp, n_mask, n_peaks = (int(v) for v in counts.sum(axis=0, dtype=np.int64))
+    bounds = np.zeros((n_fp, 4), dtype=np.int32)
+    masks = np.zeros(n_mask, dtype=np.uint8)
+    fp_start = np.zeros(n + 1, dtype=np.int32)
+    start = np.zeros(n_fp + 1, dtype=np.int32)
+    yx = np.zeros((n_peaks, 2), dtype=np.int32)
+    flux = np.zeros(n_peaks, dtype=np.float64)
+    stats = np.zeros(2, dtype=np.int32)
+    nbytes = ctypes.c_int64(0)
+    _lib.check(lib.smi_footprints_batch_fetch_bytes(n, _lib.ptr(counts, ctypes.c_int32),
+                                                    ctypes.byref(nbytes)))
+    scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    fn = lib.smi_footprints_batch_fetch_f32 if planes[0].dtype == torch.float32 else \
+        lib.smi_footprints_batch_fetch_f64
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    with torch.cuda.device(device):
+        _lib.check(fn(ctypes.c_void_p(table.ctypes.data), n, float(min_separation),
+                      _lib.ptr(counts, ctypes.c_int32), ctypes.c_void_p(work.data_ptr()),
+                      ctypes.c_void_p(scratch.data_ptr()), nbytes.value,
+                      _lib.ptr(bounds, ctypes.c_int32), _lib.ptr(masks, ctypes.c_uint8),
+                      _lib.ptr(fp_start, ctypes.c_int32), _lib.ptr(start, ctypes.c_int32),
+                      _lib.ptr(yx, ctypes.c_int32), _lib.ptr(flux, ctypes.c_double),
+                      _lib.ptr(stats, ctypes.c_int32), stream))
+    mask_start = np.concatenate([[0], np.cumsum(counts[:, 1], dtype=np.int64)])
+    per_plane = [(bounds[fp_start[k]:fp_start[k + 1]], masks[mask_start[k]:mask_start[k + 1]],
+                  start[fp_start[k]:fp_start[k + 1] + 1], yx, flux) for k in range(n)]
+    return per_plane, (int(stats[0]), int(stats[1]))
+
+
+def get_footprints_batch(planes, min_separation, min_area, thresh, _max_bytes=None, _stats=None):
+    """``[get_footprints_device(p, min_separation, min_area, thresh) for p in planes]`` for a
+    list of 2-D float32 / float64 device tensors whose shapes and dtypes may differ, equal in
+    every bound, mask byte, peak position and peak flux: per chunk of
+    ``plan_footprints_batch`` one labelling and one fetch call (``csrc/footprints_batch.hip``)
+    whose numbers of launches and of waits do not depend on the number of planes.  Views into
+    other tensors are read where they lie; planes that are not contiguous are copied first, as
+    ``get_footprints_device`` does.  ``_stats``: a list that receives, per chunk, the
+    ``(launches, synchronisations)`` pairs of the two calls."""
+    planes = list(planes)
+    for i, p in enumerate(planes):
+        if not _is_device_tensor(p):
+            raise TypeError("get_footprints_batch: plane %d is no torch device tensor but %s "
+                            "(host arrays go through get_footprints)" % (i, type(p).__name__))
+    groups = plan_footprints_batch(planes, _max_bytes)
+    out = [None] * len(planes)
+    for chunks in groups.values():
+        for chunk in chunks:
+            held = [planes[i].contiguous() for i in chunk]
+            table, counts, work, label_stats = label_batch_device(held, min_area, thresh)
+            per_plane, fetch_stats = fetch_batch_device(held, table, min_separation, counts, work)
+            for i, arrays in zip(chunk, per_plane):
+                out[i] = _footprint_objects(*arrays)
+            if _stats is not None:
+                _stats.append((label_stats, fetch_stats))
+    return out
 
 
 def get_connected_pixels(i, j, image, unchecked, footprint, bounds, thresh=0):
