@@ -30,6 +30,22 @@ void set_error(const std::string &msg);
         }                                                                          \
     } while (0)
 
+// Entry points that launch kernels refuse, after their argument checks, a host without a GPU.
+inline int have_device() {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        set_error("no HIP device available");
+        return SMI_ERR_NO_DEVICE;
+    }
+    return SMI_OK;
+}
+
+// Do the `need` elements at offset `off` lie in a buffer of `size` elements?  (A ragged task
+// table names its slices this way.)
+inline bool in_buffer(int64_t off, int64_t need, int64_t size) {
+    return off >= 0 && need >= 0 && off <= size && need <= size - off;
+}
+
 // Raise a kernel's dynamic-LDS limit to `lds` bytes on the CURRENT device.  Function
 // attributes live per device, so one process driving several GPUs (fit_blends(devices=...))
 // has to configure each of them; `configured` is the caller's static per-kernel table.

@@ -8,16 +8,14 @@
 //
 // Every blend's numbers are those of the per-image chain of starlet.hip for that blend alone
 // (smi_coadd_* -> smi_starlet_transform_* -> smi_multiresolution_support_f64 with n = 1), bit
-// for bit:
-//   coadd     ((b0 + b1) + b2) ... in the images' type, then to float64 as plane 0
-//   passes    the tap arithmetic and order of bspline_pass_kernel; a tap whose neighbour lies
-//             outside this blend's image is skipped; a task with scales <= j leaves at once
+// for bit: the arithmetic is shared with starlet.hip through starlet_device.h.
+//   coadd     the sum of the bands in the images' type, then to float64 as plane 0
+//   passes    a task with scales <= j leaves at once
 //   support   one workgroup owns a blend and runs all of its iterations, convergence test
-//             included.  The per-image call sums a plane in nb = max(1, min(ceil(2048 / planes),
-//             ceil(npix / 2048))) blocks of 256 threads and adds the partials in a final block;
-//             the workgroup here walks those nb blocks one after another -- the same pixels per
-//             thread, the same block_sum, the same final sum -- so sigma_j, the iteration count
-//             and every mask bit equal the per-image call's whatever the data
+//             included.  The per-image call sums a plane in support_blocks() blocks and adds
+//             the partials in a final block; the workgroup here walks those blocks one after
+//             another, so sigma_j, the iteration count and every mask bit equal the per-image
+//             call's whatever the data
 //   mask      M and M * w from the thresholds the support kernel left in the scratch
 //
 // The limit: one workgroup reads planes * npix coefficients twice per iteration.  At 65536
@@ -30,17 +28,17 @@
 #include <algorithm>
 
 #include "common.h"
+#include "starlet_device.h"
 
 namespace smi {
 namespace {
 
-constexpr int kT = 256;
+constexpr int kT = kSupportT;
 constexpr int kWaves = kT / 64;
 constexpr int32_t kMaxScales = 30;
 constexpr int kThrSlots = 32;                        // thresholds of a task in the scratch
 constexpr int64_t kMaxPixels = 1 << 16;              // pixels of a frame
 constexpr int kMaxVirtual = kMaxPixels / (8 * kT);   // virtual blocks per plane
-constexpr double H0 = 1.0 / 16, H1 = 1.0 / 4, H2 = 3.0 / 8, H3 = 1.0 / 4, H4 = 1.0 / 16;
 constexpr int kWork = -1, kNone = -2;                // plane selectors of the pass kernel
 
 // ---------------------------------------------------------------------------- coadd
@@ -52,14 +50,12 @@ __global__ __launch_bounds__(kT) void detect_coadd_kernel(const smi_detect_task 
     const T *in = images + t.image_off;
     double *out = coeffs + t.coeff_off;
     for (int p = blockIdx.x * kT + threadIdx.x; p < npix; p += gridDim.x * kT) {
-        T acc = in[p];
-        for (int b = 1; b < t.bands; ++b) acc = acc + in[(int64_t)b * npix + p];
-        out[p] = (double)acc;
+        out[p] = (double)strided_sum(in + p, t.bands, npix);
     }
 }
 
 // ---------------------------------------------------------------------------- passes
-// One 1-D B-spline pass at spacing 2^j over every task with more than j scales.  `in`, `out`,
+// One 1-D B-spline pass of scale j over every task with more than j scales.  `in`, `out`,
 // `diff` select a plane of the task's coefficients, its work plane (kWork) or nothing (kNone):
 //   out  : out[p] = conv        diff : diff[p] = diff[p] - conv
 // out / diff never select the plane `in` reads.
@@ -75,16 +71,8 @@ __global__ __launch_bounds__(kT) void detect_pass_kernel(const smi_detect_task *
     const int y = p / t.w, x = p - y * t.w;
     double *base = coeffs + t.coeff_off, *wk = work + t.work_off;
     const double *c = (in_sel == kWork ? wk : base + (int64_t)in_sel * npix) + p;
-    const int64_t u = AXIS == 0 ? y : x;
-    const int64_t L = AXIS == 0 ? t.h : t.w;
-    const int64_t s = AXIS == 0 ? t.w : 1;
-    // a spacing of max(h, w) or more reaches no neighbour, the same result as 2^j
-    const int64_t d1 = min(1 << j, max(t.h, t.w)), d2 = 2 * d1;
-    double acc = c[0] * H2;
-    if (u >= d2) acc = acc + c[-d2 * s] * H0;
-    if (u >= d1) acc = acc + c[-d1 * s] * H1;
-    if (u + d1 < L) acc = acc + c[d1 * s] * H3;
-    if (u + d2 < L) acc = acc + c[d2 * s] * H4;
+    const double acc =
+        bspline_tap<AXIS, double, int64_t>(c, y, x, t.h, t.w, bspline_spacing(j, t.h, t.w));
     if (out_sel != kNone) (out_sel == kWork ? wk : base + (int64_t)out_sel * npix)[p] = acc;
     if (diff_sel != kNone) {
         double *d = base + (int64_t)diff_sel * npix + p;
@@ -93,21 +81,8 @@ __global__ __launch_bounds__(kT) void detect_pass_kernel(const smi_detect_task *
 }
 
 // ---------------------------------------------------------------------------- support
-// sum over a block in a fixed order: block_sum of starlet.hip
-__device__ double block_sum(double v, double *sh) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    double t = 0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < kWaves; ++w) t += sh[w];
-    __syncthreads();
-    return t;
-}
-
-// The host loop of multiresolution_support (starlet.hip) for the blend of this workgroup.
-// PASS 0 of a plane: mean of v = w * (|w| <= thr); PASS 1: sum of (v - mean)^2.
+// The multiresolution support of the blend of this workgroup.  Pass 0 of a plane: mean of
+// v = w * ~M; pass 1: sum of (v - mean)^2.
 __global__ __launch_bounds__(kT) void detect_support_kernel(const smi_detect_task *tasks,
                                                             const double *coeffs, double K,
                                                             double epsilon, int max_iter,
@@ -119,8 +94,7 @@ __global__ __launch_bounds__(kT) void detect_support_kernel(const smi_detect_tas
     __shared__ int s_done;
     const smi_detect_task t = tasks[blockIdx.x];
     const int planes = t.scales + 1, npix = t.h * t.w, tid = threadIdx.x;
-    const int want = (2048 + planes - 1) / planes, cap = (npix + 8 * kT - 1) / (8 * kT);
-    const int nb = max(1, min(want, cap));  // <= kMaxVirtual: npix <= kMaxPixels
+    const int nb = support_blocks<int>(planes, npix);  // <= kMaxVirtual: npix <= kMaxPixels
     const double *w0 = coeffs + t.coeff_off;
     if (tid < planes) {
         s_thr[tid] = t.thresh0;
@@ -135,17 +109,8 @@ __global__ __launch_bounds__(kT) void detect_support_kernel(const smi_detect_tas
                 const double thr = s_thr[k];
                 const double m = pass ? s_mean[k] : 0.0;
                 for (int vb = 0; vb < nb; ++vb) {  // block vb of the per-image call's grid
-                    double acc = 0;
-                    for (int q = vb * kT + tid; q < npix; q += nb * kT) {
-                        const double x = w[q];
-                        const double v = x * (fabs(x) > thr ? 0.0 : 1.0);
-                        if (pass) {
-                            const double e = v - m;
-                            acc += e * e;
-                        } else {
-                            acc += v;
-                        }
-                    }
+                    const double acc =
+                        support_partial<int>(w, vb * kT + tid, nb * kT, npix, thr, pass, m);
                     const double s = block_sum(acc, sh);
                     if (tid == 0) part[vb] = s;
                 }
@@ -163,23 +128,9 @@ __global__ __launch_bounds__(kT) void detect_support_kernel(const smi_detect_tas
             __syncthreads();
         }
         iters = it + 1;
-        if (tid == 0) {
-            // sigma_j = std(w * ~M); converged when every non-zero sigma moved by < epsilon
-            // (a NaN sigma fails `> 0` and leaves the test)
-            bool conv = true;
-            for (int k = 0; k < planes; ++k) {
-                const double sig = sqrt(s_ss[k] / (double)npix);
-                s_mean[k] = sig;  // (the means are not read again)
-                if (sig > 0 && !(fabs(sig - s_last[k]) / sig < epsilon)) conv = false;
-            }
-            // not converged at max_iter: the thresholds of the last iteration stay
-            if (!conv && it + 1 < max_iter)
-                for (int k = 0; k < planes; ++k) {
-                    s_last[k] = s_mean[k];
-                    s_thr[k] = K * s_mean[k];
-                }
-            s_done = conv;
-        }
+        if (tid == 0)
+            s_done = support_converged(s_ss, planes, (double)npix, K, epsilon, it + 1 == max_iter,
+                                       s_last, s_thr);
         __syncthreads();
         if (s_done) break;
     }
@@ -187,8 +138,7 @@ __global__ __launch_bounds__(kT) void detect_support_kernel(const smi_detect_tas
     if (tid == 0) iterations[blockIdx.x] = iters;
 }
 
-// M = |w| > thr as int, and M * w (float64, -0.0 for a negative w outside the support, as the
-// reference's int * float product)
+// M = |w| > thr as int, and M * w
 __global__ __launch_bounds__(kT) void detect_mask_kernel(const smi_detect_task *tasks,
                                                          const double *coeffs, const double *thr,
                                                          int32_t *M, double *Mw) {
@@ -197,26 +147,13 @@ __global__ __launch_bounds__(kT) void detect_mask_kernel(const smi_detect_task *
     const double *th = thr + (int64_t)blockIdx.y * kThrSlots;
     for (int e = blockIdx.x * kT + threadIdx.x; e < n; e += gridDim.x * kT) {
         const double x = coeffs[t.coeff_off + e];
-        const int m = fabs(x) > th[e / npix] ? 1 : 0;
+        const int m = support_member(x, th[e / npix]);
         if (M) M[t.coeff_off + e] = m;
-        Mw[t.coeff_off + e] = (double)m * x;
+        Mw[t.coeff_off + e] = support_masked(m, x);
     }
 }
 
 // ---------------------------------------------------------------------------- host
-inline bool in_buffer(int64_t off, int64_t need, int64_t size) {
-    return off >= 0 && need >= 0 && off <= size && need <= size - off;
-}
-
-int have_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        set_error("no HIP device available");
-        return SMI_ERR_NO_DEVICE;
-    }
-    return SMI_OK;
-}
-
 unsigned blocks_for(int64_t n) { return (unsigned)((n + kT - 1) / kT); }
 
 template <typename T>

@@ -330,15 +330,6 @@ __device__ __forceinline__ uint8_t mask_byte(const int32_t *lab, int W, const in
     return lab[(int64_t)y * W + x] == root ? 1 : 0;
 }
 
-inline int have_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        set_error("no HIP device available");
-        return SMI_ERR_NO_DEVICE;
-    }
-    return SMI_OK;
-}
-
 // The order of detect.cpp inside a footprint: brightest first, equal fluxes in raster order
 template <typename Rec>
 inline bool peak_before(const Rec &a, const Rec &b) {

@@ -273,22 +273,9 @@ __global__ __launch_bounds__(kThreads) void fit_kernel(const smi_lite_init_fit *
 }
 
 // ---------------------------------------------------------------------------- host checks
-inline bool in_buffer(int64_t off, int64_t need, int64_t size) {
-    return off >= 0 && need >= 0 && off <= size && need <= size - off;
-}
-
 #define SMI_TABLES(n, host, dev)                                                   \
     SMI_REQUIRE((n) >= 0, "negative count");                                       \
     SMI_REQUIRE(((host) && (dev)) || (n) == 0, "null descriptor table")
-
-int have_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        set_error("no HIP device available");
-        return SMI_ERR_NO_DEVICE;
-    }
-    return SMI_OK;
-}
 
 template <typename T>
 int init_coadd(int32_t n, const smi_lite_init_coadd *tasks, const void *d_tasks,

@@ -4,11 +4,11 @@
 //
 // B_j (bspline_convolve, wavelet.py:154-191) is the separable 5-tap B-spline
 // (1/16, 1/4, 3/8, 1/4, 1/16) at spacing d = 2^j with zeros outside the image: first along
-// axis 0, then along axis 1, each pixel summed in the reference's order
-//   ((((x*h2 + x[-2d]*h0) + x[-d]*h1) + x[+d]*h3) + x[+2d]*h4)
-// where a term whose neighbour lies outside the image is skipped.  The reference computes in
-// float64 (a float32 image times an np.float64 tap is float64 under NumPy 2), and this file is
-// compiled without FMA contraction, so the coefficients are the reference's bit for bit.
+// axis 0, then along axis 1, each pixel summed in the reference's order (bspline_tap of
+// starlet_device.h, which holds the arithmetic this file shares with detect_batch.hip).  The
+// reference computes in float64 (a float32 image times an np.float64 tap is float64 under
+// NumPy 2), and this file is compiled without FMA contraction, so the coefficients are the
+// reference's bit for bit.
 //
 // One kernel does a 1-D pass along either axis.  Both read the five taps straight from
 // global memory: along axis 0 a wavefront reads five rows y-2d .. y+2d at the same 64
@@ -22,18 +22,16 @@
 // The multiresolution support ("ground" branch, wavelet.py:381-407) runs its per-plane
 // standard deviations on the device as deterministic two-pass float64 reductions; the
 // convergence test on a handful of numbers per iteration stays on the host.
-#include <algorithm>
-#include <cmath>
 #include <vector>
 
 #include "common.h"
+#include "starlet_device.h"
 
 namespace smi {
 namespace {
 
-constexpr int kT = 256;
+constexpr int kT = kSupportT;
 constexpr int kMaxGridY = 65535;
-constexpr double H0 = 1.0 / 16, H1 = 1.0 / 4, H2 = 3.0 / 8, H3 = 1.0 / 4, H4 = 1.0 / 16;
 
 template <typename T>
 __global__ __launch_bounds__(kT) void to_f64_kernel(const T *in, double *out, int64_t n) {
@@ -57,16 +55,7 @@ __global__ __launch_bounds__(kT) void bspline_pass_kernel(const double *__restri
     if (x >= W) return;
     for (int64_t row = blockIdx.y; row < rows; row += gridDim.y) {
         const int64_t p = row * W + x;
-        const int64_t u = AXIS == 0 ? row % H : x;
-        const int64_t L = AXIS == 0 ? H : W;
-        const int64_t s = AXIS == 0 ? (int64_t)W : 1;
-        const int64_t d1 = d, d2 = 2 * d1;
-        const double *c = in + p;
-        double acc = c[0] * H2;
-        if (u >= d2) acc = acc + c[-d2 * s] * H0;
-        if (u >= d1) acc = acc + c[-d1 * s] * H1;
-        if (u + d1 < L) acc = acc + c[d1 * s] * H3;
-        if (u + d2 < L) acc = acc + c[d2 * s] * H4;
+        const double acc = bspline_tap<AXIS, double, int64_t>(in + p, row % H, x, H, W, d);
         if (out) out[p] = addend ? acc + addend[p] : acc;
         if (diff) diff[p] = diff[p] - acc;
     }
@@ -77,38 +66,20 @@ __global__ __launch_bounds__(kT) void plane_sum_kernel(const double *in, int pla
                                                        int64_t plane, double *out) {
     const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
     if (i >= plane) return;
-    double acc = in[i];
-    for (int k = 1; k < planes; ++k) acc = acc + in[(int64_t)k * plane + i];
-    out[i] = acc;
+    out[i] = strided_sum(in + i, planes, plane);
 }
 
-// np.sum(images, axis=0) of the bands: ((b0 + b1) + b2) ... in the images' own type
+// np.sum(images, axis=0) of the bands, in the images' own type
 template <typename T>
 __global__ __launch_bounds__(kT) void coadd_kernel(const T *in, int bands, int64_t plane,
                                                    T *out) {
     const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
     if (i >= plane) return;
-    T acc = in[i];
-    for (int b = 1; b < bands; ++b) acc = acc + in[(int64_t)b * plane + i];
-    out[i] = acc;
+    out[i] = strided_sum(in + i, bands, plane);
 }
 
-// sum over a block in a fixed order (the same bits on every run)
-__device__ double block_sum(double v, double *sh) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    double t = 0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < kT / 64; ++w) t += sh[w];
-    __syncthreads();
-    return t;
-}
-
-// Plane pl = b * planes + k (image b, scale k) of the coefficients.  v = w * (|w| <= thr):
-// starlets * (~M).astype(int) of the reference.  PASS 0 sums v, PASS 1 sums (v - mean)^2.
-// Block partials go to part[pl * gridDim.x + blockIdx.x].
+// Plane pl = b * planes + k (image b, scale k) of the coefficients: PASS 0 sums v = w * ~M,
+// PASS 1 sums (v - mean)^2.  Block partials go to part[pl * gridDim.x + blockIdx.x].
 template <int PASS>
 __global__ __launch_bounds__(kT) void support_stat_kernel(const double *coeffs, int planes,
                                                           int64_t plane_stride,
@@ -118,19 +89,9 @@ __global__ __launch_bounds__(kT) void support_stat_kernel(const double *coeffs, 
     __shared__ double sh[kT / 64];
     const int pl = blockIdx.y, b = pl / planes, k = pl - b * planes;
     const double *w = coeffs + k * plane_stride + b * image_stride;
-    const double t = thr[pl];
-    const double m = PASS ? mean[pl] : 0.0;
-    double acc = 0;
-    for (int64_t q = (int64_t)blockIdx.x * kT + threadIdx.x; q < npix; q += (int64_t)gridDim.x * kT) {
-        const double x = w[q];
-        const double v = x * (fabs(x) > t ? 0.0 : 1.0);
-        if (PASS) {
-            const double e = v - m;
-            acc += e * e;
-        } else {
-            acc += v;
-        }
-    }
+    const double acc = support_partial<int64_t>(w, (int64_t)blockIdx.x * kT + threadIdx.x,
+                                                (int64_t)gridDim.x * kT, npix, thr[pl], PASS,
+                                                PASS ? mean[pl] : 0.0);
     const double s = block_sum(acc, sh);
     if (threadIdx.x == 0) part[(int64_t)pl * gridDim.x + blockIdx.x] = s;
 }
@@ -147,8 +108,7 @@ __global__ __launch_bounds__(kT) void support_final_kernel(const double *part, i
     if (threadIdx.x == 0) res[pl] = PASS ? s : s / (double)npix;
 }
 
-// M = |w| > thr as int, and M * w (float64, -0.0 for a negative w outside the support, as
-// the reference's int * float product)
+// M = |w| > thr as int, and M * w
 __global__ __launch_bounds__(kT) void support_mask_kernel(const double *coeffs, int planes,
                                                           int64_t plane_stride,
                                                           int64_t image_stride, int64_t npix,
@@ -159,19 +119,10 @@ __global__ __launch_bounds__(kT) void support_mask_kernel(const double *coeffs, 
     const double t = thr[pl];
     for (int64_t q = (int64_t)blockIdx.x * kT + threadIdx.x; q < npix; q += (int64_t)gridDim.x * kT) {
         const double x = coeffs[off + q];
-        const int m = fabs(x) > t ? 1 : 0;
+        const int m = support_member(x, t);
         if (M) M[off + q] = m;
-        if (Mw) Mw[off + q] = (double)m * x;
+        if (Mw) Mw[off + q] = support_masked(m, x);
     }
-}
-
-int have_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        set_error("no HIP device available");
-        return SMI_ERR_NO_DEVICE;
-    }
-    return SMI_OK;
 }
 
 template <int AXIS>
@@ -187,9 +138,7 @@ int bspline_pass(const double *in, int rows, int H, int W, int d, double *out,
 // B_j(in) -> out (+ addend) and/or diff -= B_j(in); `tmp` holds the axis-0 pass
 int bspline(const double *in, int rows, int H, int W, int j, double *tmp, double *out,
             const double *addend, double *diff, hipStream_t st) {
-    // a spacing of max(H, W) or more reaches no neighbour along either axis, the same
-    // result as 2^j (j <= 30 is admitted); the kernel forms 2 * d in 64 bits
-    const int d = std::min(1 << j, std::max(H, W));
+    const int d = bspline_spacing(j, H, W);  // the kernel forms 2 * d in 64 bits
     int rc = bspline_pass<0>(in, rows, H, W, d, tmp, nullptr, nullptr, st);
     if (rc) return rc;
     return bspline_pass<1>(tmp, rows, H, W, d, out, addend, diff, st);
@@ -281,10 +230,7 @@ int multiresolution_support(const double *d_coeffs, int32_t n, int32_t planes, i
     hipStream_t st = (hipStream_t)stream;
     const int np = n * planes;
     const int64_t npix = (int64_t)H * W;
-    // enough blocks per plane to fill the chip, at least ~8 pixels per thread
-    int64_t want = (2048 + np - 1) / np;
-    const int64_t cap = (npix + 8 * kT - 1) / (8 * kT);
-    const int nb = (int)std::max<int64_t>(1, std::min(want, cap));
+    const int nb = (int)support_blocks<int64_t>(np, npix);
 
     DevBuf<double> d_thr, d_mean, d_ss, d_part;
     SMI_HIP(d_thr.alloc(np));
@@ -313,24 +259,11 @@ int multiresolution_support(const double *d_coeffs, int32_t n, int32_t planes, i
         for (int b = 0; b < n; ++b) {
             if (done[b]) continue;
             iters[b] = it + 1;
-            // sigma_j = std(w * ~M); converged when every non-zero sigma moved by < epsilon
-            bool conv = true;
-            std::vector<double> sig(planes);
-            for (int k = 0; k < planes; ++k) {
-                sig[k] = std::sqrt(ss[b * planes + k] / (double)npix);
-                if (sig[k] > 0 && !(std::fabs(sig[k] - last[b * planes + k]) / sig[k] < epsilon))
-                    conv = false;
-            }
-            if (conv) {
-                done[b] = 1;  // its mask is the one of this iteration's thresholds
-                continue;
-            }
-            if (it + 1 < max_iter)
-                for (int k = 0; k < planes; ++k) {
-                    last[b * planes + k] = sig[k];
-                    thr[b * planes + k] = K * sig[k];
-                }
-            all_done = false;
+            const int o = b * planes;
+            // converged: its mask is the one of this iteration's thresholds
+            done[b] = support_converged(&ss[o], planes, (double)npix, K, epsilon,
+                                        it + 1 == max_iter, &last[o], &thr[o]);
+            if (!done[b]) all_done = false;
         }
         if (all_done) break;
     }

@@ -32,13 +32,13 @@
 
 #include "common.h"
 #include "mask_device.h"
+#include "starlet_device.h"
 
 namespace smi {
 namespace {
 
 constexpr int kT = kMaskT;
 constexpr int kWaves = kT / 64;
-constexpr float H0 = 1.0f / 16, H1 = 1.0f / 4, H2 = 3.0f / 8;
 // reduction scratch in front of the work planes: kWaves doubles x 2 + kWaves floats, then the
 // shared words of the monotonic mask operator, padded
 constexpr int kRedBytes = 512;
@@ -97,23 +97,13 @@ template <int AXIS>
 __device__ void bspline_pass(const float *in, float *out, const float *addend, int h, int w,
                              int d) {
     const int N = h * w;
-    const int L = AXIS == 0 ? h : w, s = AXIS == 0 ? w : 1;
-    const int d1 = d, d2 = 2 * d;
     for (int i = threadIdx.x; i < N; i += kT) {
         const int y = i / w, x = i - y * w;
-        const int u = AXIS == 0 ? y : x;
-        float acc = in[i] * H2;
-        if (u >= d2) acc += in[i - d2 * s] * H0;
-        if (u >= d1) acc += in[i - d1 * s] * H1;
-        if (u + d1 < L) acc += in[i + d1 * s] * H1;
-        if (u + d2 < L) acc += in[i + d2 * s] * H0;
+        const float acc = bspline_tap<AXIS, float, int>(in + i, y, x, h, w, d);
         out[i] = addend ? acc + addend[i] : acc;
     }
     __syncthreads();
 }
-
-// a spacing of max(h, w) or more reaches no neighbour: the same result as 2^j, no overflow
-__device__ __forceinline__ int spacing(int j, int h, int w) { return min(1 << min(j, 20), max(h, w)); }
 
 struct StarCtx {
     int k, b, h, w, N, P;
@@ -184,7 +174,7 @@ __global__ __launch_bounds__(kT) void starlet_step_kernel(BatchView v, StarletVi
     __syncthreads();
     // 2. the cascade: plane j + 1 = B_j plane j
     for (int j = 0; j < S; ++j) {
-        const int d = spacing(j, c.h, c.w);
+        const int d = bspline_spacing(j, c.h, c.w);
         bspline_pass<0>(grad + (int64_t)j * N, c.work0, nullptr, c.h, c.w, d);
         bspline_pass<1>(c.work0, grad + (int64_t)(j + 1) * N, nullptr, c.h, c.w, d);
     }
@@ -325,7 +315,7 @@ __global__ __launch_bounds__(kT) void starlet_forward_kernel(BatchView v, Starle
     if (S == 0)
         for (int i = threadIdx.x; i < N; i += kT) out[i] = cur[i];
     for (int j = S - 1; j >= 0; --j) {
-        const int d = spacing(j, c.h, c.w);
+        const int d = bspline_spacing(j, c.h, c.w);
         float *dst = j == 0 ? out : c.work0;
         bspline_pass<0>(cur, c.work1, nullptr, c.h, c.w, d);
         bspline_pass<1>(c.work1, dst, coeffs + (int64_t)j * N, c.h, c.w, d);
