@@ -238,6 +238,63 @@ int smi_lite_init_fit_f64(int32_t C, int32_t n, const smi_lite_init_fit *tasks, 
                           int32_t images_f64, int64_t n_image, const double *d_stamps,
                           int64_t n_stamp, double *d_out, int64_t n_out, void *stream);
 
+/* lite.init_blends_main: the scarlet-main initialisation of scarlet.lite (reference
+ * lite/initialization.py:188-247, 321-419 with use_mask=False) for a catalogue of blends, with
+ * the conventions of smi_lite_init_* above, whose snr, taps, crop and fit entries it shares.  A
+ * chunk takes at most eight launches, whatever its blends and sources: main_coadd, snr, taps of
+ * the detection images, taps of the model PSFs, main_sweep, crop, main_split, fit.
+ *   main_coadd  detect[p] = sum over the bands, in order, of images[c][p] / nr2[c], all in the
+ *               data type (np.sum(images / noise_rms**2, axis=0))
+ *   main_sweep  per source, one workgroup with the frame in LDS (at most (160 KiB - 1 KiB) /
+ *               sizeof(T) pixels): prox_uncentered_symmetry(X, 0, centre, "sdss"), then
+ *               prox_weighted_monotonic(shape, "angle", min_gradient=0, centre), then
+ *               X[~(X > thresh)] = 0, compared in double.  d_cos is the table of
+ *               cos(arctan2(-Y, -X) - arctan2(dy_i, dx_i)) over the offsets |Y| <= ry, |X| <= rx
+ *               from the centre, [2 ry + 1][2 rx + 1][8] doubles in the reference's neighbour
+ *               order, which covers every frame of the table (h - 1 <= ry, w - 1 <= rx).  Per
+ *               task the swept plane, the bounds (min row, max row, min col, max col) of its
+ *               pixels > 0 -- (0, -1, 0, -1) without any -- and its maximum
+ *   main_split  of a cut-out normalised to maximum 1: bulge = max(morph - level, 0) and
+ *               disk = min(morph, level), level cast to the data type, each divided by its own
+ *               maximum; all three live in d_morphs */
+typedef struct smi_lite_init_main_coadd {
+    int32_t bands, reserved;
+    int64_t n_pix, image_off, nr2_off, detect_off;
+} smi_lite_init_main_coadd;
+typedef struct smi_lite_init_main_sweep {
+    int32_t h, w, cy, cx;
+    int64_t plane_off, out_off;
+    double thresh;
+} smi_lite_init_main_sweep;
+typedef struct smi_lite_init_main_split {
+    int32_t bh, bw;
+    int64_t morph_off, bulge_off, disk_off;
+} smi_lite_init_main_split;
+int smi_lite_init_main_coadd_f32(int32_t n, const smi_lite_init_main_coadd *tasks,
+                                 const void *d_tasks, const float *d_images, int64_t n_image,
+                                 const float *d_nr2, int64_t n_nr2, float *d_detect,
+                                 int64_t n_detect, void *stream);
+int smi_lite_init_main_sweep_f32(int32_t n, const smi_lite_init_main_sweep *tasks,
+                                 const void *d_tasks, const float *d_planes, int64_t n_plane,
+                                 const double *d_cos, int64_t n_cos, int32_t ry, int32_t rx,
+                                 float *d_out, int64_t n_out, int32_t *d_bounds, float *d_peaks,
+                                 int64_t n_results, void *stream);
+int smi_lite_init_main_split_f32(int32_t n, const smi_lite_init_main_split *tasks,
+                                 const void *d_tasks, float *d_morphs, int64_t n_morph,
+                                 double level, void *stream);
+int smi_lite_init_main_coadd_f64(int32_t n, const smi_lite_init_main_coadd *tasks,
+                                 const void *d_tasks, const double *d_images, int64_t n_image,
+                                 const double *d_nr2, int64_t n_nr2, double *d_detect,
+                                 int64_t n_detect, void *stream);
+int smi_lite_init_main_sweep_f64(int32_t n, const smi_lite_init_main_sweep *tasks,
+                                 const void *d_tasks, const double *d_planes, int64_t n_plane,
+                                 const double *d_cos, int64_t n_cos, int32_t ry, int32_t rx,
+                                 double *d_out, int64_t n_out, int32_t *d_bounds, double *d_peaks,
+                                 int64_t n_results, void *stream);
+int smi_lite_init_main_split_f64(int32_t n, const smi_lite_init_main_split *tasks,
+                                 const void *d_tasks, double *d_morphs, int64_t n_morph,
+                                 double level, void *stream);
+
 /* get_valid_monotonic_pixels / linear_interpolate_invalid_pixels
  * (operators_pybind11.cc:61-232, float32 and float64 overload sets; callers
  * operator.py:155-176).  Row-major (rows, cols) images; `unchecked` / `orphans` are the

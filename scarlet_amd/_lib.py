@@ -82,6 +82,10 @@ def _LITE_INIT():
         "masks": table + [v, i64, v, v, v, i64, v, i64, v, v, i64, v],
         "crop": table + [v, i64, v, i64, v, i64, v],
         "fit": [i32] + table + [v, i64, v, i32, i64, v, i64, v, i64, v],
+        # lite.init_blends_main (csrc/lite_init_main.hip)
+        "main_coadd": table + [v, i64, v, i64, v, i64, v],
+        "main_sweep": table + [v, i64, v, i64, i32, i32, v, i64, v, v, i64, v],
+        "main_split": table + [v, i64, ctypes.c_double, v],
     }
     return {"smi_lite_init_%s_%s" % (step, tag): (ctypes.c_int, args)
             for step, args in steps.items() for tag in ("f32", "f64")}

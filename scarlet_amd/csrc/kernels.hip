@@ -12,6 +12,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "rounded_math.h"
 
 namespace smi {
 
@@ -349,19 +350,7 @@ struct Team {
 // Separate multiply and add (no FMA contraction): bit-identical to the
 // reference's sequential loop (operators_pybind11.cc:14-36).
 // ---------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ T mul_rn(T a, T b);
-template <>
-__device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, b); }
-template <>
-__device__ __forceinline__ double mul_rn(double a, double b) { return __dmul_rn(a, b); }
-template <typename T>
-__device__ __forceinline__ T add_rn(T a, T b);
-template <>
-__device__ __forceinline__ float add_rn(float a, float b) { return __fadd_rn(a, b); }
-template <>
-__device__ __forceinline__ double add_rn(double a, double b) { return __dadd_rn(a, b); }
-
+// (mul_rn / add_rn: rounded_math.h)
 template <typename T, typename W, int THREADS = 64>
 __device__ __forceinline__ void sweep_levels(T *img, const int32_t *level_start, int n_levels,
                                              int E, const int32_t *pix, const int32_t *cnt,

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "rounded_math.h"
 #include "mask_device.h"
 
 namespace smi {
@@ -37,14 +38,6 @@ constexpr int32_t kMaxExtent = 1 << 14;    // frame and box sides
 constexpr int64_t kMaxPixels = 1 << 22;    // pixels of a frame the one-workgroup fill takes
 constexpr int32_t kMaxStamp = 255;         // stamp sides
 constexpr int32_t kMaxPlanes = 64;
-
-__device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ double mul_rn(double a, double b) { return __dmul_rn(a, b); }
-__device__ __forceinline__ float add_rn(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ double add_rn(double a, double b) { return __dadd_rn(a, b); }
-// correctly rounded quotient (IEEE division, not the reciprocal approximation)
-__device__ __forceinline__ float div_rn(float a, float b) { return __fdiv_rn(a, b); }
-__device__ __forceinline__ double div_rn(double a, double b) { return __ddiv_rn(a, b); }
 
 // ---------------------------------------------------------------------------- coadd
 template <typename T>

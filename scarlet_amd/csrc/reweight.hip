@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "rounded_math.h"
 
 namespace smi {
 namespace {
@@ -40,14 +41,6 @@ __host__ __device__ inline int halo_pitch(int kw) { return (kTileX + kw - 1) | 1
 inline size_t lds_elems(int kh, int kw) {
     return (size_t)(kTileY + kh - 1) * halo_pitch(kw) + (size_t)kh * kw;
 }
-
-__device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ double mul_rn(double a, double b) { return __dmul_rn(a, b); }
-__device__ __forceinline__ float add_rn(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ double add_rn(double a, double b) { return __dadd_rn(a, b); }
-// correctly rounded quotient (IEEE division, not the reciprocal approximation)
-__device__ __forceinline__ float div_rn(float a, float b) { return __fdiv_rn(a, b); }
-__device__ __forceinline__ double div_rn(double a, double b) { return __ddiv_rn(a, b); }
 
 template <typename T>
 struct ReweightArgs {

@@ -8,6 +8,7 @@ from .initialization import (  # noqa: F401
     init_all_sources_main,
     init_all_sources_wavelets,
     init_blends,
+    init_blends_main,
     init_fista_component,
     init_main_parameters,
     init_monotonic_morph,
@@ -15,6 +16,7 @@ from .initialization import (  # noqa: F401
     multifit_seds,
     parameterize_sources,
     plan_init_blends,
+    plan_init_blends_main,
     WaveletInitParameters,
 )
 from .measure import calculate_snr, weight_blends, weight_sources  # noqa: F401

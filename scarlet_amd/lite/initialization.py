@@ -6,7 +6,10 @@ monotonicity variants (weighted sweep, or ``use_mask=True``: the monotonic mask 
 ``init_all_sources_wavelets`` (lite/initialization.py:422-605) starts from the detection
 coefficients of ``scarlet_amd.detect.get_detect_wavelets`` (starlet transform on the GPU);
 ``init_blends`` is the same initialisation for a catalogue of blends, as device batches
-(csrc/lite_init.hip).
+(csrc/lite_init.hip); ``init_blends_main`` is ``init_all_sources_main`` (weighted sweep) for a
+catalogue of blends: coadd, symmetry, sweep and trim of every source on the device
+(csrc/lite_init_main.hip), with one table of relative cosines per chunk in the place of a weight
+table and a radial sort per source.
 """
 
 from functools import partial
@@ -16,7 +19,8 @@ import numpy as np
 from ..bbox import Box, overlapped_slices
 from ..detect import get_detect_wavelets, get_detect_wavelets_batch
 from ..initialization import get_minimal_boxsize, trim_morphology
-from ..operator import prox_monotonic_mask, prox_uncentered_symmetry, prox_weighted_monotonic
+from ..operator import (NEIGHBOR_COORDS, prox_monotonic_mask, prox_uncentered_symmetry,
+                        prox_weighted_monotonic)
 from ..parameter import relative_step
 from .measure import calculate_snr
 from .models import LiteComponent, LiteFactorizedComponent, LiteSource
@@ -853,4 +857,379 @@ def init_blends(observations, centers, min_snr=50, bulge_grow=5, disk_grow=5, us
         sources[i] = init_all_sources_wavelets(observations[i], centers[i], min_snr, bulge_grow,
                                                disk_grow, use_psf, bulge_slice, disk_slice,
                                                scales, wav)
+    return sources
+
+
+# ---------------------------------------------------------------------------
+# init_blends_main: init_all_sources_main (weighted sweep) for a catalogue, device batches
+# ---------------------------------------------------------------------------
+# lite_init_main.hip: one workgroup sweeps a source with its frame in LDS.  A CU has 160 KiB,
+# all of which one workgroup may take; the kernel keeps 1 KiB of it for its reductions.
+_LDS_BYTES = 160 * 1024
+_LDS_RESERVE = 1024
+
+_MAIN_COADD_DESC = np.dtype([("bands", _i4), ("reserved", _i4), ("n_pix", _i8),
+                             ("image_off", _i8), ("nr2_off", _i8), ("detect_off", _i8)],
+                            align=True)
+_MAIN_SWEEP_DESC = np.dtype([("h", _i4), ("w", _i4), ("cy", _i4), ("cx", _i4),
+                             ("plane_off", _i8), ("out_off", _i8), ("thresh", "f8")], align=True)
+_MAIN_SPLIT_DESC = np.dtype([("bh", _i4), ("bw", _i4), ("morph_off", _i8), ("bulge_off", _i8),
+                             ("disk_off", _i8)], align=True)
+
+
+def _max_sweep_pixels(dtype):
+    """Pixels of the largest frame the sweep kernel holds in LDS."""
+    return (_LDS_BYTES - _LDS_RESERVE) // np.dtype(dtype).itemsize
+
+
+_COSINES = {}
+
+
+def _relative_cosines(ry, rx):
+    """``cos(arctan2(-Y, -X) - arctan2(dy, dx))`` for every offset ``|Y| <= ry``, ``|X| <= rx``
+    of a pixel from its centre and every neighbour ``(dy, dx)``, ``(2 ry + 1, 2 rx + 1, 8)``
+    float64: the expression of ``getRadialMonotonicWeights``, evaluated by NumPy on contiguous
+    arrays as there, so the bits are the same.  It depends on neither the centre nor the
+    frame.  (The last table is kept: the chunks of a catalogue share their largest frame.)"""
+    key = (int(ry), int(rx))
+    if key not in _COSINES:
+        Y = np.repeat(np.arange(-key[0], key[0] + 1), 2 * key[1] + 1)
+        X = np.tile(np.arange(-key[1], key[1] + 1), 2 * key[0] + 1)
+        to_peak = np.arctan2(-Y, -X)
+        table = np.empty((Y.size, 8))
+        for i, (dy, dx) in enumerate(NEIGHBOR_COORDS):
+            table[:, i] = np.cos(to_peak - np.arctan2(float(dy), float(dx)))
+        _COSINES.clear()
+        _COSINES[key] = table.reshape(2 * key[0] + 1, 2 * key[1] + 1, 8)
+    return _COSINES[key]
+
+
+def _sweep_level(Y, X):
+    """Level of the pixel at offset ``(Y, X)`` from the centre in the sweep of
+    lite_init_main.hip: ``2 M + m - 1`` with ``M = max(|Y|, |X|)``, ``m = min(|Y|, |X|)``
+    (-1 for the centre itself).  Every 8-neighbour strictly nearer the centre has a strictly
+    smaller level: on the same ``M`` its ``m`` is one less, on ``M - 1`` its ``m`` is at most
+    one more, and no pixel of ``M + 1`` is nearer."""
+    Y, X = np.abs(Y), np.abs(X)
+    return 2 * np.maximum(Y, X) + np.minimum(Y, X) - 1
+
+
+def _main_key(obs, detect, use_mask, percentile):
+    """``(key, reason)``: the group ``(image dtype, model PSF dtype, bands)`` of a blend the
+    device batch of ``init_blends_main`` takes, or None and why it goes through
+    ``init_all_sources_main``."""
+    if use_mask:
+        return None, "use_mask=True: the mask operators run on the GPU blend by blend"
+    if not 0 < percentile < 100:
+        return None, "percentile outside (0, 100)"
+    shape = np.shape(obs.images)
+    planes = (np.broadcast_to(np.zeros((), np.float64), (1,) + tuple(shape[1:]))
+              if len(shape) == 3 else None)
+    key, reason = _init_key(obs, planes, slice(None), slice(None), 0)
+    if key is None:
+        return None, reason
+    _, idtype, mdtype, C = key
+    h, w = shape[1:]
+    if h * w > _max_sweep_pixels(idtype):
+        return None, ("frame of {} pixels beyond the {} {} pixels of the sweep kernel's LDS image "
+                      "({} KiB per CU less {} KiB)".format(
+                          h * w, _max_sweep_pixels(idtype), idtype.name, _LDS_BYTES // 1024,
+                          _LDS_RESERVE // 1024))
+    if detect is None:
+        noise_rms = np.asarray(obs.noise_rms)
+        if (noise_rms.shape != (C,) or noise_rms.dtype.kind != "f"
+                or np.result_type(idtype, (noise_rms ** 2).dtype) != idtype):
+            return None, "noise_rms would make the coadd another dtype than the images"
+    else:
+        if not isinstance(detect, np.ndarray) or detect.shape != (h, w):
+            return None, "detect is not a 2-D array of the frame's shape"
+        if detect.dtype != idtype:
+            return None, "detect differs from the images in dtype"
+    return (idtype, mdtype, C), None
+
+
+def plan_init_blends_main(observations, centers, detect=None, use_mask=False, percentile=25):
+    """``(groups, fallback)`` of ``init_blends_main``, without touching the GPU: the positions
+    of the blends of every device group, keyed by ``(image dtype, model PSF dtype, bands)`` in
+    order of first appearance and in input order inside a group, and ``(position, reason)`` of
+    the blends that go through ``init_all_sources_main``.  Raises ``ValueError`` for a centre
+    outside its frame, or a catalogue whose arguments differ in length."""
+    observations, centers = list(observations), list(centers)
+    detect = [None] * len(observations) if detect is None else list(detect)
+    if not len(observations) == len(centers) == len(detect):
+        raise ValueError("observations, centers and detect must have one entry per blend, got "
+                         "{}, {} and {}".format(len(observations), len(centers), len(detect)))
+    groups, fallback = {}, []
+    for i, (obs, cs, det) in enumerate(zip(observations, centers, detect)):
+        shape = np.shape(obs.images)
+        if len(shape) == 3:
+            for c in cs:
+                if not (len(c) == 2 and 0 <= c[0] < shape[1] and 0 <= c[1] < shape[2]):
+                    raise ValueError("blend {}: centre {} lies outside its {} x {} frame".format(
+                        i, tuple(c), shape[1], shape[2]))
+        key, reason = _main_key(obs, det, use_mask, percentile)
+        if key is None:
+            fallback.append((i, reason))
+        else:
+            groups.setdefault(key, []).append(i)
+    return groups, fallback
+
+
+def _main_bytes(obs, n_sources, key):
+    """Bytes of the device working set of one blend of ``init_blends_main``: detection image,
+    images and variance; per source the swept plane and up to three cut-outs, counted as a
+    frame each; the stamps in the data type, the model PSF's type and float64; and the table
+    of relative cosines its frame needs, 64 bytes for each of ``(2 h - 1) (2 w - 1)`` offsets
+    (a chunk holds one table, that of its largest frame: this counts it per blend)."""
+    idtype, mdtype, C = key
+    h, w = obs.images.shape[1:]
+    n = h * w
+    stamp = C * int(np.prod(np.shape(obs.diff_kernel.image)[1:]))
+    return ((1 + 2 * C + 4 * n_sources) * n * idtype.itemsize
+            + stamp * (idtype.itemsize + mdtype.itemsize + 8) + 64 * (2 * h - 1) * (2 * w - 1))
+
+
+def _trim_box(bounds, center):
+    """The box ``trim_morphology`` cuts around ``center`` for a morphology whose pixels
+    ``> 0`` have the inclusive ``bounds`` (min row, max row, min col, max col; max < min:
+    none)."""
+    b0, b1, l0, l1 = (int(v) for v in bounds)
+    bbox = Box.from_bounds((b0, b1 + 1), (l0, l1 + 1)) if b1 >= b0 else Box.from_bounds((0, 0), (0, 0))
+    if bbox.contains(center):
+        size = 2 * max(center[0] - bbox.start[-2], bbox.stop[0] - center[-2],
+                       center[1] - bbox.start[-1], bbox.stop[1] - center[-1])
+    else:
+        size = 0
+    half = get_minimal_boxsize(size) // 2
+    return Box.from_bounds((center[0] - half, center[0] + half + 1),
+                           (center[1] - half, center[1] + half + 1))
+
+
+# launches of the last chunk of init_blends_main, by entry (tools/lite_init_main_time.py)
+_MAIN_LAUNCHES = []
+
+
+def _run_main_chunk(blends, key, opts, device):
+    """``init_all_sources_main`` of the blends of one chunk: ``blends`` is a list of
+    ``(observation, centers, detect)``; returns the list of their source lists."""
+    idtype, mdtype, C = key
+    ch = _Chunk((idtype, idtype, mdtype, C), device)
+    with ch.torch.cuda.device(ch.dev):
+        state = _main_launches(ch, blends, opts)
+    return _main_assemble(blends, state)
+
+
+def _main_launches(ch, blends, opts):
+    """Everything of a chunk that touches the device: packs and uploads the inputs, runs the
+    (at most) eight launches -- main_coadd, snr, taps twice, main_sweep, then after the host
+    has decided class and box of every source crop, main_split and fit -- and returns what the
+    assembly needs, all of it in host memory."""
+    from types import SimpleNamespace
+
+    C, idtype, mdtype = ch.C, ch.idtype, ch.mdtype
+    keep = []  # descriptor tables on the device, until the chunk is done
+    del _MAIN_LAUNCHES[:]
+
+    def call(step, dtype, table, *args):
+        if len(table):
+            _MAIN_LAUNCHES.append(step)
+        keep.append(ch.call(step, dtype, table, *args))
+
+    nb = len(blends)
+    shapes = [b[0].images.shape[1:] for b in blends]
+    n_pix = np.array([h * w for h, w in shapes], np.int64)
+    image_off, n_image = _offsets(C * n_pix)
+    detect_off, n_detect = _offsets(n_pix)
+    d_images = ch.cat([b[0].images for b in blends], idtype)
+    d_variance = ch.cat([b[0].variance for b in blends], idtype)
+    # ---- the detection images: the passed ones, the coadds of the others
+    host_detect = np.zeros(n_detect, idtype)
+    missing = [b for b in range(nb) if blends[b][2] is None]
+    for b in range(nb):
+        if blends[b][2] is not None:
+            host_detect[detect_off[b]:detect_off[b] + n_pix[b]] = blends[b][2].reshape(-1)
+    d_detect = ch.up(host_detect) if len(missing) < nb else ch.empty(n_detect, idtype)
+    coadds = np.zeros(len(missing), _MAIN_COADD_DESC)
+    for k, b in enumerate(missing):
+        coadds[k] = (C, 0, n_pix[b], image_off[b], k * C, detect_off[b])
+    d_nr2 = ch.cat([np.asarray(blends[b][0].noise_rms) ** 2 for b in missing], idtype)
+    call("main_coadd", idtype, coadds, d_images, n_image, d_nr2, len(missing) * C, d_detect,
+         n_detect)
+    # ---- per source: SNR sums, centre taps of the convolved detection image; per blend: the
+    # spectrum of the model PSF
+    psf_off, n_psf = _offsets([b[0].psfs.size for b in blends])
+    d_psfs = ch.cat([b[0].psfs for b in blends], idtype)
+    stamps = [np.broadcast_to(np.asarray(b[0].diff_kernel.image),
+                              (C,) + np.shape(b[0].diff_kernel.image)[1:]) for b in blends]
+    stamp_off, n_stamp = _offsets([s.size for s in stamps])
+    d_stamps_i = ch.cat(stamps, idtype)
+    d_stamps_m = d_stamps_i if mdtype == idtype else ch.cat(stamps, mdtype)
+    model_psfs = [np.asarray(b[0].model_psf)[0] for b in blends]
+    mpsf_off, n_mpsf = _offsets([m.size for m in model_psfs])
+    d_model_psfs = ch.cat(model_psfs, mdtype)
+
+    src_blend = np.array([b for b in range(nb) for _ in blends[b][1]], np.int64)
+    src_center = [c for b in blends for c in b[1]]
+    ns = len(src_center)
+    swept_off, n_swept = _offsets(n_pix[src_blend])
+    thresh = [float(np.mean(b[0].noise_rms) * opts["thresh"]) for b in blends]
+    snr_t, taps_t = np.zeros(ns, _SNR_DESC), np.zeros(ns, _TAPS_DESC)
+    sweep_t = np.zeros(ns, _MAIN_SWEEP_DESC)
+    ptaps_t = np.zeros(nb, _TAPS_DESC)
+    for s in range(ns):
+        b = src_blend[s]
+        h, w = shapes[b]
+        cy, cx = int(src_center[s][0]), int(src_center[s][1])
+        _, ph, pw = blends[b][0].psfs.shape
+        _, kh, kw = stamps[b].shape
+        snr_t[s] = (h, w, cy, cx, ph, pw, image_off[b], psf_off[b])
+        taps_t[s] = (h, w, cy, cx, kh, kw, detect_off[b], stamp_off[b], s * (C + 1))
+        sweep_t[s] = (h, w, cy, cx, detect_off[b], swept_off[s], thresh[b])
+    for b in range(nb):
+        mh, mw = model_psfs[b].shape
+        _, kh, kw = stamps[b].shape
+        ptaps_t[b] = (mh, mw, mh // 2, mw // 2, kh, kw, mpsf_off[b], stamp_off[b], b * (C + 1))
+    d_snr = ch.empty(2 * ns, np.float64)
+    d_taps = ch.empty(ns * (C + 1), idtype)
+    d_ptaps = ch.empty(nb * (C + 1), mdtype)
+    call("snr", idtype, snr_t, d_images, d_variance, n_image, d_psfs, n_psf, d_snr, 2 * ns)
+    call("taps", idtype, taps_t, d_detect, n_detect, d_stamps_i, n_stamp, d_taps, ns * (C + 1))
+    call("taps", mdtype, ptaps_t, d_model_psfs, n_mpsf, d_stamps_m, n_stamp, d_ptaps,
+         nb * (C + 1))
+    # ---- symmetry, sweep and trim of every source
+    ry, rx = max(h for h, _ in shapes) - 1, max(w for _, w in shapes) - 1
+    cosines = _relative_cosines(ry, rx)
+    d_cos = ch.up(cosines.reshape(-1))
+    d_swept = ch.empty(n_swept, idtype)
+    d_bounds, d_peaks = ch.empty(4 * ns, np.int32), ch.empty(ns, idtype)
+    call("main_sweep", idtype, sweep_t, d_detect, n_detect, d_cos, cosines.size, ry, rx, d_swept,
+         n_swept, d_bounds, d_peaks, ns)
+    snr = d_snr.cpu().numpy()[:2 * ns].reshape(ns, 2)
+    taps = d_taps.cpu().numpy()[:ns * (C + 1)].reshape(ns, C + 1)
+    ptaps = d_ptaps.cpu().numpy()[:nb * (C + 1)].reshape(nb, C + 1)
+    bounds = d_bounds.cpu().numpy()[:4 * ns].reshape(ns, 4)
+    peaks = d_peaks.cpu().numpy()[:ns]
+    # ---- the class and the box of every source, as init_all_sources_main decides them.  (A
+    # swept plane is nowhere above its centre pixel, so what is left of it after the trim holds
+    # the centre, the box holds all of it, and the maximum of the box is that of the plane.)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        n_comp = np.floor(snr[:, 0] / np.sqrt(snr[:, 1])) / opts["min_snr"]
+    kind = np.where(n_comp >= 2, _TWO, _ONE)
+    kind[peaks == 0] = _PSF
+    boxes = {s: _trim_box(bounds[s], src_center[s]) for s in range(ns) if kind[s] != _PSF}
+    # ---- cut-outs divided by their maximum; bulge and disk of the two-component sources
+    sizes = [boxes[s].shape[0] * boxes[s].shape[1] * (3 if kind[s] == _TWO else 1)
+             for s in boxes]
+    out_off, n_out = _offsets(sizes)
+    offs = dict(zip(boxes, (int(o) for o in out_off)))
+    crop_t = np.zeros(len(boxes), _CROP_DESC)
+    for k, (s, box) in enumerate(boxes.items()):
+        h, w = shapes[src_blend[s]]
+        crop_t[k] = (h, w, box.origin[0], box.origin[1], box.shape[0], box.shape[1],
+                     swept_off[s], 0, offs[s])
+    d_out = ch.empty(n_out, idtype)
+    d_all = ch.torch.ones(int(n_pix.max()), dtype=ch.torch.uint8, device=ch.dev)
+    call("crop", idtype, crop_t, d_swept, n_swept, d_all, int(n_pix.max()), d_out, n_out)
+    pairs = [s for s in boxes if kind[s] == _TWO]
+    split_t, fit_t = np.zeros(len(pairs), _MAIN_SPLIT_DESC), np.zeros(len(pairs), _FIT_DESC)
+    for k, s in enumerate(pairs):
+        b = src_blend[s]
+        h, w = shapes[b]
+        _, kh, kw = stamps[b].shape
+        box = boxes[s]
+        (y0, x0), (bh, bw) = box.origin, box.shape
+        split_t[k] = (bh, bw, offs[s], offs[s] + bh * bw, offs[s] + 2 * bh * bw)
+        fit_t[k] = (h, w, y0, x0, bh, bw, y0, x0, bh, bw, y0, x0, bh, bw, kh, kw,
+                    image_off[b], stamp_off[b], offs[s] + bh * bw, offs[s] + 2 * bh * bw)
+    call("main_split", idtype, split_t, d_out, n_out, float(opts["percentile"] / 100))
+    d_sums = ch.empty(len(pairs) * C * 5, np.float64)
+    if len(pairs):
+        d_stamps_fit = ch.cat(stamps, np.float64)
+        call("fit", idtype, fit_t, d_out, n_out, d_images, int(idtype == np.float64), n_image,
+             d_stamps_fit, n_stamp, d_sums, len(pairs) * C * 5)
+    morphs = d_out.cpu().numpy()
+    sums = d_sums.cpu().numpy()[:len(pairs) * C * 5].reshape(len(pairs), C, 5)
+    return SimpleNamespace(C=C, idtype=idtype, src_blend=src_blend, src_center=src_center,
+                           kind=kind, taps=taps, ptaps=ptaps, peaks=peaks, boxes=boxes, offs=offs,
+                           morphs=morphs, pairs=pairs, sums=sums)
+
+
+def _main_assemble(blends, st):
+    """The sources of a chunk from what ``_main_launches`` brought back, source by source as
+    ``init_all_sources_main`` builds them."""
+    C = st.C
+    pair_seds = dict(zip(st.pairs, _solve_pairs(st.sums, st.idtype)))
+    results = [[] for _ in blends]
+    for s, center in enumerate(st.src_center):
+        b = st.src_blend[s]
+        obs = blends[b][0]
+        spec_box = obs.bbox[0]
+        at_center = (slice(None), center[0], center[1])
+        kind = st.kind[s]
+        if kind == _PSF:
+            model_psf = obs.model_psf[0]
+            py, px = model_psf.shape[0] // 2, model_psf.shape[1] // 2
+            sed = obs.images[at_center] / st.ptaps[b, :C]
+            sed[sed < 0] = 0
+            bbox = Box(model_psf.shape, origin=(center[0] - py, center[1] - px))
+            comps = [LiteComponent(center, spec_box @ bbox, sed, model_psf / np.max(model_psf))]
+        else:
+            bbox, at = st.boxes[s], st.offs[s]
+            n = bbox.shape[0] * bbox.shape[1]
+            cut = [st.morphs[at + k * n:at + (k + 1) * n].reshape(bbox.shape).copy()
+                   for k in range(3 if kind == _TWO else 1)]
+            if kind == _TWO:
+                bulge_sed, disk_sed = pair_seds[s]
+                comps = [LiteComponent(center, spec_box @ bbox, bulge_sed, cut[1]),
+                         LiteComponent(center, spec_box @ bbox, disk_sed, cut[2])]
+            else:
+                sed = obs.images[at_center] / st.taps[s, :C]
+                sed[sed < 0] = 0
+                comps = [LiteComponent(center, spec_box @ bbox, sed * st.peaks[s], cut[0])]
+        results[b].append(LiteSource(comps, obs.dtype))
+    return results
+
+
+def init_blends_main(observations, centers, detect=None, min_snr=50, use_mask=False,
+                     percentile=25, thresh=0.5, device=None, _working_set_bytes=None):
+    """``init_all_sources_main`` for many blends: ``sources[i]`` is what
+    ``init_all_sources_main(observations[i], centers[i], detect=detect[i], min_snr=min_snr,
+    percentile=percentile, thresh=thresh)`` returns -- number and class of the sources, centres,
+    boxes, morphologies, dtypes and the spectra of PSF and single-component sources bit for bit;
+    the spectra of bulge + disk sources from float64 normal equations instead of a float32 FFT
+    convolution and ``lstsq`` -- with at most eight launches of csrc/lite_init_main.hip and
+    csrc/lite_init.hip per chunk of blends that share dtypes and bands; frames, stamps and
+    source counts may differ.  The contract is for finite data (images, variance, PSFs and
+    detection images without NaN or infinity).
+
+    ``centers``: one list of integer ``(y, x)`` per observation; a centre outside its frame
+    raises ``ValueError``.  ``detect``: None, or per blend None (the coadd
+    ``sum(images / noise_rms**2)``) or a 2-D array of the frame's shape, which is only read.
+    Blends the device path does not take -- ``use_mask=True``, a ``percentile`` outside
+    (0, 100), a ``detect`` or ``noise_rms`` of another dtype than the images, everything
+    ``init_blends`` refuses, a frame beyond the sweep kernel's LDS image (40704 float32 or
+    20352 float64 pixels) -- go through ``init_all_sources_main``; ``plan_init_blends_main``
+    names them.  ``device``: GPU index of the batches (default 0).  Wrap every list of the
+    result with ``parameterize_sources`` before fitting."""
+    observations, centers = list(observations), [list(c) for c in centers]
+    detect = [None] * len(observations) if detect is None else list(detect)
+    budget = WORKING_SET_BYTES if _working_set_bytes is None else _working_set_bytes
+    device = 0 if device is None else int(device)
+    groups, fallback = plan_init_blends_main(observations, centers, detect, use_mask, percentile)
+    opts = dict(min_snr=min_snr, percentile=percentile, thresh=thresh)
+    sources = [None] * len(observations)
+    for key, idx in groups.items():
+        items = []
+        for i in idx:
+            if not centers[i]:
+                sources[i] = []
+                continue
+            items.append((i, _main_bytes(observations[i], len(centers[i]), key)))
+        for chunk in _init_chunks(items, key, budget):
+            blends = [(observations[i], centers[i], detect[i]) for i in chunk]
+            for i, result in zip(chunk, _run_main_chunk(blends, key, opts, device)):
+                sources[i] = result
+    for i, _ in fallback:
+        sources[i] = init_all_sources_main(observations[i], centers[i], detect[i], min_snr,
+                                           use_mask, percentile, thresh)
     return sources
