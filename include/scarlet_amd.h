@@ -899,6 +899,12 @@ int smi_gemm_test(const float *A, int64_t strideA, const float *B, int64_t strid
                   int64_t scratch_elems, int32_t plan[5], int32_t *guard_ok);
 int smi_resampler_adjoint(smi_resampler *r, const float *resid, float *gpad);
 
+/* Test entry point (tests/test_gpu_update_step.py): y[i] = the square root the AMSGrad pass of
+ * the update kernels takes when the batch's eps is at least 2^-96 -- the hardware root plus
+ * the one-ulp correction, correctly rounded for operands from 2^-96 up, +inf -> +inf.  Host
+ * pointers, n < 2^30. */
+int smi_sqrt_rn_normal_test(const float *x, float *y, int64_t n);
+
 /* The low-resolution observation as a further term of a fit (Blend._loss_func sums the
  * log-likelihoods of all observations, blend.py:265-271; Observation.get_log_likelihood,
  * observation.py:147-170).  `channels[C]` gives the model channel of every band of the

@@ -723,6 +723,12 @@ int smi_gemm_test(const float *A, int64_t strideA, const float *B, int64_t strid
     return rc;
 }
 
+int smi_sqrt_rn_normal_test(const float *x, float *y, int64_t n) {
+    SMI_REQUIRE(x && y, "null argument");
+    if (int rc = have_device()) return rc;
+    return sqrt_rn_normal_test(x, y, n);
+}
+
 static constexpr int kMaxLowRes = 8;
 
 int smi_batch_attach_lowres(smi_batch *b, smi_resampler *r, const int32_t *channels,

@@ -500,6 +500,8 @@ int lowres_get_rendered(LowRes *l, float *out, hipStream_t s);
 int launch_sweep_timing(const SweepPlanDev *d_plans, const SweepPlanDev &host_plan, int plan_id,
                         int mode, int n_rep, float one_minus_g, int waves, int groups,
                         long long *cycles, float *images, hipStream_t s);
+// rounded_math.h's sqrt_rn_normal on host arrays (kernels.hip; test entry)
+int sqrt_rn_normal_test(const float *x, float *y, int64_t n);
 // box resizing (kernels.hip: resize_test_kernel and the state records)
 void launch_resize_test(const BatchView &v, int32_t *margin, double *pull, hipStream_t s);
 void launch_gather_states(const BatchView &v, const int32_t *sel, const int64_t *off, int32_t n_sel,

@@ -1587,6 +1587,7 @@ struct UpdState {
     const SweepPlanDev *ring;  // the plan when it has a ring schedule
     const SweepPlanDev *staged;  // the plan whose ring stream the workgroup holds in LDS ...
     const char *plan_lds;        // ... there (nullptr: none)
+    const uint32_t *gtab;        // the workgroup's gather offsets of that plan's box (nullptr: none)
     float one_minus_g, lthresh, cfloor, pfloor;
     const float *bg_level;
     float *us, *sed_new;
@@ -1598,6 +1599,19 @@ struct UpdState {
 // four slots; the 31^2 teams gain nothing.  The others run the code they always ran.
 constexpr bool update_lean(int npl, int mode, int team) {
     return mode != 2 && !(team == 256 && npl == 16);
+}
+// The instances whose AMSGrad pass keeps the first iteration's tenth and the general square
+// root behind scalar branches (upd_step), by the same rule: the one-wavefront classes.  The
+// teams would need 2 - 5 more registers (27 pixels per lane: 32 B more scratch), lite's 21^2
+// class one more.  FISTA has no AMSGrad pass.
+constexpr bool update_step_lean(int npl, int mode, int team) {
+    return mode != 2 && team == 64 && !(npl == 7 && mode == 1);
+}
+// The instances whose workgroups may keep a table of gather offsets beside the staged plan
+// (update_kernel_reg; the launch decides whether the LDS has room for it), by the same rule.
+// The largest class never has the room: seven images and 49 KB of plan fill the LDS.
+constexpr bool update_gather_table(int npl, int mode, int team) {
+    return team == 64 && npl < 59;
 }
 // byte offset of slot j of a lane
 template <int T, bool LEAN>
@@ -1611,8 +1625,9 @@ struct UpdFull {
 };
 
 // gradient gather, spectrum update, AMSGrad (or FISTA) step of the image, set-up of the
-// proximal sub-iterations.  EXT: the batch has frame extents (smi_batch_set_frame_extents)
-template <int NPL, int MODE, int T, bool EXT>
+// proximal sub-iterations.  EXT: the batch has frame extents (smi_batch_set_frame_extents);
+// MIXED: called by update_kernel_mixed, which keeps the code it had
+template <int NPL, int MODE, int T, bool EXT, bool MIXED>
 __device__ __forceinline__ void upd_step(const BatchView &v, const float *G, int it, float e2,
                                          int prox_max_iter, UpdState<NPL, update_xp(T)> &S) {
     constexpr bool LITE = MODE != 0;
@@ -1620,6 +1635,8 @@ __device__ __forceinline__ void upd_step(const BatchView &v, const float *G, int
     constexpr bool XP = update_xp(T);
     constexpr int kFull = UpdFull<NPL>::value;
     constexpr bool LEAN = update_lean(NPL, MODE, T);
+    constexpr bool STEP_LEAN = !MIXED && update_step_lean(NPL, MODE, T);
+    constexpr bool GTAB = !MIXED && update_gather_table(NPL, MODE, T);
     const CompCtx &c = S.c;
     it = v.local_it(c.b, it);
     const int lane = c.lane, k = S.k, N = c.N;
@@ -1657,26 +1674,45 @@ __device__ __forceinline__ void upd_step(const BatchView &v, const float *G, int
         // byte offset of each of the lane's pixels inside a band plane of G (or out of
         // range), parked in the LDS image, which is not needed before the prox loop
         uint32_t *goff = reinterpret_cast<uint32_t *>(us);
-        const float inv_w = 1.0f / (float)c.w;
         const int Hb = EXT ? v.frame_h(c.b) : v.H, Wb = EXT ? v.frame_w(c.b) : v.W;  // its frame
+        // ... or, for a box of the staged plan's shape that lies inside the frame, read from the
+        // workgroup's table of offsets relative to the box's first pixel (update_kernel_reg),
+        // which goes into the descriptor's base: no arithmetic per pixel.  Wave-uniform.
+        const uint32_t *offs = goff;
+        int64_t first_px = 0;
+        bool table = false;
+        if constexpr (GTAB) {
+            table = S.gtab && c.h == S.staged->h && c.w == S.staged->w && c.oy >= 0 && c.ox >= 0 &&
+                    c.oy + c.h <= Hb && c.ox + c.w <= Wb;
+            table = __builtin_amdgcn_readfirstlane((int)table) != 0;
+        }
+        if (table) {
+            offs = S.gtab;
+            first_px = (int64_t)c.oy * v.Fx + c.ox;
 #pragma unroll
-        for (int j = 0; j < NPL; ++j) {
-            const int i = lane + T * j;
-            // exact for i < 2^20: the float quotient is off by < 1e-6 relative
-            const int y = (int)(((float)i + 0.5f) * inv_w);
-            const int x = i - y * c.w;
-            const int fy = y + c.oy, fx = x + c.ox;
-            const bool ok = (j < kFull || i < N) && (unsigned)fy < (unsigned)Hb &&
-                            (unsigned)fx < (unsigned)Wb;
-            goff[i] = ok ? (uint32_t)(fy * v.Fx + fx) * 4u : kOutOfRange;
-            xs[j] = 0.f;
+            for (int j = 0; j < NPL; ++j) xs[j] = 0.f;
+        } else {
+            const float inv_w = 1.0f / (float)c.w;
+#pragma unroll
+            for (int j = 0; j < NPL; ++j) {
+                const int i = lane + T * j;
+                // exact for i < 2^20: the float quotient is off by < 1e-6 relative
+                const int y = (int)(((float)i + 0.5f) * inv_w);
+                const int x = i - y * c.w;
+                const int fy = y + c.oy, fx = x + c.ox;
+                const bool ok = (j < kFull || i < N) && (unsigned)fy < (unsigned)Hb &&
+                                (unsigned)fx < (unsigned)Wb;
+                goff[i] = ok ? (uint32_t)(fy * v.Fx + fx) * 4u : kOutOfRange;
+                xs[j] = 0.f;
+            }
         }
         const int64_t plane = (int64_t)v.Fy * v.Fx;
         for (int cb = 0; cb < c.C; ++cb) {
-            const rsrc_t r_g = make_rsrc(G + ((int64_t)c.b * c.C + cb) * plane, (uint32_t)plane * 4u);
+            const rsrc_t r_g = make_rsrc(G + ((int64_t)c.b * c.C + cb) * plane + first_px,
+                                         (uint32_t)(plane - first_px) * 4u);
             float g[NPL];
 #pragma unroll
-            for (int j = 0; j < NPL; ++j) g[j] = buf_load(r_g, goff[lane + T * j]);
+            for (int j = 0; j < NPL; ++j) g[j] = buf_load(r_g, offs[lane + T * j]);
             const float s = c.sed[cb];
             float acc = 0.f;
 #pragma unroll
@@ -1746,6 +1782,10 @@ __device__ __forceinline__ void upd_step(const BatchView &v, const float *G, int
         const rsrc_t r_vh = make_rsrc(v.vh_morph + c.moff, nbytes);
         constexpr int CH = NPL <= 6 ? NPL : 6;
         const float b1 = v.b1, b2 = v.b2, eps = v.eps;
+        // (both the same for every lane of the component's wavefront or team, and said so)
+        const bool first = __builtin_amdgcn_readfirstlane((int)(it == 0)) != 0;
+        const bool normal_sqrt =
+            __builtin_amdgcn_readfirstlane((int)(eps >= kSqrtNormalMin)) != 0;
         float cm[CH], cv[CH], cvh[CH];
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
@@ -1767,33 +1807,104 @@ __device__ __forceinline__ void upd_step(const BatchView &v, const float *G, int
                     nvh[u] = buf_load(r_vh, off);
                 }
             }
+            if constexpr (STEP_LEAN) {
+                // the same arithmetic group by group, with the two rare pieces behind scalar
+                // branches: the general sqrtf (an eps below kSqrtNormalMin) and the tenth of a
+                // blend's first iteration.  xs[j] carries alpha * m, then the step
+                // (three pixels between two branches: groups of two or six want more registers
+                // than the parent's code, gfx950 ISA table)
+                constexpr int SUB = 3;
+                static_assert(CH % SUB == 0, "whole sub-groups");
 #pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                const int j = j0 + u;
-                if (j < NPL) {
-                    const uint32_t off = slot_offset<T, LEAN>(lane, lane4, j);
-                    const float g = xs[j];
-                    const float m = (1.f - b1) * g + b1 * cm[u];
-                    const float vv = (1.f - b2) * g * g + b2 * cv[u];
-                    const float vh = it == 0 ? vv : fmaxf(cvh[u], vv);
-                    buf_store(r_m, off, m);
-                    buf_store(r_v, off, vv);
-                    buf_store(r_vh, off, vh);
-                    const float psi = sqrtf(fmaxf(vh, eps));
-                    float upd = alpha * m / psi;
-                    if (it == 0) upd /= 10.f;
-                    xs[j] = zs[j] - upd;
-                    zs[j] = xs[j];
-                    // slots beyond the box: x = z = 0 (loads returned 0), psi must not count
-                    const bool in_box = j < kFull || lane + T * j < N;
-                    if constexpr (XP) {
-                        const float rj = in_box ? psi : 0.f;
-                        buf_store(r_x, off, xs[j]);
-                        buf_store(r_p, off, rj);
-                        pmax = fmaxf(pmax, rj);
+                for (int u0 = 0; u0 < CH; u0 += SUB) {
+                    float w[SUB];
+#pragma unroll
+                    for (int q = 0; q < SUB; ++q) {
+                        const int u = u0 + q, j = j0 + u;
+                        if (j < NPL) {
+                            const uint32_t off = slot_offset<T, LEAN>(lane, lane4, j);
+                            const float g = xs[j];
+                            const float m = (1.f - b1) * g + b1 * cm[u];
+                            const float vv = (1.f - b2) * g * g + b2 * cv[u];
+                            const float vh = first ? vv : fmaxf(cvh[u], vv);
+                            buf_store(r_m, off, m);
+                            buf_store(r_v, off, vv);
+                            buf_store(r_vh, off, vh);
+                            w[q] = fmaxf(vh, eps);
+                            xs[j] = alpha * m;
+                        }
+                    }
+                    if (normal_sqrt) {
+#pragma unroll
+                        for (int q = 0; q < SUB; ++q)
+                            if (j0 + u0 + q < NPL) w[q] = sqrt_rn_normal(w[q]);
                     } else {
-                        rs[j] = in_box ? psi : 0.f;
-                        pmax = fmaxf(pmax, rs[j]);
+#pragma unroll
+                        for (int q = 0; q < SUB; ++q)
+                            if (j0 + u0 + q < NPL) {
+                                w[q] = sqrtf(w[q]);
+                                asm volatile("" : "+v"(w[q]));  // (a branch, not both and a select)
+                            }
+                    }
+#pragma unroll
+                    for (int q = 0; q < SUB; ++q)
+                        if (j0 + u0 + q < NPL) xs[j0 + u0 + q] = xs[j0 + u0 + q] / w[q];
+                    if (first) {  // lite/parameters.py:288-291
+#pragma unroll
+                        for (int q = 0; q < SUB; ++q)
+                            if (j0 + u0 + q < NPL) {
+                                xs[j0 + u0 + q] = xs[j0 + u0 + q] / 10.f;
+                                asm volatile("" : "+v"(xs[j0 + u0 + q]));  // (not speculated either)
+                            }
+                    }
+#pragma unroll
+                    for (int q = 0; q < SUB; ++q) {
+                        const int j = j0 + u0 + q;
+                        if (j < NPL) {
+                            xs[j] = zs[j] - xs[j];
+                            zs[j] = xs[j];
+                            const bool in_box = j < kFull || lane + T * j < N;
+                            const float rj = in_box ? w[q] : 0.f;
+                            if constexpr (XP) {
+                                const uint32_t off = slot_offset<T, LEAN>(lane, lane4, j);
+                                buf_store(r_x, off, xs[j]);
+                                buf_store(r_p, off, rj);
+                            } else {
+                                rs[j] = rj;
+                            }
+                            pmax = fmaxf(pmax, rj);
+                        }
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < CH; ++u) {
+                    const int j = j0 + u;
+                    if (j < NPL) {
+                        const uint32_t off = slot_offset<T, LEAN>(lane, lane4, j);
+                        const float g = xs[j];
+                        const float m = (1.f - b1) * g + b1 * cm[u];
+                        const float vv = (1.f - b2) * g * g + b2 * cv[u];
+                        const float vh = it == 0 ? vv : fmaxf(cvh[u], vv);
+                        buf_store(r_m, off, m);
+                        buf_store(r_v, off, vv);
+                        buf_store(r_vh, off, vh);
+                        const float psi = sqrtf(fmaxf(vh, eps));
+                        float upd = alpha * m / psi;
+                        if (it == 0) upd /= 10.f;
+                        xs[j] = zs[j] - upd;
+                        zs[j] = xs[j];
+                        // slots beyond the box: x = z = 0 (loads returned 0), psi must not count
+                        const bool in_box = j < kFull || lane + T * j < N;
+                        if constexpr (XP) {
+                            const float rj = in_box ? psi : 0.f;
+                            buf_store(r_x, off, xs[j]);
+                            buf_store(r_p, off, rj);
+                            pmax = fmaxf(pmax, rj);
+                        } else {
+                            rs[j] = in_box ? psi : 0.f;
+                            pmax = fmaxf(pmax, rs[j]);
+                        }
                     }
                 }
             }
@@ -2057,12 +2168,14 @@ __device__ __forceinline__ void update_component(const BatchView &v, const float
                                                  float e_rel, int prox_max_iter, int k,
                                                  float *us, float *sed_new,
                                                  const SweepPlanDev *staged = nullptr,
-                                                 const char *plan_lds = nullptr, int tid = -1) {
+                                                 const char *plan_lds = nullptr, int tid = -1,
+                                                 const uint32_t *gtab = nullptr) {
     constexpr bool fista = MODE == 2;
     UpdState<NPL, update_xp(T)> S;
     S.k = k;
     S.staged = staged;
     S.plan_lds = plan_lds;
+    S.gtab = gtab;
     if (tid < 0) tid = (int)threadIdx.x;
     S.c = comp_ctx(v, k, T == 64 ? (tid & 63) : tid);
     if (v.state[S.c.b] >= 2) return;
@@ -2070,7 +2183,7 @@ __device__ __forceinline__ void update_component(const BatchView &v, const float
     S.sed_new = sed_new;
     const float e2 = e_rel * e_rel;
     if (fista) prox_max_iter = 1;  // FistaParameter applies the prox once
-    upd_step<NPL, MODE, T, EXT>(v, G, it, e2, prox_max_iter, S);
+    upd_step<NPL, MODE, T, EXT, kGlobalRing>(v, G, it, e2, prox_max_iter, S);
     team_fence<T>();  // the offsets parked in `us` have been consumed
     for (int tau = 0; tau < prox_max_iter; ++tau) {
         upd_prox_begin<NPL, MODE, T>(v, S);
@@ -2133,7 +2246,7 @@ constexpr int update_pack_max(int npl, int team) {
 template <int NPL, int MODE, int T, bool EXT>
 __global__ __launch_bounds__(T * update_pack_max(NPL, T)) SMI_WAVES void update_kernel_reg(
     BatchView v, const float *G, int it, float e_rel, int prox_max_iter, int n_items,
-    int n_finalize, int min_iter, int check, int stage_plan, int persistent) {
+    int n_finalize, int min_iter, int check, int stage_plan, int persistent, int gather_off) {
     constexpr int kPack = update_pack_max(NPL, T);
     __shared__ float sed_new[kPack][64];
     __shared__ int next_item;
@@ -2152,6 +2265,7 @@ __global__ __launch_bounds__(T * update_pack_max(NPL, T)) SMI_WAVES void update_
     float *us = lds_dyn + wave * (T * NPL + 4) + 4;
     const SweepPlanDev *staged = nullptr;
     const char *plan_lds = nullptr;
+    const uint32_t *gtab = nullptr;
     if (T == 64 && (stage_plan >= 0 || persistent)) {
         if (threadIdx.x == 0) next_item = 0;
         if (stage_plan >= 0) {
@@ -2161,6 +2275,22 @@ __global__ __launch_bounds__(T * update_pack_max(NPL, T)) SMI_WAVES void update_
             const uint32_t n16 = staged->ring_bytes >> 4;
             for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
             plan_lds = reinterpret_cast<const char *>(dst);
+            if constexpr (update_gather_table(NPL, MODE, T)) {
+                // gather offsets of the plan's box, relative to its first pixel, at byte
+                // `gather_off` of the dynamic LDS (< 0: the launch found no room): T * NPL
+                // entries, those beyond the box out of range (upd_step)
+                if (gather_off >= 0) {
+                    uint32_t *tab = reinterpret_cast<uint32_t *>(lds_dyn) + (gather_off >> 2);
+                    const int w = staged->w, n = staged->h * w;
+                    const float inv_w = 1.0f / (float)w;
+                    for (int i = threadIdx.x; i < T * NPL; i += blockDim.x) {
+                        // exact for i < 2^20: the float quotient is off by < 1e-6 relative
+                        const int y = (int)(((float)i + 0.5f) * inv_w);
+                        tab[i] = i < n ? (uint32_t)(y * v.Fx + (i - y * w)) * 4u : kOutOfRange;
+                    }
+                    gtab = tab;
+                }
+            }
         }
         __syncthreads();
     }
@@ -2186,7 +2316,7 @@ __global__ __launch_bounds__(T * update_pack_max(NPL, T)) SMI_WAVES void update_
         int tid = (int)threadIdx.x;
         asm volatile("" : "+v"(tid));
         update_component<NPL, MODE, T, false, EXT>(v, G, it, e_rel, prox_max_iter, v.work[lo + k + v.work0],
-                                       us, sed_new[wave], staged, plan_lds, tid);
+                                       us, sed_new[wave], staged, plan_lds, tid, gtab);
         if (!loop) break;
     }
 }
@@ -2230,6 +2360,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) voi
         update_component<kUpdateNpl[3], MODE, 64, true, EXT>(v, G, it, e_rel, prox_max_iter, k, us, sed_new);
     else
         update_component<kUpdateNpl[4], MODE, 64, true, EXT>(v, G, it, e_rel, prox_max_iter, k, us, sed_new);
+}
+
+// test entry (smi_sqrt_rn_normal_test): the AMSGrad pass's square root, element by element in place
+__global__ __launch_bounds__(256) void sqrt_rn_normal_test_kernel(float *x, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) x[i] = sqrt_rn_normal(x[i]);
 }
 
 // development aid: shader clocks of `n_rep` sweeps of one plan per wavefront, every wavefront
@@ -2781,16 +2917,34 @@ static int launch_update_reg(const BatchView &v, const float *G, int32_t it, flo
             }
         }
     }
+    // the table of gather offsets behind the staged stream (update_kernel_reg), where it
+    // costs neither a wavefront of the workgroup nor a workgroup of the CU
+    int gather_off = -1;
+    size_t lds_table = lds;
+    if (stage >= 0) {
+        const size_t fixed = (size_t)kPack * 256 + 64;  // (static LDS of the kernel)
+        const size_t off = (size_t)pack * (T * NPL + 4) * sizeof(float) +
+                           (((size_t)v.stage_bytes[cls] + 15) & ~(size_t)15);
+        const size_t with = off + (size_t)T * NPL * sizeof(uint32_t);
+        if (with + fixed <= 160 * 1024 &&
+            (160 * 1024) / (with + fixed) == (160 * 1024) / (lds + fixed)) {
+            gather_off = (int)off;
+            lds_table = with;
+        }
+    }
     const dim3 grid(n_blocks + n_fin), block(T * pack);
 #define SMI_LAUNCH_EXT(MODE, EXT)                                                               \
     {                                                                                           \
         static size_t configured[kMaxDevices] = {};                                             \
         auto kern = update_kernel_reg<NPL, MODE, T, EXT>;                                       \
-        if (lds > 48 * 1024)                                                                    \
-            if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds, configured)) \
+        const bool tab = update_gather_table(NPL, MODE, T) && gather_off >= 0;                  \
+        const size_t lds_k = tab ? lds_table : lds;                                             \
+        if (lds_k > 48 * 1024)                                                                  \
+            if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds_k, configured)) \
                 return rc;                                                                      \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, vi, G, it, e_rel, prox_max_iter, n_items, \
-                           n_fin, fin.min_iter, fin.check, stage, persistent);                         \
+        hipLaunchKernelGGL(kern, grid, block, lds_k, s, vi, G, it, e_rel, prox_max_iter, n_items, \
+                           n_fin, fin.min_iter, fin.check, stage, persistent,                   \
+                           tab ? gather_off : -1);                                              \
     }
     // (the kernels without frame extents are those of a batch that never had them)
 #define SMI_LAUNCH(MODE)                                                                        \
@@ -3002,6 +3156,27 @@ int launch_sweep_timing(const SweepPlanDev *d_plans, const SweepPlanDev &host_pl
         return rc;
     hipLaunchKernelGGL(sweep_timing_kernel, dim3(groups), dim3(64 * waves), lds, s, d_plans, plan_id,
                        mode, n_rep, one_minus_g, cycles, images);
+    return SMI_OK;
+}
+
+int sqrt_rn_normal_test(const float *x, float *y, int64_t n) {
+    SMI_REQUIRE(n >= 0 && n < (int64_t)1 << 30, "sqrt_rn_normal_test: bad length");
+    if (n == 0) return SMI_OK;
+    float *d = nullptr;
+    SMI_HIP(hipMalloc((void **)&d, (size_t)n * sizeof(float)));
+    hipError_t e = hipMemcpy(d, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(sqrt_rn_normal_test_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256),
+                           0, nullptr, d, n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(y, d, (size_t)n * sizeof(float), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) {
+        set_error(std::string("sqrt_rn_normal_test: ") + hipGetErrorString(e));
+        return SMI_ERR_HIP;
+    }
     return SMI_OK;
 }
 
