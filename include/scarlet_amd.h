@@ -905,6 +905,29 @@ int smi_resampler_adjoint(smi_resampler *r, const float *resid, float *gpad);
  * pointers, n < 2^30. */
 int smi_sqrt_rn_normal_test(const float *x, float *y, int64_t n);
 
+/* Test entry point (tests/test_update_launch_plan_host.py; needs no device): the launch the
+ * per-class update kernel gets for `n_items` components of size class `size_class` (0 .. 8: one
+ * wavefront for boxes up to 21^2, 31^2, 41^2, 51^2, 61^2 pixels, then the four-wavefront teams)
+ * on a chip of `cu_count` compute units, with `stage_bytes` of ring plan to copy into LDS (< 0:
+ * the class has none), in a range of blends with `range_items` >= n_items components of all
+ * classes, as one of `n_ranges` ranges that are stepped side by side
+ * (smi_batch_set_sub_ranges) and, if `finalize_pending`, with the loss bookkeeping of the
+ * iteration waiting for a launch to travel with.
+ * plan = {wavefronts or teams per workgroup, updating workgroups, persistent (workgroup i loops
+ * over share i of the list: items [i q + min(i, r), ... + q + (i < r)) with q, r = n_items / and
+ * % workgroups), plan staged, dynamic LDS bytes without and with the table of gather offsets,
+ * byte offset of that table or -1, bookkeeping: 0 none pending, 1 one trailing workgroup per
+ * blend, 2 inside the persistent grid, 3 a kernel of its own in front}.  The kernel has 256 B
+ * of static LDS per packed wavefront plus 64 B besides. */
+int smi_update_launch_plan_test(int32_t n_items, int32_t size_class, int64_t stage_bytes,
+                                int32_t cu_count, int32_t range_items, int32_t finalize_pending,
+                                int32_t n_ranges, int64_t plan[8]);
+/* Test entry point (tests/test_gpu_update_fold.py): that plan as the calling thread's last
+ * update launch with a bookkeeping to place actually used it, development switches included
+ * (bookkeeping 0: there has been none; the one launch for all small classes of a
+ * range: 1 wavefront per workgroup, a workgroup per component, nothing staged). */
+int smi_update_last_fold_plan_test(int64_t plan[8]);
+
 /* The low-resolution observation as a further term of a fit (Blend._loss_func sums the
  * log-likelihoods of all observations, blend.py:265-271; Observation.get_log_likelihood,
  * observation.py:147-170).  `channels[C]` gives the model channel of every band of the

@@ -208,6 +208,12 @@ SYMBOLS = {
         + [ctypes.c_int32] * 4 + [ctypes.c_int64, c_i32p, c_i32p],
     ),
     "smi_sqrt_rn_normal_test": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64]),
+    "smi_update_launch_plan_test": (
+        ctypes.c_int,
+        [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64] + [ctypes.c_int32] * 4
+        + [ctypes.POINTER(ctypes.c_int64)],
+    ),
+    "smi_update_last_fold_plan_test": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64)]),
     "smi_batch_attach_lowres": (
         ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32p, c_f32p, c_f32p, ctypes.c_double]
     ),

@@ -729,6 +729,38 @@ int smi_sqrt_rn_normal_test(const float *x, float *y, int64_t n) {
     return sqrt_rn_normal_test(x, y, n);
 }
 
+static void put_update_plan(const UpdateLaunchPlan &p, int64_t plan[8]) {
+    plan[0] = p.pack;
+    plan[1] = p.n_blocks;
+    plan[2] = p.persistent;
+    plan[3] = p.stage;
+    plan[4] = (int64_t)p.lds;
+    plan[5] = (int64_t)p.lds_table;
+    plan[6] = p.gather_off;
+    plan[7] = p.fold;
+}
+
+int smi_update_launch_plan_test(int32_t n_items, int32_t size_class, int64_t stage_bytes,
+                                int32_t cu_count, int32_t range_items, int32_t finalize_pending,
+                                int32_t n_ranges, int64_t plan[8]) {
+    SMI_REQUIRE(plan, "null argument");
+    SMI_REQUIRE(n_ranges >= 1 && n_items > 0 && range_items >= n_items && size_class >= 0 &&
+                    size_class < kNumUpdateClasses && cu_count > 0 &&
+                    stage_bytes < ((int64_t)1 << 31),
+                "update_launch_plan_test: bad argument");
+    const UpdateLaunchPlan p = update_launch_plan(n_items, size_class, stage_bytes, cu_count,
+                                                  range_items, finalize_pending != 0, n_ranges > 1,
+                                                  UpdateLaunchSwitches());
+    put_update_plan(p, plan);
+    return SMI_OK;
+}
+
+int smi_update_last_fold_plan_test(int64_t plan[8]) {
+    SMI_REQUIRE(plan, "null argument");
+    put_update_plan(update_last_fold_plan(), plan);
+    return SMI_OK;
+}
+
 static constexpr int kMaxLowRes = 8;
 
 int smi_batch_attach_lowres(smi_batch *b, smi_resampler *r, const int32_t *channels,
@@ -2748,6 +2780,16 @@ static int sub_ranges(const smi_batch *b) {
     // throughput where a fourth hardware queue exists -- GPU_MAX_HW_QUEUES = 8 (k blend-it/s,
     // 3 / 4 / 5 ranges): 128 blends 537 / 615 / 391, 256: 746 / 776 / 603, 512: 809 / 814 /
     // 740, 1024: 919 / 857 / 826.
+    // Measured again with the persistent update, the inline rendering and the loss bookkeeping
+    // inside the update grid (four hardware queues, bench.py --blends N --sub-ranges n, 100
+    // steps, k blend-it/s, lowest - highest of three runs for n = 1 / 2 / 3 / 4): 128 blends
+    // 806 - 807 / 994 - 997 / 982 - 995 / 625 - 627, 256: 1 053 - 1 064 / 1 160 - 1 183 /
+    // 1 248 - 1 256 / 861 - 870, 512: 1 244 - 1 247 / 1 338 - 1 340 / 1 326 - 1 336 / 1 131 -
+    // 1 143, 1024: 1 357 - 1 359 / 1 398 - 1 403 / 1 372 - 1 376 / 1 280 - 1 285 with a
+    // persistent update grid of the whole chip; with the half grid a range that shares the chip
+    // now gets (kernels.hip: update_launch_plan) 1024 blends give 1 438 - 1 457 with two ranges
+    // and 1 451 - 1 459 with three.  Three ranges win at 256 blends and lose nowhere by more
+    // than the spread: the rule stays.
     const int queues = g_hw_queues.load(std::memory_order_relaxed);  // smi_set_hw_queues
     int n = b->n_sub > 0 ? b->n_sub : (nb < 128 ? 1 : (queues >= 8 && nb < 768) ? 4 : 3);
     // boxes of several size classes (one latency-bound launch per class and range): two ranges

@@ -502,6 +502,36 @@ int launch_sweep_timing(const SweepPlanDev *d_plans, const SweepPlanDev &host_pl
                         long long *cycles, float *images, hipStream_t s);
 // rounded_math.h's sqrt_rn_normal on host arrays (kernels.hip; test entry)
 int sqrt_rn_normal_test(const float *x, float *y, int64_t n);
+// The launch launch_update_reg (kernels.hip) makes of `n_items` components of size class `cls`:
+// a function of its arguments alone, so the rules can be tested without a device
+// (smi_update_launch_plan_test).  `stage_bytes` < 0: the class has no ring plan to stage;
+// `range_items`: components of all classes in the range of blends the launch belongs to;
+// `shared`: other ranges of the batch are in flight beside this one.
+enum UpdateFold : int32_t {
+    kFoldNone = 0,      // no loss bookkeeping is waiting for this launch
+    kFoldTrailing = 1,  // one trailing workgroup per blend of the range
+    kFoldInGrid = 2,    // inside the persistent grid: workgroup i takes blends i, i + n_blocks, ...
+    kFoldSeparate = 3,  // finalize_kernel, launched in front of the updates
+};
+struct UpdateLaunchSwitches {  // development aids (environment of launch_update_reg)
+    int32_t forced_pack = 0, forced_blocks = 0;
+    bool may_stage = true, may_persist = true;
+    int32_t fold_mode = 2;  // SMI_FOLD_FINALIZE: 1 = with every launch
+};
+struct UpdateLaunchPlan {
+    int32_t pack = 1;        // wavefronts (one-wavefront classes) per workgroup
+    int32_t n_blocks = 0;    // workgroups that update (trailing ones not counted)
+    int32_t persistent = 0;  // 1: workgroup i loops over share i of the list
+    int32_t stage = 0;       // 1: the class's ring plan is copied into LDS
+    int32_t gather_off = -1; // byte offset of the gather table in the dynamic LDS, -1: none
+    int32_t fold = kFoldNone;
+    size_t lds = 0, lds_table = 0;  // dynamic LDS without / with the gather table
+};
+// (test entry) the plan of this host thread's last launch that had a bookkeeping to place
+UpdateLaunchPlan update_last_fold_plan();
+UpdateLaunchPlan update_launch_plan(int32_t n_items, int32_t cls, int64_t stage_bytes, int32_t cus,
+                                    int32_t range_items, bool pending, bool shared,
+                                    const UpdateLaunchSwitches &sw);
 // box resizing (kernels.hip: resize_test_kernel and the state records)
 void launch_resize_test(const BatchView &v, int32_t *margin, double *pull, hipStream_t s);
 void launch_gather_states(const BatchView &v, const int32_t *sel, const int64_t *off, int32_t n_sel,

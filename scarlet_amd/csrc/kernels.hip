@@ -2243,6 +2243,8 @@ constexpr int update_pack_max(int npl, int team) {
 // it (a counter in LDS) until it is used up -- a workgroup that holds 150 KB of LDS must not
 // idle behind its slowest component.  (One global counter per XCD, measured: 10 240 atomic
 // additions on eight addresses take 0.25 ms, longer than the updates themselves.)
+// `persistent` == 2: the grid also does the loss bookkeeping of the range's blends (below);
+// `n_finalize` > 0: trailing workgroups do (launches that are not persistent).
 template <int NPL, int MODE, int T, bool EXT>
 __global__ __launch_bounds__(T * update_pack_max(NPL, T)) SMI_WAVES void update_kernel_reg(
     BatchView v, const float *G, int it, float e_rel, int prox_max_iter, int n_items,
@@ -2294,6 +2296,16 @@ __global__ __launch_bounds__(T * update_pack_max(NPL, T)) SMI_WAVES void update_
         }
         __syncthreads();
     }
+    // persistent == 2: the loss bookkeeping of the range rides in this grid (no trailing
+    // workgroups: they would carry the launch's threads and LDS and queue behind the persistent
+    // ones).  Workgroup i takes blends i, i + n_blocks, ... of the range, its last wavefront
+    // does them before it draws its first component -- here, where nothing of an update is
+    // live yet: at the end of the loop the same call costs every one-wavefront instance a
+    // register or scratch (<27,0,64>: 166 -> 167 VGPRs).  The other wavefronts do not wait:
+    // they draw from the share in the meantime.
+    if (T == 64 && persistent == 2 && wave == pack - 1)
+        for (int bl = (int)blockIdx.x; bl < v.nb; bl += n_blocks)
+            finalize_blend(v, bl + v.blend0, it, e_rel, min_iter, check);
     // persistent: share blockIdx.x of the list (contiguous: the components of a blend stay
     // together, in one L2 and mostly in one CU); otherwise one item per wavefront
     const bool loop = T == 64 && persistent;
@@ -2845,8 +2857,16 @@ static size_t update_lds_bytes(const BatchView &v) {
 struct PendingFinalize {
     bool on = false;
     int32_t min_iter = 0, check = 0;
+    int32_t mode = 2;  // SMI_FOLD_FINALIZE (launch_update_finalize)
 };
 static thread_local PendingFinalize pending_finalize;
+// trailing workgroups only for a range of few components (or SMI_FOLD_FINALIZE=1)
+static bool may_trail(const PendingFinalize &fin, const BatchView &v) {
+    return fin.mode == 1 || v.n_comp <= kUpdatePackLimit;
+}
+// test entry smi_update_last_fold_plan_test: the launch that last carried a bookkeeping
+static thread_local UpdateLaunchPlan last_fold_plan;
+UpdateLaunchPlan update_last_fold_plan() { return last_fold_plan; }
 
 static int cu_count() {
     static int count[kMaxDevices] = {};
@@ -2859,6 +2879,93 @@ static int cu_count() {
     return count[dev];
 }
 
+// The geometry of one update_kernel_reg launch, a pure function of its arguments (common.h:
+// UpdateLaunchPlan; test entry smi_update_launch_plan_test).
+UpdateLaunchPlan update_launch_plan(int32_t n_items, int32_t cls, int64_t stage_bytes, int32_t cus,
+                                    int32_t range_items, bool pending, bool shared,
+                                    const UpdateLaunchSwitches &sw) {
+    const int T = kUpdateTeam[cls], NPL = kUpdateNpl[cls];
+    const int kPack = update_pack_max(NPL, T);
+    UpdateLaunchPlan p;
+    // small launches are packed (update_kernel_reg); a launch that fills the chip anyway keeps
+    // one wavefront per workgroup, whose slots free up one by one
+    int pack = n_items <= kUpdatePackLimit ? kPack : 1;
+    if (sw.forced_pack > 0) pack = std::min(sw.forced_pack, kPack);
+    // the ring plan of the class staged in LDS: full workgroups, persistent when the list is
+    // longer than the chip is wide
+    int n_blocks = (n_items + pack - 1) / pack;
+    const size_t per_wave = (size_t)(T * NPL + 4) * sizeof(float);
+    size_t lds = (size_t)pack * per_wave;
+    if (T == 64 && sw.may_stage && stage_bytes >= 0) {
+        // as many wavefronts as fit the LDS beside the stream (61^2 boxes: seven images of 15 KB
+        // and 49 KB of plan)
+        const size_t fixed = (size_t)kPack * 64 * sizeof(float) + 64 + (size_t)stage_bytes;
+        const int fit = fixed < 160 * 1024 ? (int)((160 * 1024 - fixed) / per_wave) : 0;
+        if (fit >= 4) {
+            p.stage = 1;
+            pack = std::min(sw.forced_pack > 0 ? pack : kPack, fit);
+            lds = (size_t)pack * per_wave + (size_t)stage_bytes;
+            n_blocks = (n_items + pack - 1) / pack;
+            const int per_cu = std::max(1, (int)((160 * 1024) / (lds + kPack * 256 + 64)));
+            const int resident = cus * per_cu;
+            if (sw.forced_blocks > 0 && n_blocks > sw.forced_blocks) {
+                n_blocks = sw.forced_blocks;
+                p.persistent = 1;
+            } else if (n_blocks > resident && sw.may_persist) {
+                // `shared`: the launch is one range of several that are in flight side by side
+                // (batch.hip: sub_ranges).  A CU that holds one of these workgroups cannot take a
+                // workgroup of the other ranges' convolutions (111 KB of LDS, every register), so
+                // where a workgroup fills a CU the persistent grid takes half the chip and leaves
+                // the other half to them.  Where several workgroups share a CU half a grid would
+                // still be spread over every CU: those keep the full grid.  Measured on MI355X,
+                // bench.py at 1024 blends (ranges of 3 413 / 5 120 / 10 240 boxes of 41^2 for 3 /
+                // 2 / 1 ranges), k blend-it/s, lowest - highest of three runs, by SMI_PERSIST_BLOCKS:
+                //   3 ranges: 256 (chip) 1 361 - 1 378, 143 1 397 - 1 410 (two more jobs: 1 400 -
+                //             1 422, 1 412 - 1 417), 128 1 451 - 1 459, 114 1 422 - 1 431,
+                //             95 1 448 - 1 468, 72 1 391 - 1 409; one-shot workgroups
+                //             (SMI_PERSIST=0) 1 370 - 1 378
+                //   2 ranges: 256 1 396 - 1 414, 214 1 401 - 1 405, 171 1 412 - 1 417,
+                //             143 1 424 - 1 450, 128 1 438 - 1 457, 107 1 375 - 1 415, 86 1 423 - 1 434
+                //   1 range:  256 1 357 - 1 360, 214 1 317 - 1 332 (nothing to share with)
+                // Grids whose shares are whole multiples of the twelve wavefronts (143: 24, 95: 36
+                // for 3 413) are not what decides: the wavefronts draw from the share one by one.
+                // The curve is not monotonic (128 and 95 above 114) and why was not looked into.
+                // Only the 41^2 class at 1024 blends was measured: that the 51^2 and 61^2 classes
+                // (eight and seven wavefronts, one workgroup per CU as well) and other range counts
+                // gain from the same half is extrapolated from it.
+                n_blocks = shared && per_cu == 1 ? (resident + 1) / 2 : resident;
+                p.persistent = 1;
+            }
+        }
+    }
+    p.pack = pack;
+    p.n_blocks = n_blocks;
+    p.lds = p.lds_table = lds;
+    // the table of gather offsets behind the staged stream (update_kernel_reg), where it
+    // costs neither a wavefront of the workgroup nor a workgroup of the CU
+    if (p.stage) {
+        const size_t fixed = (size_t)kPack * 256 + 64;  // (static LDS of the kernel)
+        const size_t off = (size_t)pack * per_wave + (((size_t)stage_bytes + 15) & ~(size_t)15);
+        const size_t with = off + (size_t)T * NPL * sizeof(uint32_t);
+        if (with + fixed <= 160 * 1024 &&
+            (160 * 1024) / (with + fixed) == (160 * 1024) / (lds + fixed)) {
+            p.gather_off = (int32_t)off;
+            p.lds_table = with;
+        }
+    }
+    // how a pending loss bookkeeping travels: inside a persistent grid (its workgroups stay
+    // n_blocks: a trailing workgroup would carry the launch's threads and LDS and queue behind
+    // the persistent ones), as trailing workgroups where the whole range is small (`range_items`
+    // components of all its classes), else as the kernel of its own in front of this one.
+    // (Trailing workgroups wherever this LAUNCH is small, the first class of a large range of
+    // several classes: bench.py --config cfg1, 1 601 - 1 618 k blend-it/s against 1 621 - 1 629.)
+    if (pending)
+        p.fold = p.persistent ? kFoldInGrid
+                 : (sw.fold_mode == 1 || range_items <= kUpdatePackLimit) ? kFoldTrailing
+                                                                          : kFoldSeparate;
+    return p;
+}
+
 template <int NPL, int T>
 static int launch_update_reg(const BatchView &v, const float *G, int32_t it, float e_rel,
                              int32_t prox_max_iter, int32_t cls, int32_t item0, int32_t n_items,
@@ -2867,71 +2974,29 @@ static int launch_update_reg(const BatchView &v, const float *G, int32_t it, flo
     vi.work0 = item0;
     const PendingFinalize fin = pending_finalize;
     pending_finalize.on = false;
-    const int n_fin = fin.on ? v.nb : 0;
-    // small launches are packed (update_kernel_reg); a launch that fills the chip anyway keeps
-    // one wavefront per workgroup, whose slots free up one by one.  SMI_UPDATE_PACK (development
-    // aid) overrides the number of wavefronts per workgroup.
-    static const int forced = [] {
-        const char *e = getenv("SMI_UPDATE_PACK");
-        return e ? atoi(e) : 0;
+    // development aids: SMI_UPDATE_PACK overrides the number of wavefronts per workgroup,
+    // SMI_STAGE_PLAN=0 never stages the ring plan in LDS, SMI_PERSIST=0 gives one-shot
+    // workgroups, SMI_PERSIST_BLOCKS=n a persistent grid of n
+    static const UpdateLaunchSwitches env = [] {
+        UpdateLaunchSwitches sw;
+        if (const char *e = getenv("SMI_UPDATE_PACK")) sw.forced_pack = atoi(e);
+        if (const char *e = getenv("SMI_STAGE_PLAN")) sw.may_stage = atoi(e) != 0;
+        if (const char *e = getenv("SMI_PERSIST")) sw.may_persist = atoi(e) != 0;
+        if (const char *e = getenv("SMI_PERSIST_BLOCKS")) sw.forced_blocks = atoi(e);
+        return sw;
     }();
-    // SMI_STAGE_PLAN=0 (development aid): never stage the ring plan in LDS
-    static const bool may_stage = [] {
-        const char *e = getenv("SMI_STAGE_PLAN");
-        return !e || atoi(e) != 0;
-    }();
-    constexpr int kPack = update_pack_max(NPL, T);
-    int pack = n_items <= kUpdatePackLimit ? kPack : 1;
-    if (forced > 0) pack = std::min(forced, kPack);
-    // the ring plan of the class staged in LDS: full workgroups, persistent when the list is
-    // longer than the chip is wide
-    int stage = -1, persistent = 0;
-    int n_blocks = (n_items + pack - 1) / pack;
-    size_t lds = (size_t)pack * (T * NPL + 4) * sizeof(float);
-    if (T == 64 && may_stage && v.stage_plan[cls] >= 0) {
-        // as many wavefronts as fit the LDS beside the stream (61^2 boxes: seven images of 15 KB
-        // and 49 KB of plan)
-        const size_t per_wave = (size_t)(T * NPL + 4) * sizeof(float);
-        const size_t fixed = (size_t)kPack * 64 * sizeof(float) + 64 + v.stage_bytes[cls];
-        const int fit = fixed < 160 * 1024 ? (int)((160 * 1024 - fixed) / per_wave) : 0;
-        if (fit >= 4) {
-            stage = v.stage_plan[cls];
-            pack = std::min(forced > 0 ? pack : kPack, fit);
-            lds = (size_t)pack * per_wave + v.stage_bytes[cls];
-            n_blocks = (n_items + pack - 1) / pack;
-            const int resident = cu_count() * std::max(1, (int)((160 * 1024) / (lds + kPack * 256 + 64)));
-            static const bool may_persist = [] {  // development aid
-                const char *e = getenv("SMI_PERSIST");
-                return !e || atoi(e) != 0;
-            }();
-            static const int forced_blocks = [] {  // development aid
-                const char *e = getenv("SMI_PERSIST_BLOCKS");
-                return e ? atoi(e) : 0;
-            }();
-            if (forced_blocks > 0 && n_blocks > forced_blocks) {
-                n_blocks = forced_blocks;
-                persistent = 1;
-            } else if (n_blocks > resident && may_persist) {
-                n_blocks = resident;
-                persistent = 1;
-            }
-        }
-    }
-    // the table of gather offsets behind the staged stream (update_kernel_reg), where it
-    // costs neither a wavefront of the workgroup nor a workgroup of the CU
-    int gather_off = -1;
-    size_t lds_table = lds;
-    if (stage >= 0) {
-        const size_t fixed = (size_t)kPack * 256 + 64;  // (static LDS of the kernel)
-        const size_t off = (size_t)pack * (T * NPL + 4) * sizeof(float) +
-                           (((size_t)v.stage_bytes[cls] + 15) & ~(size_t)15);
-        const size_t with = off + (size_t)T * NPL * sizeof(uint32_t);
-        if (with + fixed <= 160 * 1024 &&
-            (160 * 1024) / (with + fixed) == (160 * 1024) / (lds + fixed)) {
-            gather_off = (int)off;
-            lds_table = with;
-        }
-    }
+    UpdateLaunchSwitches sw = env;
+    sw.fold_mode = fin.mode;
+    const UpdateLaunchPlan p =
+        update_launch_plan(n_items, cls, v.stage_plan[cls] >= 0 ? (int64_t)v.stage_bytes[cls] : -1,
+                           cu_count(), v.n_comp, fin.on, v.nb < v.nb_total, sw);
+    if (p.fold != kFoldNone) last_fold_plan = p;
+    if (p.fold == kFoldSeparate) launch_finalize(v, it, e_rel, fin.min_iter, fin.check, s);
+    const int n_fin = p.fold == kFoldTrailing ? v.nb : 0;
+    const int stage = p.stage ? v.stage_plan[cls] : -1;
+    const int persistent = p.persistent ? (p.fold == kFoldInGrid ? 2 : 1) : 0;
+    const int n_blocks = p.n_blocks, pack = p.pack, gather_off = p.gather_off;
+    const size_t lds = p.lds, lds_table = p.lds_table;
     const dim3 grid(n_blocks + n_fin), block(T * pack);
 #define SMI_LAUNCH_EXT(MODE, EXT)                                                               \
     {                                                                                           \
@@ -2958,20 +3023,25 @@ static int launch_update_reg(const BatchView &v, const float *G, int32_t it, flo
     return SMI_OK;
 }
 
-// finalize + update of one iteration: the loss bookkeeping shares the first launch of a
-// register-resident size class; where no such launch exists (mixed / general kernels, a
-// range without components) it is the kernel of its own it used to be
+// finalize + update of one iteration.  A range of at most kUpdatePackLimit components: the
+// loss bookkeeping rides as trailing workgroups of the first per-class launch or of the mixed
+// launch, and follows the updates where neither exists (general kernels).  A larger range: it
+// rides inside the grid of the first per-class launch if that one is persistent
+// (update_launch_plan), and is the kernel of its own in front of the updates otherwise (per-class
+// launch that is not persistent, mixed kernel, general kernels) -- as before in both cases, but
+// for the persistent grid.  A range without components: the kernel of its own.
 int launch_update_finalize(const BatchView &v, const float *G, int32_t it, float e_rel,
                            int32_t min_iter, int32_t check, int32_t prox_max_iter,
                            hipStream_t s) {
-    static const int mode = [] {  // development aid: 0 never, 1 always, default: small launches
+    static const int mode = [] {  // development aid: 0 never, 1 every launch, default: as above
         const char *e = getenv("SMI_FOLD_FINALIZE");
         return e ? atoi(e) : 2;
     }();
-    if (mode == 0 || (mode == 2 && v.n_comp > kUpdatePackLimit)) {
+    if (mode == 0) {
         launch_finalize(v, it, e_rel, min_iter, check, s);
         return launch_update(v, G, it, e_rel, prox_max_iter, nullptr, nullptr, 0, s);
     }
+    pending_finalize.mode = mode;
     pending_finalize.on = true;
     pending_finalize.min_iter = min_iter;
     pending_finalize.check = check;
@@ -3008,7 +3078,15 @@ int launch_update(const BatchView &v_in, const float *G, int32_t it, float e_rel
             const size_t lds = (size_t)(64 * kUpdateNpl[kNumUpdateClasses - 1] + 4) * sizeof(float);
             const PendingFinalize fin = pending_finalize;
             pending_finalize.on = false;
-            const int n_fin = fin.on ? v.nb : 0;
+            // (a range of more than kUpdatePackLimit components: the kernel of its own, in front)
+            const bool trail = fin.on && may_trail(fin, v);
+            if (fin.on && !trail) launch_finalize(v_in, it, e_rel, fin.min_iter, fin.check, s);
+            const int n_fin = trail ? v.nb : 0;
+            if (fin.on) {  // (test entry: one wavefront per workgroup, one workgroup per component)
+                last_fold_plan = UpdateLaunchPlan();
+                last_fold_plan.n_blocks = v.n_comp;
+                last_fold_plan.fold = trail ? kFoldTrailing : kFoldSeparate;
+            }
             const dim3 grid(v.n_comp + n_fin);
             static const int one_wave_limit = [] {  // development aid
                 const char *e = getenv("SMI_MIXED_ONE_WAVE");
@@ -3107,6 +3185,13 @@ int launch_update(const BatchView &v_in, const float *G, int32_t it, float e_rel
             ++n_side;
         }
         return SMI_OK;
+    }
+    // the general kernels carry no bookkeeping: for a range of more than kUpdatePackLimit
+    // components it stays in front of them (launch_update_finalize)
+    if (pending_finalize.on && !may_trail(pending_finalize, v)) {
+        const PendingFinalize fin = pending_finalize;
+        pending_finalize.on = false;
+        launch_finalize(v_in, it, e_rel, fin.min_iter, fin.check, s);
     }
     const size_t lds = update_lds_bytes(v);
     SMI_REQUIRE(lds <= 160 * 1024, "component box too large for the LDS-resident update");
