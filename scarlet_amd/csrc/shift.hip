@@ -42,6 +42,12 @@ __device__ __forceinline__ double block_sum(double v, double *scratch) {
     return scratch[0] + scratch[1] + scratch[2] + scratch[3];
 }
 
+// "any thread non-zero" through the same slots: unlike __syncthreads_or it takes no static LDS, so
+// the kernels' whole LDS is the dynamic size the host checks against the 160 KiB
+__device__ __forceinline__ int block_any(int flag, double *scratch) {
+    return block_sum(flag ? 1.0 : 0.0, scratch) != 0.0;
+}
+
 struct AxisOut {
     float *r;    // Dr / Tx
     float *h;    // Hx (x axis only)
@@ -323,7 +329,7 @@ __global__ __launch_bounds__(kT) void shift_forward_kernel(BatchView v, int resp
     axis_vectors(v.c_shift_fft[2 * k + 1], w, pt[1], true, false,
                  AxisOut{L.tx, L.hx, nullptr, nullptr}, L.ct, L.st, L.cb, L.sb);
     const float beta = (float)by.x;
-    const int bad = __syncthreads_or(shift_apply(L, h, w, beta, v.morph + moff, w));
+    const int bad = block_any(shift_apply(L, h, w, beta, v.morph + moff, w), L.red);
     if (bad) atomicExch(&v.state[b], v.fail_code);
 }
 
@@ -428,7 +434,7 @@ __global__ __launch_bounds__(kT) void psf_shift_forward_kernel(BatchView v, Kern
     axis_vectors(ks.Fx, w, st[1], true, false, AxisOut{L.tx, L.hx, nullptr, nullptr}, L.ct, L.st,
                  L.cb, L.sb);
     float *out = ks.shifted + ((int64_t)img * ks.ph + ks.oy) * ks.pw + ks.ox;
-    const int bad = __syncthreads_or(shift_apply(L, h, w, (float)by.x, out, ks.pw));
+    const int bad = block_any(shift_apply(L, h, w, (float)by.x, out, ks.pw), L.red);
     if (bad && tid == 0) atomicExch(&v.state[b], v.fail_code);
 }
 
