@@ -144,6 +144,45 @@ int smi_reweight_f64(int32_t device, int32_t C, int32_t kh, int32_t kw, int32_t 
                      int64_t n_sed, const double *morphs, int64_t n_morph, double *out,
                      int64_t n_out);
 
+/* lite.fit_spectra_blends: the normal equations of multifit_seds (reference
+ * scarlet/lite/initialization.py:140-186) for a catalogue of blends that share the number of
+ * bands C and the (kh, kw) difference-kernel stamp.  Per blend and band, with one column per
+ * component -- its morphology, zero outside its own box, convolved ("same") with the band's
+ * stamp on the union box of all component boxes -- and d the image on the union box, zero
+ * outside the frame:
+ *
+ *   out[blend.out_off + band (K K + K) + p K + q] = sum of column p x column q   (G, symmetric)
+ *   out[blend.out_off + band (K K + K) + K K + p] = sum of column p x d          (r)
+ *
+ * in float64, K = n_comp.  Host buffers in, host buffer out; coordinates relative to the
+ * frame's corner; offsets and sizes count elements.  images[blend.image_off .. + C h w];
+ * stamps[blend.stamp_off .. + C kh kw] in float64; morphs[component.morph_off .. + h w], rows of
+ * w.  The union box (y0, x0, fh, fw) must hold every component box.  Limits: stamp sides
+ * <= 63, 1 .. 64 components per blend, at most 32 components whose box grown by the stamp's half
+ * meets one 16 x 16 tile of the union box, union box and morphology sides <= 4096.  The plan
+ * is validated before anything is launched: a bad one returns SMI_ERR_INVALID and leaves
+ * `out` alone.  The sums of a blend have the same bits wherever it stands in the tables. */
+typedef struct smi_lite_spectra_blend {
+    int32_t h, w;            /* frame */
+    int32_t y0, x0, fh, fw;  /* union box of the components, may leave the frame */
+    int32_t comp0, n_comp;
+    int64_t image_off, stamp_off, out_off;
+} smi_lite_spectra_blend;
+typedef struct smi_lite_spectra_component {
+    int32_t y0, x0, h, w;    /* box of the morphology */
+    int64_t morph_off;
+} smi_lite_spectra_component;
+int smi_lite_spectra_f32(int32_t device, int32_t C, int32_t kh, int32_t kw, int32_t n_blends,
+                         const smi_lite_spectra_blend *blends, int32_t n_components,
+                         const smi_lite_spectra_component *components, const float *images,
+                         int64_t n_image, const double *stamps, int64_t n_stamp,
+                         const float *morphs, int64_t n_morph, double *out, int64_t n_out);
+int smi_lite_spectra_f64(int32_t device, int32_t C, int32_t kh, int32_t kw, int32_t n_blends,
+                         const smi_lite_spectra_blend *blends, int32_t n_components,
+                         const smi_lite_spectra_component *components, const double *images,
+                         int64_t n_image, const double *stamps, int64_t n_stamp,
+                         const double *morphs, int64_t n_morph, double *out, int64_t n_out);
+
 /* lite.init_blends: the wavelet initialisation of scarlet.lite (reference
  * lite/initialization.py:422-605) for a catalogue of blends.  Six steps, each one launch
  * over a table of tasks; the caller owns every buffer (`d_*`: device memory) and orders the

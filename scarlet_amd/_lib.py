@@ -70,6 +70,15 @@ def _REWEIGHT(fp):
             + [fp, ctypes.c_int64] * 5)
 
 
+def _LITE_SPECTRA(fp):
+    """smi_lite_spectra_*: device, C, kh, kw, then (count, table) of the blend and component
+    descriptors (numpy records of lite/spectra.py, passed as void *), then the (buffer, size)
+    pairs images, stamps (float64), morphs, out (float64)."""
+    return ([ctypes.c_int32] * 4 + [ctypes.c_int32, ctypes.c_void_p] * 2
+            + [fp, ctypes.c_int64, c_f64p, ctypes.c_int64, fp, ctypes.c_int64, c_f64p,
+               ctypes.c_int64])
+
+
 def _LITE_INIT():
     """smi_lite_init_*: every entry takes (count, host table, device table), then device
     buffers as void * with their sizes in elements, then the stream (lite/initialization.py)."""
@@ -169,6 +178,8 @@ SYMBOLS = {
     ),
     "smi_reweight_f32": (ctypes.c_int, _REWEIGHT(c_f32p)),
     "smi_reweight_f64": (ctypes.c_int, _REWEIGHT(c_f64p)),
+    "smi_lite_spectra_f32": (ctypes.c_int, _LITE_SPECTRA(c_f32p)),
+    "smi_lite_spectra_f64": (ctypes.c_int, _LITE_SPECTRA(c_f64p)),
     "smi_get_valid_monotonic_pixels_f32": (
         ctypes.c_int,
         [ctypes.c_int32, ctypes.c_int32, c_f32p, ctypes.c_int32, ctypes.c_int32, c_u8p, c_u8p,

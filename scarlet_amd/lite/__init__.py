@@ -33,6 +33,7 @@ from .parameters import (  # noqa: F401
     LiteParameter,
     grow_array,
 )
+from .spectra import fit_spectra_blends, plan_fit_spectra_blends  # noqa: F401
 from .utils import (  # noqa: F401
     bounds_to_bbox,
     get_circle_mask,

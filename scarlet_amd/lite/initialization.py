@@ -25,6 +25,7 @@ from ..parameter import relative_step
 from .measure import calculate_snr
 from .models import LiteComponent, LiteFactorizedComponent, LiteSource
 from .parameters import AdaproxParameter, FistaParameter
+from .spectra import _solve_spectra
 from .utils import bounds_to_bbox, insert_image, project_morph_to_center
 
 
@@ -494,12 +495,7 @@ def _solve_pairs(sums, dtype):
     gram = np.empty((n, C, 2, 2))
     gram[..., 0, 0], gram[..., 1, 1] = sums[..., 0], sums[..., 2]
     gram[..., 0, 1] = gram[..., 1, 0] = sums[..., 1]
-    # (lstsq drops singular values of the design below eps * pixels of the largest; their
-    # squares are the eigenvalues here, which float64 sums resolve to about 1e-12)
-    sol = np.einsum("ncij,ncj->nci", np.linalg.pinv(gram, rcond=1e-12, hermitian=True),
-                    sums[..., 3:])
-    seds[:] = np.moveaxis(sol, 1, 2)
-    seds[seds < 0] = 0
+    seds[:] = np.moveaxis(_solve_spectra(gram, sums[..., 3:], dtype), 1, 2)
     return seds
 
 

@@ -355,6 +355,12 @@ class LiteBlend:
 
         seds = multifit_seds(self.observation, [c.morph for c in self.components],
                              [c.bbox[1:] for c in self.components])
+        return self._set_spectra(seds, clip)
+
+    def _set_spectra(self, seds, clip):
+        """The tail of ``fit_spectra``, shared with ``lite.fit_spectra_blends``: writes
+        ``seds[k]`` into the spectrum array of component ``k``, then drops the components
+        without spectrum or morphology (``clip``) or applies ``prox_sed``."""
         for c, sed in zip(self.components, seds):
             c.sed[:] = sed
             c.sed[c.sed < 0] = 0
