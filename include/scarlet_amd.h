@@ -144,6 +144,40 @@ int smi_reweight_f64(int32_t device, int32_t C, int32_t kh, int32_t kw, int32_t 
                      int64_t n_sed, const double *morphs, int64_t n_morph, double *out,
                      int64_t n_out);
 
+/* lite.measure_blends: the sums of a catalogue row over the flux cubes of smi_reweight_* above,
+ * without the cubes having to leave the device.  Tables and input buffers are those of
+ * smi_reweight_*, validated the same way (a bad plan returns SMI_ERR_INVALID before anything is
+ * launched).  `out` may be NULL (then n_out must be 0 and out_off is ignored): no cube is
+ * stored, allocated or copied; otherwise it receives bit for bit what smi_reweight_* writes.
+ * records[(source * C + band) * SMI_LITE_MEASURE_RECORD + k], n_record >= n_sources * C *
+ * SMI_LITE_MEASURE_RECORD, in float64, with f the source's flux, M its convolved model clipped
+ * at 0, and y, x integers counted from the corner of the source's rectangle:
+ *
+ *   k = 0 sum M      2 sum f      4 sum x f      6 sum y x f    8 the largest f
+ *       1 sum M^2    3 sum y f    5 sum y^2 f    7 sum x^2 f    9 y * w + x of its first pixel
+ *
+ * (row-major first, as np.argmax; -1 when no f compares: not-a-number data).  The order of
+ * every sum depends on the (h, w) of the source's rectangle alone, so a source's record has the
+ * same bits wherever it stands in the tables. */
+#define SMI_LITE_MEASURE_RECORD 10
+int smi_lite_measure_f32(int32_t device, int32_t C, int32_t kh, int32_t kw, int32_t n_blends,
+                         const smi_reweight_blend *blends, int32_t n_sources,
+                         const smi_reweight_source *sources, int32_t n_components,
+                         const smi_reweight_component *components, const float *images,
+                         int64_t n_image, const float *stamps, int64_t n_stamp, const float *seds,
+                         int64_t n_sed, const float *morphs, int64_t n_morph, float *out,
+                         int64_t n_out, double *records, int64_t n_record);
+int smi_lite_measure_f64(int32_t device, int32_t C, int32_t kh, int32_t kw, int32_t n_blends,
+                         const smi_reweight_blend *blends, int32_t n_sources,
+                         const smi_reweight_source *sources, int32_t n_components,
+                         const smi_reweight_component *components, const double *images,
+                         int64_t n_image, const double *stamps, int64_t n_stamp, const double *seds,
+                         int64_t n_sed, const double *morphs, int64_t n_morph, double *out,
+                         int64_t n_out, double *records, int64_t n_record);
+/* milliseconds the three launches of the calling thread's last smi_lite_measure_* call took on
+ * the device (events around them), for tools/lite_measure_time.py */
+int smi_lite_measure_last_launch_ms(double *ms);
+
 /* lite.fit_spectra_blends: the normal equations of multifit_seds (reference
  * scarlet/lite/initialization.py:140-186) for a catalogue of blends that share the number of
  * bands C and the (kh, kw) difference-kernel stamp.  Per blend and band, with one column per

@@ -178,6 +178,10 @@ SYMBOLS = {
     ),
     "smi_reweight_f32": (ctypes.c_int, _REWEIGHT(c_f32p)),
     "smi_reweight_f64": (ctypes.c_int, _REWEIGHT(c_f64p)),
+    # lite/catalog.py: the arguments of smi_reweight_* (out may be None), then the records
+    "smi_lite_measure_f32": (ctypes.c_int, _REWEIGHT(c_f32p) + [c_f64p, ctypes.c_int64]),
+    "smi_lite_measure_f64": (ctypes.c_int, _REWEIGHT(c_f64p) + [c_f64p, ctypes.c_int64]),
+    "smi_lite_measure_last_launch_ms": (ctypes.c_int, [c_f64p]),
     "smi_lite_spectra_f32": (ctypes.c_int, _LITE_SPECTRA(c_f32p)),
     "smi_lite_spectra_f64": (ctypes.c_int, _LITE_SPECTRA(c_f64p)),
     "smi_get_valid_monotonic_pixels_f32": (

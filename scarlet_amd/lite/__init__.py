@@ -1,6 +1,7 @@
 """``scarlet.lite`` on the GPU: same names as the reference's lite package
 (scarlet/lite/__init__.py), the fitting loop of ``LiteBlend.fit`` on the device."""
 
+from .catalog import measure_blends, plan_measure_blends  # noqa: F401
 from .fitting import fit_blends  # noqa: F401
 from .initialization import (  # noqa: F401
     get_min_psf,
