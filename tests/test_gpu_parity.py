@@ -1241,11 +1241,17 @@ def test_more_than_64_components_in_one_blend(amd):
 
 def test_boxes_beyond_the_lds(amd):
     """121^2 box (what lite's detection-image initialisation produces on small frames):
-    the generic update kernel keeps x / psi / z in a global scratch area, the swept
-    image in LDS"""
+    14641 pixels, the largest four-wavefront class of the register-resident update kernel
+    (up to kMaxRegisterBox = 15104 pixels; the image in LDS, x and psi in a global array).
+    Then a 123^2 box, 15129 pixels: the whole batch takes the generic update kernel, which
+    keeps x / psi / z in a global scratch area and the swept image in LDS.  (Class by class:
+    tests/test_gpu_update_classes.py.)"""
     rng = np.random.default_rng(24)
     specs, kernel, data, weights = _random_scene(
         rng, 2, 100, 110, [((121, 121), (-10, -6)), ((21, 21), (40, 70))])
+    _compare_steps(amd, specs, None, data, weights, 2, {}, {})
+    specs, kernel, data, weights = _random_scene(
+        rng, 2, 100, 110, [((123, 123), (-11, -7)), ((21, 21), (40, 70))])
     _compare_steps(amd, specs, None, data, weights, 2, {}, {})
 
 

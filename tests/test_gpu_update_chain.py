@@ -1,7 +1,9 @@
 """The links of the proximal chain that follow the sweep (positivity, centre-on, normalisation)
 and the AMSGrad step of the register-resident update kernels, flag set by flag set, on boxes of
-every size class: against the CPU oracle, and bit for bit between update_kernel_mixed, the
-per-class update_kernel_reg launches and each component stepped alone.
+the size classes 0, 1, 2, 3, 4 and 6 (21^2, 31^2, 41^2 and 30 x 40, 51^2, 61^2, 71^2; classes 5, 7
+and 8, the boxes that fill a class, the boundaries of the sweep plans and the general kernel are
+in tests/test_gpu_update_classes.py): against the CPU oracle, and bit for bit between
+update_kernel_mixed, the per-class update_kernel_reg launches and each component stepped alone.
 
 Null renderer, three bands, a 96 x 96 frame; the boxes of a blend do not overlap, so a component's
 gradient does not depend on its neighbours and "alone" has the same bits to compare.  Blend 2
