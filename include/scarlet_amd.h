@@ -368,6 +368,89 @@ int smi_lite_init_main_split_f64(int32_t n, const smi_lite_init_main_split *task
                                  const void *d_tasks, double *d_morphs, int64_t n_morph,
                                  double level, void *stream);
 
+/* initialization.init_blends: the morphologies and the normal equations of the spectra of
+ * initialization.init_all_sources (reference initialization.py:30-170, 287-363, 493-588;
+ * source.py:249-522) for a catalogue of float32 blends, with the conventions of smi_lite_init_*
+ * above.  A chunk takes five launches, whatever its blends and sources.  d_data and d_var hold the cubes of build_initialization_image (data and
+ * noise_rms**2 on the model frame, (bands, h, w) per blend) at the same offsets; the variance
+ * is positive, and negated where the pixel has no weight: psf_snr leaves those pixels out and
+ * sweep reads the magnitude, as the coadd of the reference does.
+ *   psf_snr  per source and band the three float64 sums of get_psf_spectrum over the box of the
+ *            (ph, pw) PSF stamp on the pixel: sum d p, sum p p, sum p var p.  Pixels beyond the
+ *            frame hold zero data and zero noise; pixels with var <= 0 are left out.  out: 3
+ *            doubles per band
+ *   sweep    per source, one workgroup with the frame in LDS as float64 (at most (160 KiB -
+ *            1 KiB) / 8 pixels): the coadd weighted with the source's spectrum (bands doubles at
+ *            spec_off), prox_uncentered_symmetry(X, 0, centre, "sdss"),
+ *            prox_weighted_monotonic(shape, "flat", min_gradient=0, centre), then
+ *            X[~(X > thresh * std)] = 0.  Per task the plane, the bounds (min row, max row, min
+ *            col, max col) of its pixels > 0 -- (0, -1, 0, -1) without any -- and its maximum
+ *   crop     per source the (side, side) cut-out at (y0, x0), zeros beyond the frame, divided by
+ *            its maximum (one lit pixel in the middle where nothing is left), np.maximum with
+ *            the side * side doubles at floor_off; with layers == 2 split at percentile / 100 of
+ *            the peak as MultiExtendedSource.init_morphs does, each layer divided by its own
+ *            maximum.  out: layers * side * side doubles; flags: bit 0 where one is not
+ *            finite, bit 1 where the cut-out held no pixel > 0
+ *   spectra_tiles, spectra_reduce  the weighted normal equations of set_spectra_to_match.  A
+ *            blend names its (h, w) frame, the (fh, fw) region at (y0, x0) inside it that its
+ *            convolved models can reach, its float32 data and weight cubes at cube_off, its
+ *            (bands, kh, kw) float64 stamps (odd sides of at most 63; 1 x 1 for the identity) and
+ *            n_comp <= 64 components from comp0: float64 (h, w) morphologies with their origin
+ *            in frame coordinates, zero outside the box and outside the frame.  `work` lists
+ *            (blend, tile) of every 16 x 16 tile of every region, in order; at most 32 components
+ *            may reach one tile.  Per tile and band K K + 3 K doubles at part_off: G = A^T W A,
+ *            r = A^T W d, sum a w and sum a of the convolved columns a; reduce adds a blend's
+ *            tiles in order into out_off, [band][K K + 3 K] */
+typedef struct smi_init_sources_psf_snr {
+    int32_t h, w, cy, cx, ph, pw, bands, reserved;
+    int64_t cube_off, psf_off, out_off;
+} smi_init_sources_psf_snr;
+typedef struct smi_init_sources_sweep {
+    int32_t h, w, cy, cx, bands, reserved;
+    int64_t cube_off, spec_off, out_off;
+    double thresh;
+} smi_init_sources_sweep;
+typedef struct smi_init_sources_crop {
+    int32_t h, w;           /* plane */
+    int32_t y0, x0, side;   /* box, in plane coordinates */
+    int32_t layers;
+    int64_t plane_off, floor_off, out_off;
+    double percentile;
+} smi_init_sources_crop;
+typedef struct smi_init_sources_spectra_blend {
+    int32_t h, w;            /* frame */
+    int32_t y0, x0, fh, fw;  /* region, in frame coordinates */
+    int32_t bands, kh, kw;
+    int32_t n_comp, comp0, reserved;
+    int64_t cube_off, stamp_off, part_off, out_off;
+} smi_init_sources_spectra_blend;
+typedef struct smi_init_sources_spectra_component {
+    int32_t y0, x0, h, w;    /* box, in frame coordinates */
+    int64_t morph_off;
+} smi_init_sources_spectra_component;
+int smi_init_sources_psf_snr_f32(int32_t n, const smi_init_sources_psf_snr *tasks, const void *d_tasks,
+                             const float *d_data, const float *d_var, int64_t n_cube,
+                             const double *d_psfs, int64_t n_psf, double *d_out, int64_t n_out,
+                             void *stream);
+int smi_init_sources_sweep_f32(int32_t n, const smi_init_sources_sweep *tasks, const void *d_tasks,
+                           const float *d_data, const float *d_var, int64_t n_cube,
+                           const double *d_spectra, int64_t n_spectra, double *d_out,
+                           int64_t n_out, int32_t *d_bounds, double *d_peaks, int64_t n_results,
+                           void *stream);
+int smi_init_sources_crop_f32(int32_t n, const smi_init_sources_crop *tasks, const void *d_tasks,
+                          const double *d_planes, int64_t n_plane, const double *d_floors,
+                          int64_t n_floor, double *d_out, int64_t n_out, int32_t *d_flags,
+                          int64_t n_flags, void *stream);
+int smi_init_sources_spectra_tiles_f32(
+    int32_t n, const smi_init_sources_spectra_blend *blends, const void *d_blends, int32_t n_comps,
+    const smi_init_sources_spectra_component *comps, const void *d_comps, int32_t n_work,
+    const int32_t *work, const void *d_work, const float *d_data, const float *d_weights,
+    int64_t n_cube, const double *d_stamps, int64_t n_stamp, const double *d_morphs,
+    int64_t n_morph, double *d_part, int64_t n_part, int64_t n_out, void *stream);
+int smi_init_sources_spectra_reduce_f32(int32_t n, const smi_init_sources_spectra_blend *blends,
+                                        const void *d_blends, const double *d_part, int64_t n_part,
+                                        double *d_out, int64_t n_out, void *stream);
+
 /* get_valid_monotonic_pixels / linear_interpolate_invalid_pixels
  * (operators_pybind11.cc:61-232, float32 and float64 overload sets; callers
  * operator.py:155-176).  Row-major (rows, cols) images; `unchecked` / `orphans` are the

@@ -55,6 +55,7 @@ from .component import (  # noqa: F401
 )
 from .blend import Blend  # noqa: F401
 from .fitting import fit_blends  # noqa: F401
+from .initialization import init_blends, plan_init_blends  # noqa: F401
 from .source import (  # noqa: F401
     ExtendedSource,
     SingleExtendedSource,

@@ -111,6 +111,21 @@ def _DETECT_BATCH():
     return out
 
 
+def _INIT_SOURCES():
+    """smi_init_sources_*: (count, host table, device table), then device buffers as void *
+    with their sizes in elements, then the stream (initialization.init_blends)."""
+    v, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+    table = [i32, v, v]
+    return {
+        "smi_init_sources_psf_snr_f32": (ctypes.c_int, table + [v, v, i64, v, i64, v, i64, v]),
+        "smi_init_sources_sweep_f32": (ctypes.c_int, table + [v, v, i64, v, i64, v, i64, v, v, i64, v]),
+        "smi_init_sources_crop_f32": (ctypes.c_int, table + [v, i64, v, i64, v, i64, v, i64, v]),
+        "smi_init_sources_spectra_tiles_f32": (
+            ctypes.c_int, table * 3 + [v, v, i64, v, i64, v, i64, v, i64, i64, v]),
+        "smi_init_sources_spectra_reduce_f32": (ctypes.c_int, table + [v, i64, v, i64, v]),
+    }
+
+
 class BatchDesc(ctypes.Structure):
     _fields_ = [
         (name, ctypes.c_int32)
@@ -389,6 +404,7 @@ SYMBOLS = {
 }
 SYMBOLS.update(_LITE_INIT())
 SYMBOLS.update(_DETECT_BATCH())
+SYMBOLS.update(_INIT_SOURCES())
 
 _lib = None
 

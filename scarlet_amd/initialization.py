@@ -424,3 +424,733 @@ def set_spectra_to_match(sources, observations):
     for p in parameters:
         if p is not None and p.constraint is not None:
             p[:] = p.constraint(p, 0)
+
+
+# ---------------------------------------------------------------------------------------------
+# init_blends: init_all_sources for a catalogue of blends.  The morphologies of all sources of
+# a chunk of blends come from three launches of csrc/init_sources.hip (psf_snr, sweep, crop);
+# the source objects are assembled on the host through the existing classes, and the float64
+# normal equations of ``set_spectra=True`` come from two more (spectra_tiles, spectra_reduce);
+# the host solves them, K x K per blend and band.
+# ---------------------------------------------------------------------------------------------
+_i4, _i8 = np.int32, np.int64
+_PSF_SNR_DESC = np.dtype([("h", _i4), ("w", _i4), ("cy", _i4), ("cx", _i4), ("ph", _i4),
+                          ("pw", _i4), ("bands", _i4), ("reserved", _i4), ("cube_off", _i8),
+                          ("psf_off", _i8), ("out_off", _i8)], align=True)
+_SWEEP_DESC = np.dtype([("h", _i4), ("w", _i4), ("cy", _i4), ("cx", _i4), ("bands", _i4),
+                        ("reserved", _i4), ("cube_off", _i8), ("spec_off", _i8), ("out_off", _i8),
+                        ("thresh", "f8")], align=True)
+_CROP_DESC = np.dtype([("h", _i4), ("w", _i4), ("y0", _i4), ("x0", _i4), ("side", _i4),
+                       ("layers", _i4), ("plane_off", _i8), ("floor_off", _i8), ("out_off", _i8),
+                       ("percentile", "f8")], align=True)
+_SPECTRA_BLEND = np.dtype([("h", _i4), ("w", _i4), ("y0", _i4), ("x0", _i4), ("fh", _i4),
+                           ("fw", _i4), ("bands", _i4), ("kh", _i4), ("kw", _i4), ("n_comp", _i4),
+                           ("comp0", _i4), ("reserved", _i4), ("cube_off", _i8), ("stamp_off", _i8),
+                           ("part_off", _i8), ("out_off", _i8)], align=True)
+_SPECTRA_COMPONENT = np.dtype([("y0", _i4), ("x0", _i4), ("h", _i4), ("w", _i4),
+                               ("morph_off", _i8)], align=True)
+SPECTRA_TILE = 16
+MAX_COMPONENTS = 64       # of a blend
+MAX_PRESENT = 32          # components whose convolved model reaches one tile
+# |seen ratio - 0.1| <= NEAR_SEEN: the band is the loop's to decide
+NEAR_SEEN = 1e-6
+# the float64 plane of a source lives in the LDS of a CU: 160 KiB less 1 KiB of scratch
+MAX_SWEEP_PIXELS = (160 * 1024 - 1024) // 8
+MAX_STAMP = 63
+MAX_BOX_SIDE = 1 << 12
+WORKING_SET_BYTES = 1 << 30
+# |snr / min_snr - k| <= NEAR_INTEGER * k: the loop forms the S/N with float32 dots in no fixed
+# order, the device in float64; a count that close to the edge is the loop's to decide
+NEAR_INTEGER = 1e-4
+_OPTION_DEFAULTS = dict(thresh=1, max_components=1, min_components=1, min_snr=50, shifting=False,
+                        resizing=True, boxsize=None, fallback=True, silent=False, set_spectra=True)
+
+
+def _covers(slices, shape):
+    return all(isinstance(s, slice) and range(*s.indices(n)) == range(n)
+               for s, n in zip(slices, shape))
+
+
+def _box_side(boxsize):
+    """Side of the box ``trim_morphology`` cuts for ``boxsize``."""
+    return 2 * (int(boxsize) // 2) + 1
+
+
+def _refusal(frame, centers, observations, opts):
+    """Why the device path of ``init_blends`` does not take a blend, or None."""
+    from .frame import Frame
+
+    if not isinstance(frame, Frame):
+        return "frame is not a Frame"
+    observations = tuple(_as_tuple(observations))
+    if len(observations) != 1:
+        return "{} observations: the device path takes one".format(len(observations))
+    obs = observations[0]
+    renderer = getattr(obs, "renderer", None)
+    if getattr(obs, "model_frame", None) is not frame or renderer is None:
+        return "the observation is not matched to the frame"
+    if type(renderer) is ConvolutionRenderer:
+        if renderer._convolution_type != "fft" or renderer.parameters:
+            return "ConvolutionRenderer with a real-space convolution or a free psf_shift"
+    elif type(renderer) is not NullRenderer:
+        return "renderer {} is neither ConvolutionRenderer nor NullRenderer".format(
+            type(renderer).__name__)
+    if np.dtype(frame.dtype) != np.float32:
+        return "frame dtype {} is not float32".format(np.dtype(frame.dtype).name)
+    data, weights = obs.data, obs.weights
+    if (type(data) is not np.ndarray or type(weights) is not np.ndarray
+            or data.dtype != np.float32 or weights.dtype != np.float32):
+        return "data or weights are not plain float32 arrays"
+    shape = tuple(frame.shape)
+    if (tuple(data.shape) != shape or renderer.channel_map is not None
+            or not all(_covers(sl, shape) for sl in renderer.slices)):
+        return "the observation does not cover exactly the model frame"
+    if frame.psf is None:
+        return "no frame PSF"
+    if obs.psf is None:
+        return "no observation PSF"
+    if type(renderer) is ConvolutionRenderer:
+        stamp = np.shape(renderer.diff_kernel.image)
+        if len(stamp) != 3 or stamp[1] % 2 == 0 or stamp[2] % 2 == 0:
+            return "even difference-kernel stamp"
+        if max(stamp[1:]) > MAX_STAMP:
+            return "difference-kernel stamp beyond {0} x {0}".format(MAX_STAMP)
+    pshape = tuple(obs.psf.bbox.shape)
+    if len(pshape) != 3 or pshape[0] != shape[0] or max(pshape[1:]) > MAX_STAMP:
+        return "observation PSF is not one stamp per band of at most {0} x {0}".format(MAX_STAMP)
+    if shape[1] * shape[2] > MAX_SWEEP_PIXELS:
+        return "frame of {} pixels beyond the {} float64 pixels of the sweep kernel's LDS image".format(
+            shape[1] * shape[2], MAX_SWEEP_PIXELS)
+    if not 0 <= opts["max_components"] <= 2:
+        return "max_components outside 0 .. 2"
+    if not (np.isfinite(opts["thresh"]) and opts["thresh"] >= 0):
+        return "thresh is negative or not finite"
+    if opts["boxsize"] is not None and not 1 <= _box_side(opts["boxsize"]) <= MAX_BOX_SIDE:
+        return "boxsize beyond the crop kernel's limits"
+    if opts["fallback"] and not (np.isfinite(opts["min_snr"]) and opts["min_snr"] > 0):
+        return "min_snr is not a positive number"
+    centers = list(centers)
+    if not centers:
+        return "no centres"
+    for center in centers:
+        try:
+            pixel = np.round(frame.get_pixel(center)).astype("int")
+            same = np.array_equal(pixel, np.round(obs.get_pixel(center)).astype("int"))
+        except Exception:
+            return "a centre that is no coordinate"
+        if not same:
+            return "a centre on another pixel of the observation than of the frame"
+        if not (0 <= pixel[0] < shape[1] and 0 <= pixel[1] < shape[2]):
+            return "centre {} rounds to a pixel outside the frame".format(tuple(np.ravel(center)))
+    return None
+
+
+def _options(kwargs):
+    unknown = set(kwargs) - set(_OPTION_DEFAULTS)
+    if unknown:
+        raise TypeError("unexpected arguments: {}".format(sorted(unknown)))
+    return dict(_OPTION_DEFAULTS, **kwargs)
+
+
+def _group_key(frame, observations):
+    """Blends of one device group share dtype, bands and the shape of the PSF stamp."""
+    obs = tuple(_as_tuple(observations))[0]
+    return (np.dtype(frame.dtype).str, int(frame.C)) + tuple(int(n) for n in obs.psf.bbox.shape[1:])
+
+
+def plan_init_blends(frames, centers, observations, **options):
+    """``(groups, fallback)`` of ``init_blends``, without touching the GPU or the library: the
+    positions of the blends of every device group, keyed by ``(dtype, bands, PSF stamp height,
+    width)`` in order of first appearance and in list order inside a group, and ``(position,
+    reason)`` of the blends that go through ``init_all_sources``."""
+    opts = _options(options)
+    frames, centers, observations = list(frames), [list(c) for c in centers], list(observations)
+    if not len(frames) == len(centers) == len(observations):
+        raise ValueError("frames, centers and observations must have one entry per blend, got "
+                         "{}, {} and {}".format(len(frames), len(centers), len(observations)))
+    groups, fallback = {}, []
+    for i, (frame, cs, obs) in enumerate(zip(frames, centers, observations)):
+        reason = _refusal(frame, cs, obs, opts)
+        if reason is None:
+            groups.setdefault(_group_key(frame, obs), []).append(i)
+        else:
+            fallback.append((i, reason))
+    return groups, fallback
+
+
+def _blend_bytes(frame, n_sources, boxsize=None):
+    """Upper bound of the bytes of the device working set of one blend: data, variance and
+    weight cubes; per source the swept float64 plane and two float64 layers of its box, twice
+    (the cut-outs and the morphologies of the normal equations) -- the box of ``boxsize``, or,
+    where the trim decides, the largest standard box a frame of this size can ask for --; the
+    sums of the normal equations of two components per source, tile by tile."""
+    C, h, w = frame.shape
+    n = h * w
+    side = (_box_side(boxsize) if boxsize is not None
+            else _box_side(get_minimal_boxsize(2 * max(h, w))))
+    K = 2 * n_sources
+    tiles = -(-h // SPECTRA_TILE) * -(-w // SPECTRA_TILE)
+    return (3 * 4 * C * n + n_sources * 8 * (n + 4 * side * side)
+            + 8 * (tiles + 1) * C * (K * K + 3 * K))
+
+
+def _chunks(items, budget):
+    """Consecutive runs of ``(position, bytes)`` whose working sets stay within ``budget`` (a
+    blend beyond the budget is a chunk of its own)."""
+    out, run, used = [], [], 0
+    for pos, need in items:
+        if run and used + need > budget:
+            out.append(run)
+            run, used = [], 0
+        run.append(pos)
+        used += need
+    if run:
+        out.append(run)
+    return out
+
+
+def _offsets(sizes):
+    off = np.zeros(len(sizes) + 1, np.int64)
+    np.cumsum(np.asarray(sizes, np.int64), out=off[1:])
+    return off[:-1], int(off[-1])
+
+
+def _detect_cubes(obs):
+    """``observations[0]._detect`` as ``build_initialization_image`` makes and keeps it: the
+    data and the variance on the model frame."""
+    if not hasattr(obs, "_detect"):
+        frame = obs.model_frame
+        d = np.zeros(frame.shape, dtype=frame.dtype)
+        v = np.zeros(frame.shape, dtype=frame.dtype)
+        data_sl, model_sl = obs.renderer.slices
+        obs.renderer.map_channels(d)[model_sl] += obs.data[data_sl]
+        obs.renderer.map_channels(v)[model_sl] += obs.noise_rms[data_sl] ** 2
+        obs._detect = (np.array([d]), np.array([v]))
+    return obs._detect
+
+
+def component_count(snr_sums, opts):
+    """Components ``init_source`` starts a source with, from the ``(bands, 3)`` float64 sums of
+    the psf_snr kernel; None where the loop has to decide (a non-finite S/N, or ``snr /
+    min_snr`` within ``NEAR_INTEGER`` of a count it would change)."""
+    lo, hi = int(opts["min_components"]), int(opts["max_components"])
+    if not opts["fallback"]:
+        return hi
+    with np.errstate(all="ignore"):
+        ratio = float(np.sum(snr_sums[:, 0]) / np.sqrt(np.sum(snr_sums[:, 2])) / opts["min_snr"])
+    if not np.isfinite(ratio):
+        return None
+    for k in range(min(lo, hi), max(lo, hi) + 2):
+        if abs(ratio - k) <= NEAR_INTEGER * max(abs(k), 1):
+            return None
+    count = min(hi, max(lo, int(np.floor(ratio))))
+    return count if count >= 0 else None
+
+
+def trim_box(bounds, pixel, boxsize=None):
+    """``(origin, side)`` of the box ``trim_morphology`` cuts around ``pixel`` for a morphology
+    whose pixels ``> 0`` have the inclusive ``bounds`` (min row, max row, min col, max col;
+    max < min: none)."""
+    if boxsize is None:
+        b0, b1, l0, l1 = (int(v) for v in bounds)
+        cy, cx = int(pixel[0]), int(pixel[1])
+        size = 0
+        if b1 >= b0 and b0 <= cy <= b1 and l0 <= cx <= l1:
+            size = 2 * max(cy - b0, b1 + 1 - cy, cx - l0, l1 + 1 - cx)
+        boxsize = get_minimal_boxsize(size)
+    half = int(boxsize) // 2
+    return (int(pixel[0]) - half, int(pixel[1]) - half), 2 * half + 1
+
+
+class _Device:
+    """Uploads and launches of one chunk of ``init_blends`` (csrc/init_sources.hip)."""
+
+    def __init__(self, device):
+        import torch
+
+        from . import _lib
+
+        self.torch, self.lib, self.check = torch, _lib.load(), _lib.check
+        self.dev = torch.device("cuda", device)
+        self.keep = []
+        self.launches = []  # entries called, in order
+
+    def up(self, a):
+        return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+
+    def cat(self, parts, dtype):
+        parts = [np.ascontiguousarray(p, dtype).reshape(-1) for p in parts]
+        return self.up(np.concatenate(parts) if parts else np.zeros(1, dtype))
+
+    def empty(self, n, dtype):
+        return self.torch.empty(max(int(n), 1), dtype=getattr(self.torch, np.dtype(dtype).name),
+                                device=self.dev)
+
+    def call(self, step, table, *args):
+        """One smi_init_sources_<step>_f32 launch on the current stream: ``args`` are tensors
+        (passed as pointer) or integers, after (count, host table, device table)."""
+        import ctypes
+
+        if not len(table):
+            return
+        self.launches.append(step)
+        fn = getattr(self.lib, "smi_init_sources_%s_f32" % step)
+        argv = self.table(table)
+        for a in args:
+            if isinstance(a, np.ndarray):  # (a further table: count, host, device)
+                argv += self.table(a)
+            else:
+                argv.append(ctypes.c_void_p(a.data_ptr()) if hasattr(a, "data_ptr") else a)
+        stream = ctypes.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
+        self.check(fn(*argv, stream))
+
+    def table(self, table):
+        """(count, host pointer, device pointer) of a descriptor table."""
+        d_table = self.up(table.reshape(-1).view(np.uint8) if table.size else np.zeros(8, np.uint8))
+        self.keep += [table, d_table]  # (until the stream has been synchronised)
+        return [len(table), table.ctypes.data, d_table.data_ptr()]
+
+
+def pack_chunk(blends, opts):
+    """Host tables and buffers of the first two launches of a chunk.  ``blends``: a list of
+    ``(frame, centers, observation)``.  Returns a dict with the packed ``data``, ``var``
+    (float32), ``psfs`` and ``spectra`` (float64), the ``psf_snr`` and ``sweep`` tables, per source
+    its blend, pixel and pixel spectra, and ``loop``: the blends of the chunk (by position in it)
+    that a look at their values sends through ``init_all_sources``, with the reason -- non-finite
+    data, or a variance that is not positive."""
+    n_pix = [b[0].shape[1] * b[0].shape[2] for b in blends]
+    cube_off, n_cube = _offsets([b[0].C * n for b, n in zip(blends, n_pix)])
+    psfs = [np.asarray(b[2].psf.get_model(), np.float64) for b in blends]
+    psf_off, n_psf = _offsets([p.size for p in psfs])
+    data, var, loop = [], [], {}
+    src_blend, src_pixel, src_spec = [], [], []
+    for k, (frame, centers, obs) in enumerate(blends):
+        d, v = _detect_cubes(obs)
+        d, v = np.asarray(d[0]), np.ma.getdata(v[0])
+        data.append(d)
+        # (the coadd reads the variance as it stands, also under the mask of noise_rms, where
+        # get_psf_spectrum leaves the pixel out: those pixels go up negated)
+        var.append(np.where(obs.weights != 0, v, -v))
+        if not (np.isfinite(d).all() and np.isfinite(v).all() and (v > 0).all()
+                and psfs[k].shape[0] == frame.C):
+            loop[k] = "data or variance not finite, or a variance that is not positive"
+            continue
+        for center in centers:
+            src_blend.append(k)
+            src_pixel.append(tuple(int(p) for p in np.round(frame.get_pixel(center)).astype("int")))
+            src_spec.append(get_pixel_spectrum(center, (obs,), concat=False))
+    ns = len(src_blend)
+    spec_off, n_spec = _offsets([blends[k][0].C for k in src_blend])
+    snr_off, n_snr = _offsets([3 * blends[k][0].C for k in src_blend])
+    plane_off, n_plane = _offsets([n_pix[k] for k in src_blend])
+    snr_t, sweep_t = np.zeros(ns, _PSF_SNR_DESC), np.zeros(ns, _SWEEP_DESC)
+    spectra = np.zeros(n_spec, np.float64)
+    for s, k in enumerate(src_blend):
+        C, h, w = blends[k][0].shape
+        (cy, cx), (_, ph, pw) = src_pixel[s], psfs[k].shape
+        snr_t[s] = (h, w, cy, cx, ph, pw, C, 0, cube_off[k], psf_off[k], snr_off[s])
+        sweep_t[s] = (h, w, cy, cx, C, 0, cube_off[k], spec_off[s], plane_off[s], opts["thresh"])
+        # (the loop writes the float32 pixel spectrum into a float64 vector of the frame's bands)
+        spectra[spec_off[s]:spec_off[s] + C] = src_spec[s][0]
+    return dict(data=data, var=var, n_cube=n_cube, cube_off=cube_off, psfs=psfs, n_psf=n_psf, spectra=spectra,
+                psf_snr=snr_t, sweep=sweep_t, n_snr=n_snr, n_plane=n_plane, snr_off=snr_off,
+                plane_off=plane_off, src_blend=src_blend, src_pixel=src_pixel, src_spec=src_spec,
+                loop=loop)
+
+
+def _floor_image(cache, frame, center, side):
+    """The peak-normalised band-mean model PSF in a box of ``side``: what
+    ``SingleExtendedSource.init_morph`` takes the maximum with; once per frame and side."""
+    from .source import CompactExtendedSource
+
+    key = (id(frame), side)
+    if key not in cache:
+        cache[key] = CompactExtendedSource.init_morph(frame, center, boxsize=side)[0]
+    return cache[key]
+
+
+def _components(sources):
+    from .component import CombinedComponent
+
+    return [c for s in sources for c in (s.children if isinstance(s, CombinedComponent) else (s,))]
+
+
+def _identical_pair(frame_shape, morphs, boxes):
+    """Does ``set_spectra_to_match`` meet two components with identical models?  Its own cheap
+    screen (the sum and the sum of absolute values within the ``np.allclose`` bound, a little
+    wider here for the other order of the sums), then ``np.allclose`` of the two planes."""
+    C, H, W = frame_shape
+    placed, sums = [], []
+    for m, (y0, x0) in zip(morphs, boxes):
+        h, w = m.shape
+        ys, ye, xs, xe = max(y0, 0), min(y0 + h, H), max(x0, 0), min(x0 + w, W)
+        cut = m[ys - y0:ye - y0, xs - x0:xe - x0]
+        placed.append((ys, xs, cut))
+        sums.append((C * float(np.sum(cut)), C * float(np.sum(np.abs(cut)))))
+    bound = 1e-8 * C * H * W
+    for k in range(len(morphs)):
+        for prev in range(k):
+            gap = bound + 1e-5 * sums[prev][1]
+            if abs(sums[k][0] - sums[prev][0]) > 2 * gap + 1e-8 * (abs(sums[k][0]) + abs(sums[prev][0])):
+                continue
+            planes = np.zeros((2, H, W))
+            for plane, (ys, xs, cut) in zip(planes, (placed[k], placed[prev])):
+                plane[ys:ys + cut.shape[0], xs:xs + cut.shape[1]] = cut
+            if np.allclose(planes[0], planes[1]):
+                return True
+    return False
+
+
+def _most_present(region, boxes, shapes, kh, kw):
+    """The largest number of components whose box, grown by the stamp's half, meets one tile of
+    ``region`` = (y0, x0, fh, fw)."""
+    y0, x0, fh, fw = region
+    most = 0
+    for ty in range(0, fh, SPECTRA_TILE):
+        for tx in range(0, fw, SPECTRA_TILE):
+            th, tw = min(SPECTRA_TILE, fh - ty), min(SPECTRA_TILE, fw - tx)
+            n = 0
+            for (by, bx), (h, w) in zip(boxes, shapes):
+                cy, cx = by - y0, bx - x0
+                n += (cy - kh // 2 < ty + th and cy + h + kh // 2 > ty
+                      and cx - kw // 2 < tx + tw and cx + w + kw // 2 > tx)
+            most = max(most, n)
+    return most
+
+
+def pack_spectra(items, cube_off):
+    """Host tables and buffers of the two spectra launches.  ``items``: ``(k, frame, observation,
+    sources)`` of the blends of a chunk that have their sources, ``k`` the position in the chunk;
+    ``cube_off[k]``: where the blend's data cube lies.  Sets every free spectrum to 1, as
+    ``set_spectra_to_match`` does first.  Returns a dict with the ``blends``, ``components`` and
+    ``work`` tables, the packed float64 ``morphs`` and ``stamps``, ``n_part`` and ``n_out``,
+    ``taken``: per packed blend ``(k, parameters, bands, components, out_off)``, and ``loop``:
+    the reason per blend the loop has to take."""
+    from .component import FactorizedComponent
+
+    rows, comp_rows, work, morph_parts, stamp_parts, taken, loop = [], [], [], [], [], [], {}
+    n_morph = n_stamp = n_part = n_out = 0
+    for k, frame, obs, sources in items:
+        C, H, W = frame.shape
+        comps = _components(sources)
+        parameters, morphs, boxes = [], [], []
+        for comp in comps:
+            p = comp.get_parameter("spectrum")
+            if (not isinstance(comp, FactorizedComponent) or p is None or p.fixed
+                    or p.shape != (C,)):
+                loop[k] = "a component without a free spectrum of the frame's bands"
+                break
+            p[:] = 1
+            m = np.asarray(comp.get_models_of_children()[1], np.float64)
+            if m.ndim != 2 or not m.size:
+                loop[k] = "a morphology that is no image"
+                break
+            parameters.append(p)
+            morphs.append(m)
+            boxes.append(tuple(int(o) for o in comp.bbox.origin[-2:]))
+        if k in loop:
+            continue
+        K = len(morphs)
+        if not 1 <= K <= MAX_COMPONENTS:
+            loop[k] = "{} components: the device takes 1 .. {}".format(K, MAX_COMPONENTS)
+            continue
+        if type(obs.renderer) is ConvolutionRenderer:
+            stamps = np.asarray(obs.renderer.kernel_image(), np.float64)
+        else:
+            stamps = np.ones((C, 1, 1))
+        if stamps.ndim != 3 or stamps.shape[0] != C:
+            loop[k] = "difference kernel without one stamp per band"
+            continue
+        kh, kw = stamps.shape[1:]
+        # the region: what the convolved models reach inside the frame
+        lo_y = lo_x = 1 << 30
+        hi_y = hi_x = -(1 << 30)
+        for m, (y0, x0) in zip(morphs, boxes):
+            ys, ye, xs, xe = max(y0, 0), min(y0 + m.shape[0], H), max(x0, 0), min(x0 + m.shape[1], W)
+            if ys < ye and xs < xe:
+                lo_y, hi_y = min(lo_y, ys - kh // 2), max(hi_y, ye + kh // 2)
+                lo_x, hi_x = min(lo_x, xs - kw // 2), max(hi_x, xe + kw // 2)
+        lo_y, hi_y, lo_x, hi_x = max(lo_y, 0), min(hi_y, H), max(lo_x, 0), min(hi_x, W)
+        if lo_y >= hi_y or lo_x >= hi_x:
+            loop[k] = "no component inside the frame"
+            continue
+        region = (lo_y, lo_x, hi_y - lo_y, hi_x - lo_x)
+        if K > MAX_PRESENT and _most_present(region, boxes, [m.shape for m in morphs], kh,
+                                             kw) > MAX_PRESENT:
+            loop[k] = "more than {} components reach one tile".format(MAX_PRESENT)
+            continue
+        if _identical_pair(frame.shape, morphs, boxes):
+            loop[k] = "two components with identical models"
+            continue
+        tiles = -(-region[2] // SPECTRA_TILE) * -(-region[3] // SPECTRA_TILE)
+        E = K * K + 3 * K
+        b = len(rows)
+        rows.append((H, W) + region + (C, kh, kw, K, len(comp_rows), 0, cube_off[k], n_stamp,
+                                       n_part, n_out))
+        for m, (y0, x0) in zip(morphs, boxes):
+            comp_rows.append((y0, x0, m.shape[0], m.shape[1], n_morph))
+            morph_parts.append(m)
+            n_morph += m.size
+        work += [(b, t) for t in range(tiles)]
+        stamp_parts.append(stamps)
+        taken.append((k, parameters, C, K, n_out))
+        n_stamp += stamps.size
+        n_part += tiles * C * E
+        n_out += C * E
+    return dict(blends=np.array(rows, _SPECTRA_BLEND) if rows else np.zeros(0, _SPECTRA_BLEND),
+                components=(np.array(comp_rows, _SPECTRA_COMPONENT) if comp_rows
+                            else np.zeros(0, _SPECTRA_COMPONENT)),
+                work=np.array(work, np.int32).reshape(-1, 2), morphs=morph_parts, n_morph=n_morph,
+                stamps=stamp_parts, n_stamp=n_stamp, n_part=n_part, n_out=n_out, taken=taken,
+                loop=loop)
+
+
+def seen_components(sum_mw, sum_m, mean_w):
+    """The components ``set_spectra_to_match`` solves a band for: those whose ``seen`` ratio
+    ``sum m w / sum m / mean(w)`` exceeds 0.1; None where the loop has to decide (a ratio that
+    is not finite, or within ``NEAR_SEEN`` of 0.1)."""
+    with np.errstate(all="ignore"):
+        ratio = np.asarray(sum_mw, np.float64) / np.asarray(sum_m, np.float64) / mean_w
+    if not np.isfinite(ratio).all() or (np.abs(ratio - 0.1) <= NEAR_SEEN).any():
+        return None
+    return np.flatnonzero(ratio > 0.1)
+
+
+def solve_spectra(sums, K, weights):
+    """``(K, bands)`` spectra from the ``(bands, K K + 3 K)`` sums of the device -- G, r, sum m w
+    and sum m per band -- and the observation's ``weights``, as ``set_spectra_to_match`` ends; or
+    the reason (a string) why the loop has to take the blend."""
+    C = sums.shape[0]
+    spectra = np.zeros((K, C))
+    for c in range(C):
+        G, rest = sums[c, :K * K].reshape(K, K), sums[c, K * K:].reshape(3, K)
+        mean_w = np.mean(weights[c].reshape(-1).astype(np.float64))
+        seen = seen_components(rest[1], rest[2], mean_w)
+        if seen is None:
+            return "a band whose seen ratio is not finite or within {} of 0.1".format(NEAR_SEEN)
+        try:
+            spectra[seen, c] = np.linalg.inv(G[np.ix_(seen, seen)]) @ rest[0][seen]
+        except np.linalg.LinAlgError:
+            return "a singular normal matrix"
+    if not np.isfinite(spectra).all():
+        return "a spectrum that is not finite"
+    return spectra
+
+
+def _run_chunk(blends, opts, device, report):
+    """``init_all_sources`` of the blends of one chunk, ``(frame, centers, observation)`` each:
+    the list of their ``(sources, skipped)``, or the reason (a string) why the loop has to take
+    the blend."""
+    import time
+
+    t0 = time.perf_counter()
+    pk = pack_chunk(blends, opts)
+    src_blend, src_pixel = pk["src_blend"], pk["src_pixel"]
+    ns = len(src_blend)
+    loop = dict(pk["loop"])
+    dv = _Device(device)
+    torch = dv.torch
+    t1 = time.perf_counter()
+    with torch.cuda.device(dv.dev):
+        d_data, d_var = dv.cat(pk["data"], np.float32), dv.cat(pk["var"], np.float32)
+        d_psfs, d_spec = dv.cat(pk["psfs"], np.float64), dv.up(pk["spectra"] if ns else np.zeros(1))
+        d_snr = dv.empty(pk["n_snr"], np.float64)
+        d_planes = dv.empty(pk["n_plane"], np.float64)
+        d_bounds, d_peaks = dv.empty(4 * ns, np.int32), dv.empty(ns, np.float64)
+        if opts["fallback"]:
+            dv.call("psf_snr", pk["psf_snr"], d_data, d_var, pk["n_cube"], d_psfs, pk["n_psf"],
+                    d_snr, pk["n_snr"])
+        dv.call("sweep", pk["sweep"], d_data, d_var, pk["n_cube"], d_spec, len(pk["spectra"]),
+                d_planes, pk["n_plane"], d_bounds, d_peaks, ns)
+        snr = d_snr.cpu().numpy()
+        bounds = d_bounds.cpu().numpy()[:4 * ns].reshape(ns, 4)
+        t2 = time.perf_counter()
+        # ---- between the launches: component count and box of every source
+        counts, boxes, floors = [], [], {}
+        for s, k in enumerate(src_blend):
+            C = blends[k][0].C
+            count = component_count(snr[pk["snr_off"][s]:pk["snr_off"][s] + 3 * C].reshape(C, 3),
+                                    opts)
+            if count is None:
+                loop.setdefault(k, "a source whose snr / min_snr is not finite or within {} of a "
+                                   "component count".format(NEAR_INTEGER))
+            counts.append(count)
+            boxes.append(trim_box(bounds[s], src_pixel[s], opts["boxsize"]))
+        cropped = [s for s in range(ns) if src_blend[s] not in loop and counts[s] > 0]
+        sizes = [counts[s] * boxes[s][1] ** 2 for s in cropped]
+        out_off, n_out = _offsets(sizes)
+        floor_parts, floor_at, n_floor = [], {}, 0
+        crop_t = np.zeros(len(cropped), _CROP_DESC)
+        for j, s in enumerate(cropped):
+            k = src_blend[s]
+            frame, centers, _ = blends[k]
+            (y0, x0), side = boxes[s]
+            key = (id(frame), side)
+            if key not in floor_at:
+                floor_at[key] = n_floor
+                floor_parts.append(_floor_image(floors, frame, centers[0], side))
+                n_floor += side * side
+            crop_t[j] = (frame.shape[1], frame.shape[2], y0, x0, side, counts[s],
+                         pk["plane_off"][s], floor_at[key], out_off[j], 25.0)
+        d_floors = dv.cat(floor_parts, np.float64)
+        d_out, d_flags = dv.empty(n_out, np.float64), dv.empty(len(cropped), np.int32)
+        dv.call("crop", crop_t, d_planes, pk["n_plane"], d_floors, n_floor, d_out, n_out, d_flags,
+                len(cropped))
+        morphs = d_out.cpu().numpy()
+        flags = d_flags.cpu().numpy()[:len(cropped)]
+    t3 = time.perf_counter()
+    at, empty = {}, set()
+    for j, s in enumerate(cropped):
+        if flags[j] & 1:
+            loop.setdefault(src_blend[s], "a morphology that is not finite")
+        if flags[j] & 2:  # (the cut-out held no pixel > 0: what the loop warns about)
+            empty.add(s)
+        at[s] = int(out_off[j])
+    # ---- the source objects
+    results = [None if k in loop else ([], []) for k in range(len(blends))]
+    noise = {}
+    for s, k in enumerate(src_blend):
+        if k in loop:
+            continue
+        frame, centers, obs = blends[k]
+        center = centers[len(results[k][0])]
+        if k not in noise:
+            from .source import _noise_rms
+            noise[k] = _noise_rms((obs,))
+        if s in empty:
+            logger.warning(f"No flux in morphology model for source at {center}")
+        try:
+            (y0, x0), side = boxes[s]
+            layers = [morphs[at[s] + i * side * side:at[s] + (i + 1) * side * side]
+                      .reshape(side, side).copy() for i in range(counts[s])]
+            source = _assemble(frame, center, obs, counts[s], pk["src_spec"][s], layers,
+                               Box((side, side), origin=(y0, x0)), noise[k], opts)
+            source.check_parameters()
+        except Exception as exc:  # (whatever it is, the loop meets and reports it)
+            loop[k] = "{} while assembling a source".format(type(exc).__name__)
+            results[k] = None
+            continue
+        results[k][0].append(source)
+    t4 = time.perf_counter()
+    # ---- the spectra: normal equations on the device, K x K solves on the host
+    if opts["set_spectra"]:
+        items = [(k, blends[k][0], blends[k][2], r[0]) for k, r in enumerate(results)
+                 if r is not None and r[0]]
+        sp = pack_spectra(items, pk["cube_off"])
+        for k, why in sp["loop"].items():
+            loop[k], results[k] = why, None
+        if sp["taken"]:
+            with torch.cuda.device(dv.dev):
+                d_weights = dv.cat([b[2].weights for b in blends], np.float32)
+                d_morphs, d_stamps = dv.cat(sp["morphs"], np.float64), dv.cat(sp["stamps"], np.float64)
+                d_part, d_sums = dv.empty(sp["n_part"], np.float64), dv.empty(sp["n_out"], np.float64)
+                dv.call("spectra_tiles", sp["blends"], sp["components"], sp["work"], d_data,
+                        d_weights, pk["n_cube"], d_stamps, sp["n_stamp"], d_morphs, sp["n_morph"],
+                        d_part, sp["n_part"], sp["n_out"])
+                dv.call("spectra_reduce", sp["blends"], d_part, sp["n_part"], d_sums, sp["n_out"])
+                sums = d_sums.cpu().numpy()
+            for k, parameters, C, K, off in sp["taken"]:
+                E = K * K + 3 * K
+                spectra = solve_spectra(sums[off:off + C * E].reshape(C, E), K, blends[k][2].weights)
+                if isinstance(spectra, str):
+                    loop[k], results[k] = spectra, None
+                    continue
+                for p, row in zip(parameters, spectra):
+                    p[:] = row
+                for p in parameters:
+                    if p.constraint is not None:
+                        p[:] = p.constraint(p, 0)
+    t5 = time.perf_counter()
+    if report is not None:
+        report["launches"] = list(dv.launches)  # (of the last chunk)
+        times = report.setdefault("times", {})
+        for name, dt in (("pack", t1 - t0), ("device", t2 - t1), ("crop", t3 - t2),
+                         ("assemble", t4 - t3), ("spectra", t5 - t4)):
+            times[name] = times.get(name, 0.0) + dt
+    return [loop[k] if r is None else r for k, r in enumerate(results)]
+
+
+def _assemble(frame, center, obs, count, per_obs, layers, bbox, noise, opts):
+    """The source ``ExtendedSource(..., K=count)`` builds at ``center``, from the morphology
+    layers of the device: the same classes, parameters, steps and constraint chains, through the
+    classes' own parts."""
+    from .component import CombinedComponent, FactorizedComponent
+    from .source import (CompactExtendedSource, MultiExtendedSource, SingleExtendedSource,
+                         _fitted_morphology)
+    from .spectrum import TabulatedSpectrum
+
+    shifting, resizing = opts["shifting"], opts["resizing"]
+    if count == 0:
+        return CompactExtendedSource(frame, center, (obs,), shifting=shifting, resizing=resizing,
+                                     boxsize=opts["boxsize"])
+    amplitudes = np.concatenate(per_obs).reshape(-1)
+    if count == 1:
+        source = SingleExtendedSource.__new__(SingleExtendedSource)
+        spectrum = TabulatedSpectrum(frame, amplitudes, min_step=noise.copy())
+        morphology = _fitted_morphology(frame, center, layers[0], bbox, shifting, resizing)
+        FactorizedComponent.__init__(source, frame, spectrum, morphology)
+        source.center = morphology.center
+        return source
+    source = MultiExtendedSource.__new__(MultiExtendedSource)
+    # (what the single source's spectrum parameter holds)
+    amplitudes = TabulatedSpectrum(frame, amplitudes, min_step=noise.copy()).get_parameter(0)._data
+    min_step = noise / 10
+    components = []
+    for layer in layers:
+        morphology = _fitted_morphology(frame, center, layer, bbox.copy(), shifting, resizing)
+        components.append(FactorizedComponent(
+            frame, TabulatedSpectrum(frame, amplitudes.copy(), min_step=min_step), morphology))
+        source.center = morphology.center
+    CombinedComponent.__init__(source, components)
+    return source
+
+
+def init_blends(frames, centers, observations, device=None, _working_set_bytes=None,
+                _report=None, **options):
+    """``init_all_sources`` for a catalogue: ``results[i]`` is what ``init_all_sources(frames[i],
+    centers[i], observations[i], **options)`` returns, ``(sources, skipped)`` -- the same source
+    classes, boxes, centres, steps, constraint chains and flags, the morphology images and the
+    pixel spectra bit for bit -- with at most five launches of csrc/init_sources.hip per chunk
+    of blends, whatever their frames, stamps and source counts: the point-source S/N that decides
+    the component count, the spectrum-weighted coadd with symmetry, monotonic sweep and trim of
+    every source, the normalised cut-outs with their bulge / disk split and, for
+    ``set_spectra=True``, the float64 weighted normal equations of ``set_spectra_to_match`` tile
+    by tile and their sum.  The host solves them (K x K per blend and band); these spectra agree
+    with the loop's within the rounding of the two ways to form the sums (catalogue initialisation), and do
+    not depend on the list a blend is in.
+
+    ``observations[i]``: one ``Observation`` matched to ``frames[i]``, or a sequence holding one.
+    The options are those of ``init_all_sources``.  Blends the device path does not take go
+    through ``init_all_sources`` after the device groups, in list order; ``plan_init_blends``
+    names them and says why.  So does a blend whose values leave a decision to the loop:
+    non-finite data, a non-finite morphology or spectrum, a source whose ``snr / min_snr`` lies
+    within 1e-4 (relative) of a component count, a band whose ``seen`` ratio lies within 1e-6 of
+    0.1, two components with identical models, a singular normal matrix, more than 64
+    components or more than 32 on one 16 x 16 tile.  ``device``: GPU index (default 0).
+    ``_report``: a dict that receives ``fallback`` -- ``(position, reason)`` of the blends the
+    loop took --, ``launches`` of the last chunk and the seconds by step in ``times``."""
+    import time
+
+    opts = _options(options)
+    frames, centers, observations = list(frames), [list(c) for c in centers], list(observations)
+    groups, fallback = plan_init_blends(frames, centers, observations, **options)
+    budget = WORKING_SET_BYTES if _working_set_bytes is None else _working_set_bytes
+    device = 0 if device is None else int(device)
+    results = [None] * len(frames)
+    for idx in groups.values():
+        items = [(i, _blend_bytes(frames[i], len(centers[i]), opts["boxsize"])) for i in idx]
+        for chunk in _chunks(items, budget):
+            blends = [(frames[i], centers[i], tuple(_as_tuple(observations[i]))[0]) for i in chunk]
+            for i, result in zip(chunk, _run_chunk(blends, opts, device, _report)):
+                if isinstance(result, str):
+                    fallback.append((i, "at run time: " + result))
+                else:
+                    results[i] = result
+    t0 = time.perf_counter()
+    for i, result in enumerate(results):
+        if result is None:
+            results[i] = init_all_sources(frames[i], centers[i], observations[i], **opts)
+    if _report is not None:
+        _report.setdefault("times", {})["loop"] = time.perf_counter() - t0
+        _report["fallback"] = sorted(fallback)
+    return results
