@@ -217,6 +217,59 @@ int smi_lite_spectra_f64(int32_t device, int32_t C, int32_t kh, int32_t kw, int3
                          int64_t n_image, const double *stamps, int64_t n_stamp,
                          const double *morphs, int64_t n_morph, double *out, int64_t n_out);
 
+/* measure_blends: the sums a catalogue row of scarlet.measure is made of, for the sources of
+ * many blends that share the number of model bands C and the (kh, kw) stamp shape; three
+ * launches.  Host buffers in, host buffers out; coordinates relative to the corner of the
+ * source's frame; offsets and sizes count elements.
+ *
+ * A model pixel of band c is the sum over the source's components, in table order and in float64,
+ * of the rounded products seds[sed_off + c] * morphs[morph_off + y w + x], zero outside a
+ * component's box.
+ *
+ *   records[(source * C + c) * SMI_MEASURE_SOURCES_RECORD + k] over the source's box, y and x
+ *   integers counted from its corner:
+ *     k = 0 sum m    2 sum x m      4 sum y x m    6 the largest m
+ *         1 sum y m  3 sum y^2 m    5 sum x^2 m    7 y * w + x of its first pixel (-1: none)
+ *   rendered[(row + b) * 3 + q], row = the bands of all sources before this one, b the source's
+ *   band (source.band0 + b of the band table): with R the model of bands[..].channel, what of it
+ *   lies in the frame, convolved ("same", zero boundary, float64 over the float32 taps
+ *   stamps[stamp_off .. + kh kw]) and W = weights[weight_off .. + fh fw], over the frame's
+ *   pixels the source's box grown by the stamp's half reaches:
+ *     q = 0 sum R    1 sum R^2    2 sum R^2 (1 / W)
+ *
+ * Limits: odd stamp sides <= 63, box and morphology sides <= 16384, a component's box inside its
+ * source's.  Every table is validated before anything is launched: a bad one returns
+ * SMI_ERR_INVALID and leaves the outputs alone.  The order of every sum depends on the source's
+ * box, its frame and the stamp shape alone: a source's sums have the same bits wherever it
+ * stands in the tables. */
+typedef struct smi_measure_source {
+    int32_t y0, x0, h, w;   /* box of the source's model, may leave the frame */
+    int32_t fh, fw;         /* frame */
+    int32_t comp0, n_comp;  /* its components, in the order they are added */
+    int32_t band0, n_band;  /* the observed bands of its blend in the band table */
+} smi_measure_source;
+typedef struct smi_measure_component {
+    int32_t y0, x0, h, w;   /* box of the morphology, inside the source's */
+    int64_t sed_off, morph_off;
+} smi_measure_component;
+typedef struct smi_measure_band {
+    int32_t channel, reserved;  /* model band this observed band renders */
+    int64_t stamp_off, weight_off;
+} smi_measure_band;
+#define SMI_MEASURE_SOURCES_RECORD 8
+int smi_measure_sources_f32(int32_t device, int32_t C, int32_t kh, int32_t kw, int32_t n_sources,
+                            const smi_measure_source *sources, int32_t n_components,
+                            const smi_measure_component *components, int32_t n_bands,
+                            const smi_measure_band *bands, const double *seds, int64_t n_sed,
+                            const double *morphs, int64_t n_morph, const float *stamps,
+                            int64_t n_stamp, const float *weights, int64_t n_weight,
+                            double *records, int64_t n_record, double *rendered,
+                            int64_t n_rendered);
+/* ms[0 .. 2]: milliseconds the model, render and reduce launches of the calling thread's last
+ * smi_measure_sources_f32 call took on the device (events around them), for
+ * tools/measure_blends_time.py */
+int smi_measure_sources_last_launch_ms(double *ms);
+
 /* lite.init_blends: the wavelet initialisation of scarlet.lite (reference
  * lite/initialization.py:422-605) for a catalogue of blends.  Six steps, each one launch
  * over a table of tasks; the caller owns every buffer (`d_*`: device memory) and orders the

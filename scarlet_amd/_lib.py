@@ -79,6 +79,15 @@ def _LITE_SPECTRA(fp):
                ctypes.c_int64])
 
 
+def _MEASURE_SOURCES():
+    """smi_measure_sources_f32: device, C, kh, kw, then (count, table) of the source, component
+    and band descriptors (numpy records of measure.py, passed as void *), then the (buffer, size)
+    pairs seds, morphs (float64), stamps, weights (float32), records, rendered (float64)."""
+    return ([ctypes.c_int32] * 4 + [ctypes.c_int32, ctypes.c_void_p] * 3
+            + [c_f64p, ctypes.c_int64] * 2 + [c_f32p, ctypes.c_int64] * 2
+            + [c_f64p, ctypes.c_int64] * 2)
+
+
 def _LITE_INIT():
     """smi_lite_init_*: every entry takes (count, host table, device table), then device
     buffers as void * with their sizes in elements, then the stream (lite/initialization.py)."""
@@ -197,6 +206,8 @@ SYMBOLS = {
     "smi_lite_measure_f32": (ctypes.c_int, _REWEIGHT(c_f32p) + [c_f64p, ctypes.c_int64]),
     "smi_lite_measure_f64": (ctypes.c_int, _REWEIGHT(c_f64p) + [c_f64p, ctypes.c_int64]),
     "smi_lite_measure_last_launch_ms": (ctypes.c_int, [c_f64p]),
+    "smi_measure_sources_f32": (ctypes.c_int, _MEASURE_SOURCES()),
+    "smi_measure_sources_last_launch_ms": (ctypes.c_int, [c_f64p]),
     "smi_lite_spectra_f32": (ctypes.c_int, _LITE_SPECTRA(c_f32p)),
     "smi_lite_spectra_f64": (ctypes.c_int, _LITE_SPECTRA(c_f64p)),
     "smi_get_valid_monotonic_pixels_f32": (

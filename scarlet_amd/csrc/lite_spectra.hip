@@ -30,11 +30,16 @@
 #include <algorithm>
 
 #include "common.h"
+#include "window_device.h"
 
 namespace smi {
 namespace {
 
-constexpr int kTile = 16;
+using window::kTile;  // the tile, its window and the tap loop: window_device.h
+using window::tap_range;
+using window::tap_sum;
+using window::uniform;
+using window::window_pitch;
 constexpr int kThreads = kTile * kTile;
 constexpr int kSegs = 8, kSegLen = kThreads / kSegs;  // 8 x 32 pixels
 constexpr int kPitch = kThreads + kSegs;              // doubles of a column in LDS
@@ -58,10 +63,6 @@ __host__ __device__ inline Tile tile_of(const smi_lite_spectra_blend &bl, int ti
     return t;
 }
 
-// Row pitch in doubles of the window a morphology is staged in, (16 + kh - 1) x (16 + kw - 1):
-// 16 (mod 32), so that the two rows of 16 pixels a half-wavefront reads fall on different banks.
-__host__ __device__ inline int window_pitch(int kw) { return (kw - 1 + 31) / 32 * 32 + kTile; }
-
 inline int32_t tiles_of(const smi_lite_spectra_blend &bl) {
     return ((bl.fh + kTile - 1) / kTile) * ((bl.fw + kTile - 1) / kTile);
 }
@@ -75,9 +76,6 @@ __host__ __device__ inline bool present_on(const smi_lite_spectra_blend &bl,
     return cy - kh / 2 < t.y0 + t.h && cy + d.h + kh / 2 > t.y0 && cx - kw / 2 < t.x0 + t.w &&
            cx + d.w + kw / 2 > t.x0;
 }
-
-// a value every lane of the wavefront holds, as one the compiler keeps in a scalar register
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 template <typename T>
 struct SpectraArgs {
@@ -148,17 +146,10 @@ __global__ __launch_bounds__(kThreads) void spectra_tile_kernel(const SpectraArg
             // window[i + kh - 1 - ky][j + kw - 1 - kx]; the taps under which no pixel of the
             // tile meets the morphology's rows [r0, r0 + h) and columns add exact zeros (finite
             // stamps): skipped
-            const int ky_lo = uniform(max(0, kh - (r0 + d.h)));
-            const int ky_hi = uniform(min(kh - 1, kh - 1 - r0 + kTile - 1));
-            const int kx_lo = uniform(max(0, kw - (c0 + d.w)));
-            const int kx_hi = uniform(min(kw - 1, kw - 1 - c0 + kTile - 1));
-            double acc = 0;
-            for (int ky = ky_lo; ky <= ky_hi; ++ky) {
-                const double *row = win + (i + kh - 1 - ky) * wp + j + kw - 1;
-                const double *k = kern + ky * kw;
-#pragma unroll 4
-                for (int kx = kx_lo; kx <= kx_hi; ++kx) acc += k[kx] * row[-kx];
-            }
+            int ky_lo, ky_hi, kx_lo, kx_hi;
+            tap_range(kh, r0, d.h, &ky_lo, &ky_hi);
+            tap_range(kw, c0, d.w, &kx_lo, &kx_hi);
+            const double acc = tap_sum(win, wp, i, j, kh, kw, kern, ky_lo, ky_hi, kx_lo, kx_hi);
             col[s * kPitch + at] = inside ? acc : 0.0;
             __syncthreads();  // (the window is staged again)
         }

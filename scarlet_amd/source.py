@@ -12,7 +12,7 @@ import numpy as np
 from . import initialization as init
 from . import operator
 from .bbox import Box, overlapped_slices
-from .component import CombinedComponent, FactorizedComponent
+from .component import CombinedComponent, Component, FactorizedComponent
 from .constraint import CenterOnConstraint, PositivityConstraint
 from .morphology import (ExtendedSourceMorphology, GaussianMorphology, ImageMorphology,
                          PointSourceMorphology, SpergelMorphology, StarletMorphology)
@@ -48,6 +48,17 @@ def _fitted_morphology(frame, sky_coord, image, bbox, shifting, resizing):
     return ExtendedSourceMorphology(
         frame, frame.get_pixel(sky_coord), image, bbox=bbox, monotonic="angle",
         symmetric=False, min_grad=0, shifting=shifting, resizing=resizing)
+
+
+class NullSource(Component):
+    """A source without components (source.py:24-58): its model is zero over the whole frame.
+    It keeps a place in a list of sources; it has no parameters and is not fitted."""
+
+    def __init__(self, model_frame):
+        super().__init__(model_frame)
+
+    def get_model(self, *parameters, frame=None):
+        return self._in_frame(np.zeros(self.frame.shape), frame)
 
 
 class RandomSource(FactorizedComponent):
