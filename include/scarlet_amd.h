@@ -1043,10 +1043,30 @@ int smi_batch_conv_path_used(smi_batch *b, int32_t *path);
  * kernel clips components to the blend's own extent instead of H x W: nothing is rendered
  * beyond it, and no gradient flows back from beyond it (lite/models.py:206-216).  The caller
  * pads data and weights beyond the extent (weights 0, data finite).  h = w = NULL gives every
- * blend the full frame again.  Not combined with shifting components, point sources,
- * smi_batch_set_kernel_shift, smi_batch_attach_lowres, smi_batch_add_observation or
- * smi_batch_resize_test: those calls, and this one after them, return an error. */
+ * blend the full frame again.  The normalisation term of the loss (Observation.log_norm) is
+ * formed anew by the call, over every blend's own frame and in the order of a batch of that
+ * frame shape, and keeps what smi_batch_add_loss_constant has added; on the fused convolution
+ * path a blend's loss then has the bits it has in an unpadded batch (the rocFFT path sums
+ * w (m - d)^2 in blocks of the padded plane).
+ *
+ * smi_batch_set_frame_extents is the call of the lite loop and keeps the contract it had:
+ * image components only -- not combined with shifting components, point sources, starlet or
+ * profile components, smi_batch_set_kernel_shift, smi_batch_attach_lowres,
+ * smi_batch_add_observation or smi_batch_resize_test: those calls, and this one after them,
+ * return an error.
+ *
+ * smi_batch_set_frame_extents_all is the call of the main loop (fit_blends): the same extents
+ * for every component kind of the step loop -- image components, point sources, shifting
+ * components (the Fourier shift acts on the box, its gradient is gathered from the extent),
+ * starlet and profile components -- set before or after this call.  A box may reach beyond its
+ * blend's extent into the padding, as it may overhang H x W: those pixels are parameters of
+ * the component that see no data and no gradient.  smi_batch_resize_test,
+ * smi_batch_update_components (keep codes 2 / 3 included), smi_batch_get_component_states and
+ * the per-blend counters (smi_batch_set_round and the calls it stands for) read a component's
+ * own box and state only and work as without extents.  Still not combined with
+ * smi_batch_set_kernel_shift, smi_batch_attach_lowres or smi_batch_add_observation. */
 int smi_batch_set_frame_extents(smi_batch *b, const int32_t *h, const int32_t *w);
+int smi_batch_set_frame_extents_all(smi_batch *b, const int32_t *h, const int32_t *w);
 
 /* The FFT shape smi_batch_create picks for a desc with fft_h = fft_w = 0 and these sizes
  * (host only, no GPU): the fused kernel's shape (fused_conv_choose) or, on the rocFFT path, the

@@ -54,7 +54,7 @@ from .component import (  # noqa: F401
     CombinedComponent,
 )
 from .blend import Blend  # noqa: F401
-from .fitting import fit_blends  # noqa: F401
+from .fitting import fit_blends, plan_fit_blends  # noqa: F401
 from .initialization import init_blends, plan_init_blends  # noqa: F401
 from .measure import measure_blends, plan_measure_blends  # noqa: F401
 from .source import (  # noqa: F401

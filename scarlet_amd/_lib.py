@@ -350,6 +350,7 @@ SYMBOLS = {
     "smi_batch_set_states": (ctypes.c_int, [ctypes.c_void_p, c_i32p]),
     "smi_batch_set_iteration_base": (ctypes.c_int, [ctypes.c_void_p, c_i32p]),
     "smi_batch_set_frame_extents": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p]),
+    "smi_batch_set_frame_extents_all": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p]),
     "smi_fft_shape_for": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                          ctypes.c_int32, ctypes.c_int32, c_i32p, c_i32p]),
     "smi_batch_set_pause_at": (ctypes.c_int, [ctypes.c_void_p, c_i32p]),

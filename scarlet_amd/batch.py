@@ -154,6 +154,22 @@ def fft_shape_for(H, W, kernel_shape, conv_path="auto"):
     return fy.value, fx.value
 
 
+def _conv_plan(h, w, kernel_shape):
+    """(conv_path, Fy, Fx, zb) that ``BlendBatch`` picks with conv_path="auto" for one frame.
+    zb: the fused kernel's variant, the number of all-padding 16-row / 16-column blocks of the
+    frame up to 2 (fused_conv.hip, launch_impl): its FFT skips them, and contracted arithmetic
+    next to skipped zeros rounds differently, so blends of one batch must agree on it.  With
+    ``zb`` equal for every member the padded frame has the same (the minimum of theirs)."""
+    if kernel_shape is None:
+        return None, h, w, 0
+    try:
+        fy, fx = fft_shape_for(h, w, kernel_shape, "fused")
+    except Exception:  # noqa: BLE001 -- the fused kernel cannot take the frame
+        return ("rocfft",) + fft_shape_for(h, w, kernel_shape, "rocfft") + (0,)
+    zb = min(fy // 16 - (h + 15) // 16, fx // 16 - (w + 15) // 16, 2)
+    return "fused", fy, fx, zb
+
+
 class BlendBatch:
     """A batch of blends sharing the frame shape ``(C, H, W)``.
 
@@ -179,17 +195,26 @@ class BlendBatch:
         ``[:h, :w]`` of its ``(H, W)`` plane and its components are clipped to it (ragged
         frames in one batch; ``smi_batch_set_frame_extents``).  Pad data and weights beyond
         it with finite values and weight 0.
+    frame_kinds: what may stand next to ``frame_shapes``.  "image" (the lite loop's
+        contract): image components only, and no ``resize_test``.  "all" (``fit_blends``;
+        ``smi_batch_set_frame_extents_all``): point sources, shifting, starlet and profile
+        components as well, and ``resize_test`` / ``update_components`` work as without
+        extents.
     """
 
     def __init__(self, data, weights, components, kernel=None, max_iter=200,
                  fft_shape=None, device=0, conv_path="auto", scheme="amsgrad", log_norm=True,
-                 frame_shapes=None):
+                 frame_shapes=None, frame_kinds="image"):
+        if frame_kinds not in ("image", "all"):
+            raise ValueError("frame_kinds must be 'image' or 'all'")
+        self.frame_kinds = frame_kinds
         if any(getattr(c, "profile", None) is not None for blend in components for c in blend):
             # (refused by the library as well; here before any device work)
             if scheme != "amsgrad":
                 raise NotImplementedError("profile components with scheme={!r} (FISTA)".format(scheme))
-            if frame_shapes is not None:
-                raise NotImplementedError("profile components with frame extents")
+            if frame_shapes is not None and frame_kinds != "all":
+                raise NotImplementedError("profile components with frame extents need "
+                                          "frame_kinds='all'")
         lib = _lib.load()
         self._lib = lib
         self._h = ctypes.c_void_p()
@@ -243,17 +268,21 @@ class BlendBatch:
 
     def set_frame_extents(self, frame_shapes):
         """One ``(h, w)`` per blend with ``1 <= h <= H``, ``1 <= w <= W``, or ``None`` for
-        the full frame everywhere (``smi_batch_set_frame_extents``)."""
-        if frame_shapes is not None and getattr(self, "_profile", None):
-            raise NotImplementedError("profile components with frame extents")
+        the full frame everywhere (``smi_batch_set_frame_extents``, or
+        ``smi_batch_set_frame_extents_all`` for a batch opened with ``frame_kinds="all"``)."""
+        every = getattr(self, "frame_kinds", "image") == "all"
+        if frame_shapes is not None and not every and getattr(self, "_profile", None):
+            raise NotImplementedError("profile components with frame extents need "
+                                      "frame_kinds='all'")
         if frame_shapes is None:
             _lib.check(self._lib.smi_batch_set_frame_extents(self._h, None, None))
             self.frame_shapes = None
             return
         hw = np.asarray(frame_shapes, dtype=np.int32).reshape(self.n_blends, 2)
         h, w = _lib.i32(hw[:, 0]), _lib.i32(hw[:, 1])
-        _lib.check(self._lib.smi_batch_set_frame_extents(
-            self._h, _lib.ptr(h, ctypes.c_int32), _lib.ptr(w, ctypes.c_int32)))
+        call = (self._lib.smi_batch_set_frame_extents_all if every
+                else self._lib.smi_batch_set_frame_extents)
+        _lib.check(call(self._h, _lib.ptr(h, ctypes.c_int32), _lib.ptr(w, ctypes.c_int32)))
         self.frame_shapes = [tuple(int(x) for x in r) for r in hw]
 
     # -- component tables ---------------------------------------------------

@@ -260,6 +260,9 @@ struct smi_batch {
     size_t saved_bytes[12] = {};
     int scheme = SMI_SCHEME_AMSGRAD;
     bool include_log_norm = true;
+    // what smi_batch_add_loss_constant has added to log_norm since the observation was set, call
+    // by call: smi_batch_set_frame_extents forms the term anew and adds them again
+    std::vector<std::vector<double>> loss_constants;
     bool lite_flags = false;  // some component uses FIT_CENTER / BG_THRESH
     int32_t *have_prev = nullptr;
     float *scratch = nullptr;  // update-kernel state of boxes too large for the LDS
@@ -292,6 +295,9 @@ struct smi_batch {
     int32_t *state = nullptr, *zero_state = nullptr, *n_loss = nullptr, *status_out = nullptr;
     int32_t *it_base = nullptr;  // BatchView::it_base (smi_batch_set_iteration_base)
     int32_t *frame_hw = nullptr;  // BatchView::frame_hw (smi_batch_set_frame_extents)
+    // the extents were set by smi_batch_set_frame_extents_all: every component kind and
+    // smi_batch_resize_test are allowed next to them
+    bool extents_all = false;
     int32_t *pause_at = nullptr, *conv_flag = nullptr;  // smi_batch_set_pause_at
     std::vector<char> plan_shared;  // plans[i] belongs to the plan cache (smi_batch_add_sweep_plan)
     int32_t *h_round = nullptr;  // pinned staging of smi_batch_set_round / get_round, 3 x n_blends
@@ -1200,6 +1206,41 @@ static int interleave_observation(smi_batch *b, const float *d_data, const float
     return SMI_OK;
 }
 
+// Observation.log_norm of the first observation into b->log_norm (zero for a batch without the
+// term), per blend over its own frame: a batch with frame extents sums it in the order of a batch
+// of the blend's own frame shape (log_norm_extents_kernel)
+static int observation_log_norm(smi_batch *b) {
+    if (b->frame_hw)
+        launch_log_norm_extents(b->weights, b->frame_hw, b->log_norm, b->d.n_blends, b->d.C, b->d.H,
+                                b->d.W, b->stream);
+    else
+        launch_log_norm(b->weights, b->log_norm, b->d.n_blends, (int64_t)b->d.C * b->d.H * b->d.W,
+                        b->stream);
+    if (!b->include_log_norm)
+        SMI_HIP(hipMemsetAsync(b->log_norm, 0, b->d.n_blends * sizeof(double), b->stream));
+    return SMI_OK;
+}
+
+static int add_to_log_norm(smi_batch *b, const double *constant) {
+    SMI_HIP(hipStreamSynchronize(b->stream));
+    const int nb = b->d.n_blends;
+    std::vector<double> ln(nb);
+    SMI_HIP(hipMemcpy(ln.data(), b->log_norm, nb * sizeof(double), hipMemcpyDeviceToHost));
+    for (int i = 0; i < nb; ++i) ln[i] += constant[i];
+    SMI_HIP(hipMemcpy(b->log_norm, ln.data(), nb * sizeof(double), hipMemcpyHostToDevice));
+    return SMI_OK;
+}
+
+// the term of the observation again, after the frame extents changed, with the constants added
+// since in their order (further observations and extents exclude each other)
+static int refresh_log_norm(smi_batch *b) {
+    if (!b->have_obs) return SMI_OK;
+    if (int rc = observation_log_norm(b)) return rc;
+    for (const auto &c : b->loss_constants)
+        if (int rc = add_to_log_norm(b, c.data())) return rc;
+    return SMI_OK;
+}
+
 int smi_batch_set_observation(smi_batch *b, const float *data, const float *weights) {
     SMI_REQUIRE(b && data && weights, "null argument");
     // (log_norm is recomputed from this observation alone: the terms of observations added
@@ -1215,10 +1256,8 @@ int smi_batch_set_observation(smi_batch *b, const float *data, const float *weig
     g_observation_uploads.fetch_add(1);
     b->own_obs = true;
     if ((rc = interleave_observation(b, b->data, b->weights, &b->dw))) return rc;
-    launch_log_norm(b->weights, b->log_norm, b->d.n_blends, (int64_t)b->d.C * b->d.H * b->d.W,
-                    b->stream);
-    if (!b->include_log_norm)
-        SMI_HIP(hipMemsetAsync(b->log_norm, 0, b->d.n_blends * sizeof(double), b->stream));
+    b->loss_constants.clear();
+    if (int rc2 = observation_log_norm(b)) return rc2;
     b->have_obs = true;
     refresh_view(b);
     return SMI_OK;
@@ -1239,12 +1278,8 @@ int smi_batch_add_loss_constant(smi_batch *b, const double *constant) {
     SMI_REQUIRE(b && constant, "null argument");
     SMI_REQUIRE(b->have_obs, "smi_batch_add_loss_constant follows smi_batch_set_observation");
     SMI_HIP(hipSetDevice(b->device));
-    SMI_HIP(hipStreamSynchronize(b->stream));
-    const int nb = b->d.n_blends;
-    std::vector<double> ln(nb);
-    SMI_HIP(hipMemcpy(ln.data(), b->log_norm, nb * sizeof(double), hipMemcpyDeviceToHost));
-    for (int i = 0; i < nb; ++i) ln[i] += constant[i];
-    SMI_HIP(hipMemcpy(b->log_norm, ln.data(), nb * sizeof(double), hipMemcpyHostToDevice));
+    if (int rc = add_to_log_norm(b, constant)) return rc;
+    b->loss_constants.emplace_back(constant, constant + b->d.n_blends);
     return SMI_OK;
 }
 
@@ -1304,10 +1339,8 @@ int smi_batch_set_observation_device(smi_batch *b, const float *d_data, const fl
     b->data = const_cast<float *>(d_data);
     b->weights = const_cast<float *>(d_weights);
     if (int rc = interleave_observation(b, b->data, b->weights, &b->dw, true)) return rc;
-    launch_log_norm(b->weights, b->log_norm, b->d.n_blends, (int64_t)b->d.C * b->d.H * b->d.W,
-                    b->stream);
-    if (!b->include_log_norm)
-        SMI_HIP(hipMemsetAsync(b->log_norm, 0, b->d.n_blends * sizeof(double), b->stream));
+    b->loss_constants.clear();
+    if (int rc2 = observation_log_norm(b)) return rc2;
     b->have_obs = true;
     refresh_view(b);
     return SMI_OK;
@@ -1611,10 +1644,12 @@ static int set_components_impl(smi_batch *b, const smi_components *c, const int3
     SMI_REQUIRE(c->blend && c->origin_y && c->origin_x && c->box_h && c->box_w &&
                     (keep || (c->sed && c->morph)) && c->sed_min_step && c->morph_step && c->prox_flags,
                 "missing component array");
-    if (b->frame_hw)
+    if (b->frame_hw && !b->extents_all)
         for (int k = 0; k < b->d.n_components; ++k)
-            SMI_REQUIRE(!(c->prox_flags[k] & (SMI_COMPONENT_POINT_SOURCE | SMI_COMPONENT_SHIFTING)),
-                        "frame extents: point sources and shifting components are not supported");
+            SMI_REQUIRE(!(c->prox_flags[k] & (SMI_COMPONENT_POINT_SOURCE | SMI_COMPONENT_SHIFTING |
+                                              SMI_COMPONENT_STARLET | SMI_COMPONENT_PROFILE)),
+                        "frame extents: image components only (smi_batch_set_frame_extents_all takes "
+                        "every kind)");
     SMI_HIP(hipSetDevice(b->device));
     SMI_HIP(hipStreamSynchronize(b->stream));  // pending steps may still read the old arrays
     const int n = b->d.n_components, nb = b->d.n_blends, C = b->d.C;
@@ -1693,7 +1728,6 @@ static int set_components_impl(smi_batch *b, const smi_components *c, const int3
                                                SMI_COMPONENT_FIXED_MORPH)),
                         "a starlet component takes no other flag than the two FIXED ones");
             SMI_REQUIRE(b->scheme == SMI_SCHEME_AMSGRAD, "starlet components with SMI_SCHEME_FISTA");
-            SMI_REQUIRE(!b->frame_hw, "frame extents: starlet components are not supported");
             SMI_REQUIRE(c->star_planes[k] >= 1 && c->star_planes[k] <= 31, "starlet planes out of range");
             SMI_REQUIRE(c->box_h[k] <= 4096 && c->box_w[k] <= 4096 && np * c->star_planes[k] < ((int64_t)1 << 31),
                         "starlet component box too large");
@@ -1713,7 +1747,6 @@ static int set_components_impl(smi_batch *b, const smi_components *c, const int3
             SMI_REQUIRE(!(c->prox_flags[k] & ~(SMI_COMPONENT_PROFILE | SMI_COMPONENT_FIXED_SED)),
                         "a profile component takes no other flag than SMI_COMPONENT_FIXED_SED");
             SMI_REQUIRE(b->scheme == SMI_SCHEME_AMSGRAD, "profile components with SMI_SCHEME_FISTA");
-            SMI_REQUIRE(!b->frame_hw, "frame extents: profile components are not supported");
             SMI_REQUIRE(c->prof_kind[k] == SMI_PROFILE_GAUSSIAN || c->prof_kind[k] == SMI_PROFILE_SPERGEL,
                         "unknown profile kind");
             SMI_REQUIRE(c->box_h[k] <= 4096 && c->box_w[k] <= 4096, "profile component box too large");
@@ -2135,7 +2168,9 @@ int smi_batch_update_components(smi_batch *b, const smi_components *c, const int
 
 int smi_batch_resize_test(smi_batch *b, int32_t *margin, double *edge_pull) {
     SMI_REQUIRE(b && b->have_components && margin && edge_pull, "components not set / null argument");
-    SMI_REQUIRE(!b->frame_hw, "smi_batch_resize_test does not support frame extents");
+    SMI_REQUIRE(!b->frame_hw || b->extents_all,
+                "smi_batch_resize_test does not support frame extents set by smi_batch_set_frame_extents "
+                "(smi_batch_set_frame_extents_all does)");
     SMI_HIP(hipSetDevice(b->device));
     const int n = b->d.n_components;
     int32_t *d_margin = nullptr;
@@ -2204,22 +2239,26 @@ int smi_batch_set_iteration_base(smi_batch *b, const int32_t *base) {
     return SMI_OK;
 }
 
-int smi_batch_set_frame_extents(smi_batch *b, const int32_t *h, const int32_t *w) {
+static int set_frame_extents_impl(smi_batch *b, const int32_t *h, const int32_t *w, bool all) {
     SMI_REQUIRE(b != nullptr, "null batch");
     SMI_REQUIRE((h == nullptr) == (w == nullptr), "smi_batch_set_frame_extents: h and w must both be set or both NULL");
     SMI_HIP(hipSetDevice(b->device));
     SMI_HIP(hipStreamSynchronize(b->stream));  // pending steps may still read the old extents
     if (!h) {
+        const bool had = b->frame_hw != nullptr;
         if (b->frame_hw) (void)hipFree(b->frame_hw);
         b->frame_hw = nullptr;
+        b->extents_all = false;
         refresh_view(b);
-        return SMI_OK;
+        return had ? refresh_log_norm(b) : SMI_OK;
     }
-    SMI_REQUIRE(b->n_point == 0 && b->n_shift == 0,
-                "frame extents: point sources and shifting components are not supported");
+    if (!all) {  // (the narrower call keeps its contract: image components, no resize test)
+        SMI_REQUIRE(b->n_point == 0 && b->n_shift == 0,
+                    "frame extents: point sources and shifting components are not supported");
+        SMI_REQUIRE(b->star.n_star == 0, "frame extents: starlet components are not supported");
+        SMI_REQUIRE(b->prof.n_prof == 0, "frame extents: profile components are not supported");
+    }
     SMI_REQUIRE(!b->ks.stamp, "frame extents: a shifting difference kernel is not supported");
-    SMI_REQUIRE(b->star.n_star == 0, "frame extents: starlet components are not supported");
-    SMI_REQUIRE(b->prof.n_prof == 0, "frame extents: profile components are not supported");
     SMI_REQUIRE(b->lowres.empty() && b->layers.empty(),
                 "frame extents: further observations are not supported");
     const int nb = b->d.n_blends;
@@ -2232,8 +2271,18 @@ int smi_batch_set_frame_extents(smi_batch *b, const int32_t *h, const int32_t *w
     }
     if (!b->frame_hw) SMI_HIP(dev_alloc(&b->frame_hw, hw.size()));
     SMI_HIP(hipMemcpy(b->frame_hw, hw.data(), hw.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    b->extents_all = all;
     refresh_view(b);
-    return SMI_OK;
+    // (the normalisation term of the loss is summed over the own frames from now on)
+    return refresh_log_norm(b);
+}
+
+int smi_batch_set_frame_extents(smi_batch *b, const int32_t *h, const int32_t *w) {
+    return set_frame_extents_impl(b, h, w, false);
+}
+
+int smi_batch_set_frame_extents_all(smi_batch *b, const int32_t *h, const int32_t *w) {
+    return set_frame_extents_impl(b, h, w, true);
 }
 
 int smi_batch_set_pause_at(smi_batch *b, const int32_t *it) {

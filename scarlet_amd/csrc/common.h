@@ -544,6 +544,8 @@ void launch_interleave_obs(const float *data, const float *weights, float4 *dw, 
                            int32_t H, int32_t W, hipStream_t s);
 void launch_log_norm(const float *weights, double *log_norm, int32_t nb, int64_t n,
                      hipStream_t s);
+void launch_log_norm_extents(const float *weights, const int32_t *frame_hw, double *log_norm,
+                             int32_t nb, int32_t C, int32_t H, int32_t W, hipStream_t s);
 void launch_wrap_kernel(const float *kern, float *out, int32_t n_img, int32_t ph,
                         int32_t pw, int32_t Fy, int32_t Fx, float scale, hipStream_t s);
 void launch_crop(const float *P, float *out, int32_t n_img, int32_t H, int32_t W,

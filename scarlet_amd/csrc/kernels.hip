@@ -1012,8 +1012,8 @@ __global__ __launch_bounds__(64) void point_source_kernel(BatchView v, const flo
     };
 
     if (mode != 2) {
-        // (point sources and frame extents exclude each other: smi_batch_set_frame_extents)
-        const float g_sed = gather_gradient<64>(v, c, G, us, v.H, v.W);
+        // (the blend's own frame, smi_batch_set_frame_extents: a wave-uniform read)
+        const float g_sed = gather_gradient<64>(v, c, G, us, v.frame_h(c.b), v.frame_w(c.b));
         __syncthreads();
         double gy = 0.0, gx = 0.0;
         if (moffat) {
@@ -2637,6 +2637,44 @@ __global__ __launch_bounds__(256) void log_norm_kernel(const float *weights, dou
     }
 }
 
+// The same term of a batch with frame extents (smi_batch_set_frame_extents): the sum runs over
+// the blend's own [C][h][w] corner of its [C][H][W] cube, pixel j of the corner going to the
+// thread that takes pixel j of the unpadded cube above, so the term has the bits it has in a
+// batch of the blend's own frame shape (the padding carries weight 0 and would add nothing, but
+// it would hand the pixels to other threads).  h <= H and w <= W are checked where the extents
+// are set.
+__global__ __launch_bounds__(256) void log_norm_extents_kernel(const float *weights,
+                                                               const int32_t *frame_hw,
+                                                               double *out, int C, int H, int W) {
+    const int b = blockIdx.x;
+    const int h = frame_hw[2 * b], w = frame_hw[2 * b + 1];
+    const int64_t n = (int64_t)C * h * w;
+    const float *cube = weights + (int64_t)b * C * H * W;
+    double cnt = 0.0, sl = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += 256) {
+        const int c = (int)(i / ((int64_t)h * w)), r = (int)(i - (int64_t)c * h * w);
+        const int y = r / w, x = r - y * w;
+        const float wv = cube[((int64_t)c * H + y) * W + x];
+        if (wv != 0.f) {
+            cnt += 1.0;
+            sl += log((double)wv);
+        }
+    }
+    cnt = wave_sum(cnt);
+    sl = wave_sum(sl);
+    __shared__ double pc[4], ps[4];
+    if ((threadIdx.x & 63) == 0) {
+        pc[threadIdx.x >> 6] = cnt;
+        ps[threadIdx.x >> 6] = sl;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double c = pc[0] + pc[1] + pc[2] + pc[3];
+        const double s = ps[0] + ps[1] + ps[2] + ps[3];
+        out[b] = 0.5 * c * 1.8378770664093453 - 0.5 * s;  // ln(2 pi)
+    }
+}
+
 // kernel stamp -> FFT input with the stamp centre (ph/2, pw/2) at index (0,0),
 // wrapped around (the layout the reference reaches with _pad + ifftshift,
 // fft.py:255-273), scaled by 1/(Fy Fx) for the unnormalised inverse transform
@@ -3307,6 +3345,12 @@ void launch_interleave_obs(const float *data, const float *weights, float4 *dw, 
 void launch_log_norm(const float *weights, double *log_norm, int32_t nb, int64_t n,
                      hipStream_t s) {
     hipLaunchKernelGGL(log_norm_kernel, dim3(nb), dim3(256), 0, s, weights, log_norm, n);
+}
+
+void launch_log_norm_extents(const float *weights, const int32_t *frame_hw, double *log_norm,
+                             int32_t nb, int32_t C, int32_t H, int32_t W, hipStream_t s) {
+    hipLaunchKernelGGL(log_norm_extents_kernel, dim3(nb), dim3(256), 0, s, weights, frame_hw,
+                       log_norm, C, H, W);
 }
 
 void launch_wrap_kernel(const float *kern, float *out, int32_t n_img, int32_t ph, int32_t pw,

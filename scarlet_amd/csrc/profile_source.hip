@@ -85,8 +85,10 @@ __device__ void profile_step(const BatchView &v, const ProfileView &pv, const fl
     __shared__ double sh[kWaves * kProfileDoubles];
     double *par = pv.par + (int64_t)s * kProfileDoubles;
     const ProfileConsts pc = profile_consts(par, KIND);
-    // the box clipped to the frame: the gradient is zero where it overhangs (blend.py:30-46)
-    const int y_lo = max(oy, 0), y_hi = min(oy + h, v.H), x_lo = max(ox, 0), x_hi = min(ox + w, v.W);
+    // the box clipped to the blend's own frame (smi_batch_set_frame_extents: a wave-uniform
+    // read): the gradient is zero where it overhangs (blend.py:30-46)
+    const int y_lo = max(oy, 0), y_hi = min(oy + h, v.frame_h(b));
+    const int x_lo = max(ox, 0), x_hi = min(ox + w, v.frame_w(b));
     const int cw = max(x_hi - x_lo, 0), n = max(y_hi - y_lo, 0) * cw;
     const float *sed = v.sed + (int64_t)k * C;
     const int64_t plane = (int64_t)v.Fy * v.Fx;

@@ -263,6 +263,8 @@ __global__ __launch_bounds__(kT) void shift_backward_kernel(BatchView v, const f
     const float *sed = v.sed + (int64_t)k * C;
     double *pt = v.pt + (int64_t)k * 8;
     const double s_y = pt[0], s_x = pt[1];
+    // the blend's own frame (smi_batch_set_frame_extents): a wave-uniform read
+    const int Hb = v.frame_h(b), Wb = v.frame_w(b);
 
     // 1. gradient w.r.t. the shifted image over the box (zero outside the frame,
     //    blend.py:30-46) and w.r.t. the spectrum (lite/models.py:206-216)
@@ -277,7 +279,7 @@ __global__ __launch_bounds__(kT) void shift_backward_kernel(BatchView v, const f
         for (int i = tid; i < N; i += kT) {
             const int y = i / w, x = i - y * w;
             const int fy = y + oy, fx = x + ox;
-            const bool ok = (unsigned)fy < (unsigned)v.H && (unsigned)fx < (unsigned)v.W;
+            const bool ok = (unsigned)fy < (unsigned)Hb && (unsigned)fx < (unsigned)Wb;
             const float gv = ok ? Gc[(int64_t)fy * v.Fx + fx] : 0.f;
             L.g[i] = fmaf(s, gv, L.g[i]);
             part += (double)gv * (double)shifted[i];

@@ -159,13 +159,15 @@ __global__ __launch_bounds__(kT) void starlet_step_kernel(BatchView v, StarletVi
     const int oy = v.c_oy[c.k], ox = v.c_ox[c.k];
     const float *sed = v.sed + (int64_t)c.k * C;
     float *grad = sv.grad + c.coff;
+    // the blend's own frame (smi_batch_set_frame_extents): a wave-uniform read
+    const int Hb = v.frame_h(c.b), Wb = v.frame_w(c.b);
 
     // 1. a_0 = sum_c sed_c G_c over the box, zero outside the frame (blend.py:30-46)
     for (int i = tid; i < N; i += kT) {
         const int y = i / c.w, x = i - y * c.w;
         const int fy = y + oy, fx = x + ox;
         float acc = 0.f;
-        if ((unsigned)fy < (unsigned)v.H && (unsigned)fx < (unsigned)v.W) {
+        if ((unsigned)fy < (unsigned)Hb && (unsigned)fx < (unsigned)Wb) {
             const float *g = G + ((int64_t)c.b * C * v.Fy + fy) * v.Fx + fx;
             for (int ch = 0; ch < C; ++ch) acc = fmaf(sed[ch], g[(int64_t)ch * v.Fy * v.Fx], acc);
         }

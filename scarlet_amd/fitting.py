@@ -1,25 +1,30 @@
-"""``fit_blends``: many ``Blend`` objects fitted in one device batch per group of equal frame and
-kernel shapes (reference: the per-blend loop of scarlet/testing/api.py:216-224, every blend through
-``Blend.fit``, blend.py:85-198).  The batch stays on the device for the whole call: resize test
-and resize on the device, every blend at its own iteration counter and pausing at its own
-hooks; ``Blend.fit`` takes the same path for one blend.
+"""``fit_blends``: many ``Blend`` objects fitted in one device batch per group of blends whose
+own frames get the same convolution (reference: the per-blend loop of
+scarlet/testing/api.py:216-224, every blend through ``Blend.fit``, blend.py:85-198).  The batch
+stays on the device for the whole call: resize test and resize on the device, every blend at its
+own iteration counter and pausing at its own hooks; ``Blend.fit`` takes the same path for one
+blend.
 
-``_fit_blends_on`` sorts the blends (``_classify``) into those ``Blend.fit``'s own loop has to
-fit and groups of equal shapes, each opened by ``_open_batch``.  ``_fit_group_resident`` is the
-loop of a group; what it decides is plain NumPy on plain arrays, tested without a device: how
-far every blend runs in the next launch (``_plan_round``, on ``blend._next_round``), which boxes
-shrink or grow and to which size (``_resize_candidates``, on the rules of ``morphology.py``), the
+``_fit_blends_on`` sorts the blends (``_sort_blends``: ``_classify``, ``_group_key``) into those
+``Blend.fit``'s own loop has to fit and groups that share bands, kernel cube shape and the
+convolution plan of their own frame, each opened by ``_open_batch``: frames of different sizes
+are padded to the largest of the group (``_pad_cubes``) and clipped on the device
+(``BlendBatch(frame_shapes=..., frame_kinds="all")``), frames of one size open the batch they
+always opened.  ``_fit_group_resident`` is the loop of a group; what it decides is plain NumPy on
+plain arrays, tested without a device: how far every blend runs in the next launch
+(``_plan_round``, on ``blend._next_round``), which boxes shrink or grow and to which size (``_resize_candidates``, on the rules of ``morphology.py``), the
 rows the device resizes by itself (``_device_rows``).  ``_host_visit`` runs ``update()`` of the
 sources the device does not stand for, ``_component_table`` holds what the loop tracks per
 component and ``_write_back`` brings the device's state to the Python objects."""
 
+import functools
 import logging
 import os
 from types import SimpleNamespace
 
 import numpy as np
 
-from .batch import BlendBatch
+from .batch import BlendBatch, _conv_plan
 from .blend import (Blend, _adaprox_options, _at_hook, _flatten, _mark_std, _next_round,
                     _update_sources)
 from .component import CombinedComponent, FactorizedComponent
@@ -81,14 +86,25 @@ def _import_state(blend, state):
         _refresh_boxes(src)
 
 
-def fit_blends(blends, max_iter=200, e_rel=1e-3, min_iter=1, devices=None, **alg_kwargs):
+def fit_blends(blends, max_iter=200, e_rel=1e-3, min_iter=1, devices=None, _report=None,
+               **alg_kwargs):
     """Fit many independent ``Blend`` objects together.
 
     Equivalent to ``[b.fit(max_iter, e_rel, min_iter, **alg_kwargs) for b in blends]``
     -- same per-blend iteration counts, losses, parameter and optimizer-state side
-    effects -- but blends that share the frame shape and the difference-kernel stamp run
-    in one device batch, so every kernel launch works on all of them (the batched path
-    the benchmark measures, behind the reference's per-blend API).  The box-resizing hook
+    effects -- but blends that share the number of bands, the shape of the difference-kernel
+    cube and the convolution plan of their OWN frame (path, FFT shape and fused-kernel
+    variant: ``plan_fit_blends``) run in one device batch, whatever their frame sizes, so
+    every kernel launch works on all of them (the batched path the benchmark measures,
+    behind the reference's per-blend API).  Frames of different sizes are padded to the
+    largest of their group with data 0 and weight 0, and every component -- images, point
+    sources, shifting, starlet and profile components -- is clipped to its blend's own
+    frame on the device (``BlendBatch(frame_shapes=..., frame_kinds="all")``): a blend gets what
+    ``Blend.fit`` gives it alone, whatever list it is in -- bit for bit on the fused
+    convolution path; frames too large for it go through rocFFT, where the loss is summed in
+    blocks of the padded plane and a padded blend's losses are those of its own fit to the
+    rounding of that float64 sum.  Blends without a convolution
+    (``NullRenderer``) share a batch when their frames are equal.  The box-resizing hook
     and the restart it triggers (blend.py:196-198, 284-292) stay per blend: after every
     round the blends are regrouped by their own iteration counter.
 
@@ -103,10 +119,19 @@ def fit_blends(blends, max_iter=200, e_rel=1e-3, min_iter=1, devices=None, **alg
     Returns the list of ``(n_iter, logL)`` tuples; a blend whose parameters turned
     non-finite gets ``(n_iter, nan)`` (and keeps the state of its last iteration), the
     others continue; ``fit_blends.errors`` lists ``(index, ArithmeticError)`` of the last call.
+
+    ``_report``: a dict that receives what the call did -- ``"groups"`` and ``"alone"`` as
+    ``plan_fit_blends`` returns them and ``"batches"``, the number of ``BlendBatch`` objects
+    the groups opened (with ``devices="ranks"``: of this rank's shard).
     """
     blends = list(blends)
     kw = dict(max_iter=max_iter, e_rel=e_rel, min_iter=min_iter, **alg_kwargs)
     fit_blends.errors = []
+    report = dict(groups=[], alone={}, batches=0)
+    if _report is not None:
+        _report.clear()
+        _report.update(report)
+        report = _report
     if isinstance(devices, str):
         if devices != "ranks":
             raise ValueError("devices must be None, an int, a list of GPU indices or 'ranks'")
@@ -123,7 +148,9 @@ def fit_blends(blends, max_iter=200, e_rel=1e-3, min_iter=1, devices=None, **alg
         # a rank that fails must still take part in the collective, or the others hang in it:
         # its exception travels as text and every rank raises together
         try:
-            mine, errs = _fit_blends_on(blends[lo:hi], local_rank, **kw)
+            part = {}
+            mine, errs = _fit_blends_on(blends[lo:hi], local_rank, _report=part, **kw)
+            _merge_report(report, part, lo)
             part = dict(lo=lo, results=mine, errors=[(lo + i, str(e)) for i, e in errs],
                         states=[_export_state(b) for b in blends[lo:hi]], failed=None)
             import pickle
@@ -165,7 +192,7 @@ def fit_blends(blends, max_iter=200, e_rel=1e-3, min_iter=1, devices=None, **alg
                 _freeze_users[0] += 1
                 mine = True
         try:
-            out, fit_blends.errors = _fit_blends_on(blends, device, **kw)
+            out, fit_blends.errors = _fit_blends_on(blends, device, _report=report, **kw)
         finally:
             if mine:
                 with _freeze_lock:
@@ -177,18 +204,62 @@ def fit_blends(blends, max_iter=200, e_rel=1e-3, min_iter=1, devices=None, **alg
     from .dist import shard_range
 
     cuts = [shard_range(len(blends), i, len(devices)) for i in range(len(devices))]
+    parts = [{} for _ in cuts]
     with ThreadPoolExecutor(len(devices)) as pool:
-        jobs = [pool.submit(_fit_blends_on, blends[lo:hi], int(dev), **kw)
-                for (lo, hi), dev in zip(cuts, devices)]
+        jobs = [pool.submit(_fit_blends_on, blends[lo:hi], int(dev), _report=rep, **kw)
+                for (lo, hi), dev, rep in zip(cuts, devices, parts)]
         out = []
-        for (lo, _), job in zip(cuts, jobs):
+        for (lo, _), job, rep in zip(cuts, jobs, parts):
             part, errs = job.result()
+            _merge_report(report, rep, lo)
             out.extend(part)
             fit_blends.errors.extend((lo + i, e) for i, e in errs)
     return out
 
 
 fit_blends.errors = []
+
+
+def _merge_report(report, part, lo):
+    """The report of the shard that starts at blend ``lo`` into the report of the call."""
+    report["groups"].extend((key, [lo + i for i in idx]) for key, idx in part.get("groups", []))
+    report["alone"].update((lo + i, why) for i, why in part.get("alone", {}).items())
+    report["batches"] += part.get("batches", 0)
+
+
+def plan_fit_blends(blends, max_iter=200, e_rel=1e-3, min_iter=1, devices=None, **alg_kwargs):
+    """``(groups, alone)`` of ``fit_blends(blends, ...)`` with the same arguments, without a
+    GPU: ``groups``, a list of ``(key, positions)`` -- the blends of every device batch, in the
+    order the batches are opened and in list order inside a group -- and ``alone``,
+    ``{position: reason}`` of the blends ``Blend.fit``'s own loop fits one at a time.
+    ``key = (bands, kernel cube shape, (conv_path, Fy, Fx, zb))``: the convolution plan is
+    that of the blend's own frame (``_conv_plan``), so the frames of a group may differ;
+    without a kernel (``NullRenderer``) the plan is ``(None, h, w, 0)``, the frame itself.
+    With a list of ``devices`` every shard (``dist.shard_range``) has groups of its own.
+    Like the fit, the call prepares the blends' device descriptions and drops what an earlier
+    ``fit`` left of its scheme on them."""
+    blends = list(blends)
+    if isinstance(devices, str) and devices != "ranks":
+        raise ValueError("devices must be None, an int, a list of GPU indices or 'ranks'")
+    if isinstance(devices, str):
+        from . import dist as sdist
+
+        rank, _, world = sdist.env_rank()
+        if not sdist._active():
+            rank, world = 0, 1
+        cuts = [sdist.shard_range(len(blends), rank, world)]
+    elif devices is None or np.isscalar(devices) or len(devices) == 1:
+        cuts = [(0, len(blends))]
+    else:
+        from .dist import shard_range
+
+        cuts = [shard_range(len(blends), i, len(devices)) for i in range(len(devices))]
+    report = dict(groups=[], alone={}, batches=0)
+    for lo, hi in cuts:
+        part = {}
+        _sort_blends(blends[lo:hi], dict(alg_kwargs), part)
+        _merge_report(report, part, lo)
+    return report["groups"], report["alone"]
 
 
 def _device_hook_covers(node):
@@ -208,15 +279,38 @@ def _device_hook_covers(node):
     return False
 
 
-def _open_batch(runs, specs, flat, capacity, device, opt):
-    """The device batch of a group of blends that share the frame and kernel shapes: their
-    observation cubes stacked, the components ``flat`` described by ``specs`` (per blend),
-    room for ``capacity`` losses per blend, the blends' loss constants, the state stored on the
-    Parameters and the optimizer constants ``opt``."""
+def _pad_cubes(cubes):
+    """``(n, C, H, W)`` float32: the ``(C, h, w)`` cubes in the top left corners of planes of
+    the largest ``h`` and the largest ``w``, zeros beyond."""
+    H, W = max(c.shape[1] for c in cubes), max(c.shape[2] for c in cubes)
+    out = np.zeros((len(cubes), cubes[0].shape[0], H, W), dtype=np.float32)
+    for i, c in enumerate(cubes):
+        out[i, :, :c.shape[1], :c.shape[2]] = c
+    return out
+
+
+def _open_batch(runs, specs, flat, capacity, device, opt, report=None):
+    """The device batch of a group of blends (``_group_key``): their observation cubes stacked,
+    the components ``flat`` described by ``specs`` (per blend), room for ``capacity`` losses
+    per blend, the blends' loss constants, the state stored on the Parameters and the
+    optimizer constants ``opt``.  Frames of different sizes are padded to the largest (data 0,
+    weight 0) and become the batch's frame extents; the convolution is the one every member's
+    own frame gets (the padded frame might pick another).  ``report["batches"]`` counts."""
     data, weights, kernel = zip(*(r.obs for r in runs))
-    batch = BlendBatch(np.stack(data), np.stack(weights), specs,
+    frames = [tuple(d.shape[1:]) for d in data]
+    ragged = {}
+    if len(set(frames)) > 1:
+        path, fy, fx, _ = _conv_plan(*frames[0], kernel[0].shape)
+        ragged = dict(fft_shape=(fy, fx), conv_path=path, frame_shapes=frames,
+                      frame_kinds="all")
+        data, weights = _pad_cubes(data), _pad_cubes(weights)
+    else:
+        data, weights = np.stack(data), np.stack(weights)
+    batch = BlendBatch(data, weights, specs,
                        kernel=None if kernel[0] is None else np.stack(kernel),
-                       max_iter=capacity, device=device)
+                       max_iter=capacity, device=device, **ragged)
+    if report is not None:
+        report["batches"] = report.get("batches", 0) + 1
     try:
         if any(r.blend._loss_constant for r in runs):
             batch.add_loss_constant([r.blend._loss_constant for r in runs])
@@ -228,10 +322,10 @@ def _open_batch(runs, specs, flat, capacity, device, opt):
     return batch
 
 
-def _fit_group_rebuilt(group, device, max_iter, opt, step_kw):
-    """Blends that share the frame and kernel shapes, with components the resident path does
-    not cover (point sources, free shifts): a device batch per round and iteration counter,
-    state over the host in between."""
+def _fit_group_rebuilt(group, device, max_iter, opt, step_kw, report=None):
+    """Blends of one group (``_group_key``), with components the resident path does not cover
+    (point sources, free shifts, starlet and profile components): a device batch per round and
+    iteration counter, state over the host in between."""
     while True:
         todo = [r for r in group if r.result is None and r.total < max_iter]
         if not todo:
@@ -244,7 +338,7 @@ def _fit_group_rebuilt(group, device, max_iter, opt, step_kw):
             flat = [c for cs in comps for c in cs]
             n = _next_round(local, min(max_iter - r.total for r in part))
             batch = _open_batch(part, [r.blend._specs(c) for r, c in zip(part, comps)], flat, n,
-                                device, opt)
+                                device, opt, report)
             try:
                 if local > 0:  # the stopping rule compares with the loss before this round
                     batch.set_previous_loss(np.array([r.blend.loss[-1] for r in part]))
@@ -450,8 +544,8 @@ def _write_back(batch, group, flat, t):
         r.blend.loss.extend(history[i][:n_loss[i]])
 
 
-def _fit_group_resident(group, device, max_iter, opt, step_kw, mode=None):
-    """Blends that share the frame and kernel shapes, factorized image components only: ONE
+def _fit_group_resident(group, device, max_iter, opt, step_kw, mode=None, report=None):
+    """Blends of one group (``_group_key``), factorized image components only: ONE
     device batch for the whole fit, and every launch steps ALL blends that are still
     iterating.  The observation is uploaded once.  A blend whose boxes change starts its
     adaprox call anew (blend.py:276-302) while its batch mates go on: the device keeps the
@@ -482,7 +576,7 @@ def _fit_group_resident(group, device, max_iter, opt, step_kw, mode=None):
     state = np.zeros(nb, dtype=np.int32)  # 0 iterating, 2 finished, 3 failed
     g = 0  # the batch's iteration counter: blend i is at g - (its counter base) = local[i]
     pushed = (None, None)  # what the device holds as per-blend states / counter bases
-    batch = _open_batch(group, specs, flat, max(max_iter, 1), device, opt)
+    batch = _open_batch(group, specs, flat, max(max_iter, 1), device, opt, report)
     try:
         while True:
             plan = _plan_round(state, max_iter - base - local, local, g, mode == "lockstep")
@@ -625,6 +719,49 @@ def _classify(blend):
     return None, _Run(blend, obs, specs)
 
 
+def _group_key(run):
+    """What the blends of one device batch share: the number of bands, the shape of the
+    difference-kernel cube (one stamp for all bands or one per band) and the convolution plan
+    of the blend's OWN frame -- ``(conv_path, Fy, Fx, zb)``, ``_conv_plan`` -- so that padding
+    to a batch mate's frame never changes the convolution a blend sees.  Without a kernel
+    (``NullRenderer``) the plan is the frame shape itself."""
+    data, _, kernel = run.obs
+    return _key_of(data.shape, None if kernel is None else kernel.shape)
+
+
+@functools.lru_cache(maxsize=4096)
+def _key_of(shape, kshape):
+    # (a catalogue of equal frames asks the library once, not once per blend)
+    C, h, w = (int(n) for n in shape)
+    kshape = None if kshape is None else tuple(int(n) for n in kshape)
+    return C, kshape, _conv_plan(h, w, kshape)
+
+
+def _sort_blends(blends, alg_kwargs, report):
+    """Every blend by itself (and why), or in a group: ``(prox_max_iter, opt, sorted_out,
+    groups)`` -- the adaprox options parsed from ``alg_kwargs`` (which is emptied),
+    ``_classify`` of every blend and ``[(key, positions)]`` in order of first appearance.
+    ``report`` receives ``groups`` and ``alone`` (``plan_fit_blends``)."""
+    report.update(groups=[], alone={}, batches=0)
+    if alg_kwargs.get("callback") is not None or alg_kwargs.get("scheme", "amsgrad") != "amsgrad":
+        why = ("a callback" if alg_kwargs.get("callback") is not None else
+               "scheme {!r}".format(alg_kwargs.get("scheme"))) + ": Blend.fit's host-stepped mode"
+        report["alone"] = {i: why for i in range(len(blends))}
+        return None, None, None, None
+    alg_kwargs.pop("scheme", None)
+    alg_kwargs.pop("callback", None)
+    prox_max_iter, opt = _adaprox_options(alg_kwargs)
+    sorted_out = [_classify(b) for b in blends]
+    groups = {}
+    for i, (why, run) in enumerate(sorted_out):
+        if why is not None:
+            report["alone"][i] = why
+        else:
+            groups.setdefault(_group_key(run), []).append(i)
+    report["groups"] = list(groups.items())
+    return prox_max_iter, opt, sorted_out, report["groups"]
+
+
 def _fit_alone(blend, device, *args, **kwargs):
     """``Blend.fit`` on GPU ``device``; an ArithmeticError is returned instead of raised."""
     blend.device = device
@@ -652,26 +789,26 @@ def _assemble(blends, fitted):
 
 
 def _fit_blends_on(blends, device, max_iter=200, e_rel=1e-3, min_iter=1, _from_fit=False,
-                   **alg_kwargs):
+                   _report=None, **alg_kwargs):
     """``fit_blends`` of ``blends`` on GPU ``device``: (results, [(index, error)]).
     ``_from_fit``: the call comes from ``Blend.fit`` itself, which keeps a blend that has to be
-    fitted by its own loop (``None, None`` is returned then).  The environment variable
-    ``SCARLET_AMD_FIT_BLENDS`` is a development switch for A/B runs, read here once per call:
-    ``rebuild`` (a batch per round instead of the resident one), ``host-resize`` (every resize
-    over the host), ``lockstep`` (all blends stop at the nearest hook of any of them)."""
+    fitted by its own loop (``None, None`` is returned then).  ``_report``: the dict of
+    ``fit_blends``.  The environment variable ``SCARLET_AMD_FIT_BLENDS`` is a development
+    switch for A/B runs, read here once per call: ``rebuild`` (a batch per round instead of
+    the resident one), ``host-resize`` (every resize over the host), ``lockstep`` (all blends
+    stop at the nearest hook of any of them)."""
     args = (max_iter, e_rel, min_iter)
-    if alg_kwargs.get("callback") is not None or alg_kwargs.get("scheme", "amsgrad") != "amsgrad":
+    report = {} if _report is None else _report
+    host_stepped = dict(alg_kwargs)
+    prox_max_iter, opt, sorted_out, groups = _sort_blends(blends, alg_kwargs, report)
+    if sorted_out is None:
         # a callback sees every blend's parameters after every iteration, another scheme of
         # proxmin.adaprox steps on the host from the device's gradients: both are Blend.fit's
         # host-stepped modes, one blend at a time -- which is what this call stands for
         # (scarlet/testing/api.py:216-224)
-        return _assemble(blends, [_fit_alone(b, device, *args, **alg_kwargs) for b in blends])
-    alg_kwargs.pop("scheme", None)
-    alg_kwargs.pop("callback", None)
-    prox_max_iter, opt = _adaprox_options(alg_kwargs)
+        return _assemble(blends, [_fit_alone(b, device, *args, **host_stepped) for b in blends])
     mode = os.environ.get("SCARLET_AMD_FIT_BLENDS")
     # -- every blend: by itself (and why), or in a batch
-    sorted_out = [_classify(b) for b in blends]
     if _from_fit and any(why is not None for why, _ in sorted_out):
         return None, None
     fitted = []
@@ -680,17 +817,13 @@ def _fit_blends_on(blends, device, max_iter=200, e_rel=1e-3, min_iter=1, _from_f
             logger.debug("fit_blends: blend %d is fitted by itself: %s", i, why)
             run = _fit_alone(blends[i], device, *args, prox_max_iter=prox_max_iter, **opt)
         fitted.append(run)
-    # -- the groups of equal frame and kernel shapes
+    # -- the groups: bands, kernel cube shape and the convolution plan of the own frame
     step_kw = dict(e_rel=e_rel, min_iter=min_iter, prox_max_iter=prox_max_iter)
-    by_shape = {}
-    for r in fitted:
-        if isinstance(r, _Run):
-            data, _, kernel = r.obs
-            by_shape.setdefault((data.shape, None if kernel is None else kernel.shape), []).append(r)
-    for group in by_shape.values():
+    for _, idx in groups:
+        group = [fitted[i] for i in idx]
         if mode != "rebuild" and all(_device_hook_covers(src) for r in group
                                      for src in r.blend.sources):
-            _fit_group_resident(group, device, max_iter, opt, step_kw, mode)
+            _fit_group_resident(group, device, max_iter, opt, step_kw, mode, report)
         else:
-            _fit_group_rebuilt(group, device, max_iter, opt, step_kw)
+            _fit_group_rebuilt(group, device, max_iter, opt, step_kw, report)
     return _assemble(blends, fitted)

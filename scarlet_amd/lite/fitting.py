@@ -14,7 +14,7 @@ import threading
 
 import numpy as np
 
-from ..batch import BlendBatch, fft_shape_for
+from ..batch import BlendBatch, _conv_plan
 
 # rocFFT batches of transposed complex shapes must not be alive on one device at the same
 # time (smi_batch_create, plans_enter): with several host threads on one device, the
@@ -26,22 +26,6 @@ _rocfft_locks_guard = threading.Lock()
 def _rocfft_lock(device):
     with _rocfft_locks_guard:
         return _rocfft_locks.setdefault(device, threading.Lock())
-
-
-def _conv_plan(h, w, kernel_shape):
-    """(conv_path, Fy, Fx, zb) that ``BlendBatch`` picks with conv_path="auto" for one frame.
-    zb: the fused kernel's variant, the number of all-padding 16-row / 16-column blocks of the
-    frame up to 2 (fused_conv.hip, launch_impl): its FFT skips them, and contracted arithmetic
-    next to skipped zeros rounds differently, so blends of one batch must agree on it.  With
-    ``zb`` equal for every member the padded frame has the same (the minimum of theirs)."""
-    if kernel_shape is None:
-        return None, h, w, 0
-    try:
-        fy, fx = fft_shape_for(h, w, kernel_shape, "fused")
-    except Exception:  # noqa: BLE001 -- the fused kernel cannot take the frame
-        return ("rocfft",) + fft_shape_for(h, w, kernel_shape, "rocfft") + (0,)
-    zb = min(fy // 16 - (h + 15) // 16, fx // 16 - (w + 15) // 16, 2)
-    return "fused", fy, fx, zb
 
 
 def _check(blend, max_iter, e_rel):
