@@ -270,6 +270,71 @@ int smi_measure_sources_f32(int32_t device, int32_t C, int32_t kh, int32_t kw, i
  * tools/measure_blends_time.py */
 int smi_measure_sources_last_launch_ms(double *ms);
 
+/* render_blends: the images of many blends that share the number of model bands C and the
+ * (kh, kw) stamp shape; three launches.  Host buffers in, host buffers out; coordinates relative
+ * to the corner of the blend's frame; offsets and sizes count elements.  Components and bands are
+ * those of smi_measure_sources_f32; data[weight_off .. + fh fw] is the band's image beside its
+ * weights.  The bands of the blends tile the band table in order (blend.band0 = the bands of the
+ * blends before it), the components of a source are among its blend's.
+ *
+ * With R the blend's scene -- every model pixel of bands[..].channel the sum over the blend's
+ * components, in table order and in float64, of the rounded products seds[sed_off + c] *
+ * morphs[morph_off + y w + x], zero outside the frame -- convolved ("same", zero boundary, float64
+ * over the float32 taps), D the data and W the weights of observed band b of the blend:
+ *
+ *   rendered[blend.out_off + (b fh + y) fw + x] = float32(R)
+ *   residual[the same]                          = D - float32(R)           (in float32)
+ *   chi2[blend.band0 + b]                       = sum W (R - D)^2          (in float64)
+ *
+ * chi2 is summed per 16 x 16 tile (segments of 32 pixels in pixel order, the 8 segments joined
+ * by a butterfly), then over the tiles in tile order.  With SMI_RENDER_SOURCES, per source, R_k
+ * being its components alone rendered as smi_measure_sources_f32 renders them (the same bits) on
+ * its region (gy0, gx0, gh, gw) -- its box grown by the stamp's half, clipped to the frame --:
+ *
+ *   source_rendered[source.out_off + (b gh + y - gy0) gw + x - gx0] = float32(R_k)
+ *
+ * and with SMI_RENDER_REWEIGHT (which implies the former) the rules of scarlet/lite/measure.py:
+ *
+ *   flux[the same] = float32(ratio * image), ratio = max(R_k, 0) / max(R, 0), 0 where the
+ *   denominator is 0 and 1 where it exceeds 1; image = D, or D * (W > 0) with SMI_RENDER_MASK.
+ *
+ * Without SMI_RENDER_SOURCES n_sources must be 0; without SMI_RENDER_REWEIGHT `flux` is not
+ * written and may be NULL with n_flux 0.  launch_ms (may be NULL) receives the milliseconds the
+ * scene, sources and reduce launches took on the device (events around them).
+ *
+ * Limits: odd stamp sides <= 63, box and morphology sides <= 16384, a component's box inside its
+ * source's.  Every table is validated before anything is launched: a bad one returns
+ * SMI_ERR_INVALID and leaves the outputs alone.  The order of every sum depends on the frame, the
+ * boxes and the stamp shape alone: a blend's outputs have the same bits wherever it stands in the
+ * tables. */
+typedef struct smi_render_blend {
+    int32_t fh, fw;         /* frame */
+    int32_t comp0, n_comp;  /* its components, sources in a row, in the order they are added */
+    int32_t band0, n_band;  /* its observed bands in the band table */
+    int64_t out_off;        /* its [n_band][fh][fw] cubes in rendered and residual */
+} smi_render_blend;
+typedef struct smi_render_source {
+    int32_t y0, x0, h, w;   /* box of the source's model, may leave the frame */
+    int32_t blend;
+    int32_t comp0, n_comp;  /* its components, among its blend's */
+    int32_t reserved;
+    int64_t out_off;        /* its [n_band][gh][gw] cubes in source_rendered and flux */
+} smi_render_source;
+#define SMI_RENDER_SOURCES 1
+#define SMI_RENDER_REWEIGHT 2
+#define SMI_RENDER_MASK 4
+int smi_render_sources_f32(int32_t device, int32_t C, int32_t kh, int32_t kw, int32_t flags,
+                           int32_t n_blends, const smi_render_blend *blends, int32_t n_sources,
+                           const smi_render_source *sources, int32_t n_components,
+                           const smi_measure_component *components, int32_t n_bands,
+                           const smi_measure_band *bands, const double *seds, int64_t n_sed,
+                           const double *morphs, int64_t n_morph, const float *stamps,
+                           int64_t n_stamp, const float *data, int64_t n_data,
+                           const float *weights, int64_t n_weight, float *rendered,
+                           int64_t n_rendered, float *residual, int64_t n_residual, double *chi2,
+                           int64_t n_chi2, float *source_rendered, int64_t n_source_rendered,
+                           float *flux, int64_t n_flux, double *launch_ms);
+
 /* lite.init_blends: the wavelet initialisation of scarlet.lite (reference
  * lite/initialization.py:422-605) for a catalogue of blends.  Six steps, each one launch
  * over a table of tasks; the caller owns every buffer (`d_*`: device memory) and orders the

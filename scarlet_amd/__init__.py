@@ -57,6 +57,7 @@ from .blend import Blend  # noqa: F401
 from .fitting import fit_blends, plan_fit_blends  # noqa: F401
 from .initialization import init_blends, plan_init_blends  # noqa: F401
 from .measure import measure_blends, plan_measure_blends  # noqa: F401
+from .rendering import plan_render_blends, render_blends  # noqa: F401
 from .source import (  # noqa: F401
     ExtendedSource,
     SingleExtendedSource,
@@ -72,6 +73,7 @@ from .source import (  # noqa: F401
 from .model import Model, UpdateException  # noqa: F401
 from .wavelet import Starlet  # noqa: F401
 from . import detect, fft, initialization, measure, operator, synthetic, wavelet  # noqa: F401
+from . import rendering  # noqa: F401
 from ._lib import configure  # noqa: F401
 
 __version__ = "0.1.0"

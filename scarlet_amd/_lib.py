@@ -88,6 +88,16 @@ def _MEASURE_SOURCES():
             + [c_f64p, ctypes.c_int64] * 2)
 
 
+def _RENDER_SOURCES():
+    """smi_render_sources_f32: device, C, kh, kw, flags, then (count, table) of the blend, source,
+    component and band descriptors (numpy records of rendering.py and measure.py, passed as
+    void *), then the (buffer, size) pairs seds, morphs (float64), stamps, data, weights, rendered,
+    residual (float32), chi2 (float64), source_rendered, flux (float32), then launch_ms."""
+    return ([ctypes.c_int32] * 5 + [ctypes.c_int32, ctypes.c_void_p] * 4
+            + [c_f64p, ctypes.c_int64] * 2 + [c_f32p, ctypes.c_int64] * 5
+            + [c_f64p, ctypes.c_int64] + [c_f32p, ctypes.c_int64] * 2 + [c_f64p])
+
+
 def _LITE_INIT():
     """smi_lite_init_*: every entry takes (count, host table, device table), then device
     buffers as void * with their sizes in elements, then the stream (lite/initialization.py)."""
@@ -208,6 +218,7 @@ SYMBOLS = {
     "smi_lite_measure_last_launch_ms": (ctypes.c_int, [c_f64p]),
     "smi_measure_sources_f32": (ctypes.c_int, _MEASURE_SOURCES()),
     "smi_measure_sources_last_launch_ms": (ctypes.c_int, [c_f64p]),
+    "smi_render_sources_f32": (ctypes.c_int, _RENDER_SOURCES()),
     "smi_lite_spectra_f32": (ctypes.c_int, _LITE_SPECTRA(c_f32p)),
     "smi_lite_spectra_f64": (ctypes.c_int, _LITE_SPECTRA(c_f64p)),
     "smi_get_valid_monotonic_pixels_f32": (
