@@ -1322,6 +1322,81 @@ int smi_detect_wavelets_f64(int32_t n, const smi_detect_task *tasks, const void 
                             int32_t *d_support, int32_t *d_iterations, void *d_scratch,
                             int64_t scratch_bytes, void *stream);
 
+/* apply_wavelet_denoising (wavelet.py:424-465) for a ragged list of images, resident on the
+ * device (denoise_batch.hip): image_coeffs = T(image) with all the task's scales, generation 2;
+ * M = the "ground" multiresolution support of image_coeffs; x = R(image_coeffs); then max_iter
+ * times x = x + R(M * (image_coeffs - T(x))) and, if `positive`, x[x < 0] = 0.  Float64 in the
+ * reference's operation order: every image's x is bit for bit what smi_starlet_transform_* ->
+ * smi_multiresolution_support_f64 (n = 1) -> smi_starlet_reconstruction_f64 give with the
+ * element-wise steps between them.  The table convention is the one of smi_detect_wavelets_*
+ * (host copy validated before anything is launched, device copy read by the kernels, offsets
+ * and sizes in elements, the caller owns every buffer).  One task per image:
+ *   h, w       its pixels [h][w] at image_off of d_images
+ *   scales     planes = scales + 1 planes [h][w] at coeff_off of d_coeffs (image_coeffs),
+ *              d_support (M as 0 / 1) and d_current (work: T(x) and what follows); ranges in
+ *              table order, not overlapping
+ *   plane_off  its plane [h][w] of d_x (the result) and of d_work; ranges in table order,
+ *              not overlapping
+ *   sigma0, thresh0  as in smi_detect_task
+ * `stages` selects what runs, any union of
+ *   SMI_DENOISE_TRANSFORM  d_images -> d_coeffs
+ *   SMI_DENOISE_SUPPORT    d_coeffs -> d_support, d_iterations[n] (may be NULL), with max_iter
+ *                          iterations at most; h * w <= 65536 (one workgroup per image), d_scratch
+ *                          of smi_denoise_scratch_bytes(n) bytes
+ *   SMI_DENOISE_ITERATE    d_coeffs, d_support -> d_x
+ * so that an image beyond the limit of the support stage takes its support from
+ * smi_multiresolution_support_f64 between two calls.  h * w <= 2^30, 0 <= scales <= 30,
+ * n <= 65535, max_iter >= 1.  The calls allocate nothing, copy nothing and wait for nothing; they
+ * enqueue smi_denoise_launches(S, max_iter, stages) launches on `stream`, S the largest `scales`
+ * of the table, whatever n:
+ *   (1 + 4 S) + 2 + (2 S + max_iter * max(6 S, 1))     for the three stages. */
+enum { SMI_DENOISE_TRANSFORM = 1, SMI_DENOISE_SUPPORT = 2, SMI_DENOISE_ITERATE = 4 };
+typedef struct smi_denoise_task {
+    int32_t h, w, scales, reserved;
+    int64_t image_off, coeff_off, plane_off;
+    double sigma0, thresh0;
+} smi_denoise_task;
+int smi_denoise_scratch_bytes(int32_t n, int64_t *bytes);
+int smi_denoise_launches(int32_t top_scales, int32_t max_iter, int32_t stages, int32_t *launches);
+int smi_denoise_f32(int32_t n, const smi_denoise_task *tasks, const void *d_tasks, int32_t stages,
+                    double K, double epsilon, int32_t max_iter, int32_t positive,
+                    const float *d_images, int64_t n_images, double *d_coeffs, int32_t *d_support,
+                    double *d_current, int64_t n_coeffs, double *d_x, double *d_work,
+                    int64_t n_planes, int32_t *d_iterations, void *d_scratch,
+                    int64_t scratch_bytes, void *stream);
+int smi_denoise_f64(int32_t n, const smi_denoise_task *tasks, const void *d_tasks, int32_t stages,
+                    double K, double epsilon, int32_t max_iter, int32_t positive,
+                    const double *d_images, int64_t n_images, double *d_coeffs, int32_t *d_support,
+                    double *d_current, int64_t n_coeffs, double *d_x, double *d_work,
+                    int64_t n_planes, int32_t *d_iterations, void *d_scratch,
+                    int64_t scratch_bytes, void *stream);
+
+/* The resampling products of interpolate_observation (interpolation.py:427-463, 563-599) for a
+ * ragged catalogue (sinc_resample.hip): out = Sy . X . Sx^T for every band X [ho][wo] (float32 or
+ * float64, widened when read), Sy [hf][ho] and Sx [wf][wo] float64 sinc matrices formed on the
+ * host, out [hf][wf] float64.  One task per band and blend, table convention as above:
+ *   x_off            the band in d_x
+ *   sy_off, sx_off   the matrices in d_mats (the bands of a blend share theirs)
+ *   tmp_off          [hf][wo] of d_tmp for Sy . X; ranges in table order, not overlapping
+ *   out_off          the result in d_out; ranges in table order, not overlapping
+ * Every output element is one accumulator, the terms in ascending inner index, one fused
+ * multiply-add per step, first for Sy . X, then for (Sy . X) . Sx^T: its bits do not depend on
+ * the list or the grid.  Two launches whatever n <= 65535; nothing allocated, copied or waited
+ * for.  SMI_SINC_TILE: the side of the square LDS tiles. */
+#define SMI_SINC_TILE 16
+typedef struct smi_sinc_task {
+    int32_t ho, wo, hf, wf;
+    int64_t x_off, sy_off, sx_off, tmp_off, out_off;
+} smi_sinc_task;
+int smi_sinc_resample_f32(int32_t n, const smi_sinc_task *tasks, const void *d_tasks,
+                          const float *d_x, int64_t n_x, const double *d_mats, int64_t n_mats,
+                          double *d_tmp, int64_t n_tmp, double *d_out, int64_t n_out,
+                          void *stream);
+int smi_sinc_resample_f64(int32_t n, const smi_sinc_task *tasks, const void *d_tasks,
+                          const double *d_x, int64_t n_x, const double *d_mats, int64_t n_mats,
+                          double *d_tmp, int64_t n_tmp, double *d_out, int64_t n_out,
+                          void *stream);
+
 /* get_footprints (detect_pybind11.cc) on the host, in two calls.  The first finds the
  * footprints of image[H][W] -- 4-connected pixels > thresh, seeds in raster order, kept when
  * the box has more than min_area pixels and the footprint at least min_area -- with their

@@ -130,6 +130,28 @@ def _DETECT_BATCH():
     return out
 
 
+def _DENOISE_BATCH():
+    """smi_denoise_*: (count, host table, device table), stages, K, epsilon, max_iter, positive,
+    then device buffers as void * (images; image coefficients, support and current coefficients
+    with their common size; result and work planes with theirs), the iteration counts, the
+    scratch with its bytes, the stream (wavelet.py)."""
+    v, i32, i64, f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
+    args = [i32, v, v, i32, f64, f64, i32, i32, v, i64, v, v, v, i64, v, v, i64, v, v, i64, v]
+    out = {"smi_denoise_%s" % tag: (ctypes.c_int, args) for tag in ("f32", "f64")}
+    out["smi_denoise_scratch_bytes"] = (ctypes.c_int, [i32, c_i64p])
+    out["smi_denoise_launches"] = (ctypes.c_int, [i32, i32, i32, c_i32p])
+    return out
+
+
+def _SINC_RESAMPLE():
+    """smi_sinc_resample_*: (count, host table, device table), then the (buffer, size) pairs
+    bands, matrices, intermediates, results as void * with sizes in elements, the stream
+    (interpolation.py)."""
+    v, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+    args = [i32, v, v] + [v, i64] * 4 + [v]
+    return {"smi_sinc_resample_%s" % tag: (ctypes.c_int, args) for tag in ("f32", "f64")}
+
+
 def _INIT_SOURCES():
     """smi_init_sources_*: (count, host table, device table), then device buffers as void *
     with their sizes in elements, then the stream (initialization.init_blends)."""
@@ -427,6 +449,8 @@ SYMBOLS = {
 }
 SYMBOLS.update(_LITE_INIT())
 SYMBOLS.update(_DETECT_BATCH())
+SYMBOLS.update(_DENOISE_BATCH())
+SYMBOLS.update(_SINC_RESAMPLE())
 SYMBOLS.update(_INIT_SOURCES())
 
 _lib = None

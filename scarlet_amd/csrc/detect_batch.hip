@@ -34,11 +34,9 @@ namespace smi {
 namespace {
 
 constexpr int kT = kSupportT;
-constexpr int kWaves = kT / 64;
 constexpr int32_t kMaxScales = 30;
-constexpr int kThrSlots = 32;                        // thresholds of a task in the scratch
-constexpr int64_t kMaxPixels = 1 << 16;              // pixels of a frame
-constexpr int kMaxVirtual = kMaxPixels / (8 * kT);   // virtual blocks per plane
+constexpr int kThrSlots = kSupportSlots;             // thresholds of a task in the scratch
+constexpr int64_t kMaxPixels = kSupportMaxPixels;    // pixels of a frame
 constexpr int kWork = -1, kNone = -2;                // plane selectors of the pass kernel
 
 // ---------------------------------------------------------------------------- coadd
@@ -81,61 +79,17 @@ __global__ __launch_bounds__(kT) void detect_pass_kernel(const smi_detect_task *
 }
 
 // ---------------------------------------------------------------------------- support
-// The multiresolution support of the blend of this workgroup.  Pass 0 of a plane: mean of
-// v = w * ~M; pass 1: sum of (v - mean)^2.
+// The multiresolution support of the blend of this workgroup (support_workgroup of
+// starlet_device.h, which denoise_batch.hip runs as well).
 __global__ __launch_bounds__(kT) void detect_support_kernel(const smi_detect_task *tasks,
                                                             const double *coeffs, double K,
                                                             double epsilon, int max_iter,
                                                             double *thr_out,
                                                             int32_t *iterations) {
-    __shared__ double sh[kWaves];
-    __shared__ double part[kMaxVirtual];
-    __shared__ double s_thr[kThrSlots], s_last[kThrSlots], s_mean[kThrSlots], s_ss[kThrSlots];
-    __shared__ int s_done;
     const smi_detect_task t = tasks[blockIdx.x];
-    const int planes = t.scales + 1, npix = t.h * t.w, tid = threadIdx.x;
-    const int nb = support_blocks<int>(planes, npix);  // <= kMaxVirtual: npix <= kMaxPixels
-    const double *w0 = coeffs + t.coeff_off;
-    if (tid < planes) {
-        s_thr[tid] = t.thresh0;
-        s_last[tid] = t.sigma0;
-    }
-    __syncthreads();
-    int iters = 0;
-    for (int it = 0; it < max_iter; ++it) {
-        for (int pass = 0; pass < 2; ++pass) {
-            for (int k = 0; k < planes; ++k) {
-                const double *w = w0 + (int64_t)k * npix;
-                const double thr = s_thr[k];
-                const double m = pass ? s_mean[k] : 0.0;
-                for (int vb = 0; vb < nb; ++vb) {  // block vb of the per-image call's grid
-                    const double acc =
-                        support_partial<int>(w, vb * kT + tid, nb * kT, npix, thr, pass, m);
-                    const double s = block_sum(acc, sh);
-                    if (tid == 0) part[vb] = s;
-                }
-                __syncthreads();
-                double acc = 0;  // the final block: partials i, i + 256, ...
-                for (int i = tid; i < nb; i += kT) acc += part[i];
-                const double s = block_sum(acc, sh);
-                if (tid == 0) {
-                    if (pass)
-                        s_ss[k] = s;
-                    else
-                        s_mean[k] = s / (double)npix;
-                }
-            }
-            __syncthreads();
-        }
-        iters = it + 1;
-        if (tid == 0)
-            s_done = support_converged(s_ss, planes, (double)npix, K, epsilon, it + 1 == max_iter,
-                                       s_last, s_thr);
-        __syncthreads();
-        if (s_done) break;
-    }
-    if (tid < planes) thr_out[(int64_t)blockIdx.x * kThrSlots + tid] = s_thr[tid];
-    if (tid == 0) iterations[blockIdx.x] = iters;
+    support_workgroup(coeffs + t.coeff_off, t.scales + 1, t.h * t.w, t.sigma0, t.thresh0, K,
+                      epsilon, max_iter, thr_out + (int64_t)blockIdx.x * kThrSlots,
+                      iterations + blockIdx.x);
 }
 
 // M = |w| > thr as int, and M * w

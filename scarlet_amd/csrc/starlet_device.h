@@ -1,6 +1,7 @@
 // The starlet arithmetic (reference scarlet/wavelet.py:154-408) shared by the kernels of
 // starlet.hip -- (n, H, W) stacks of one call, float64 -- of detect_batch.hip -- a ragged table
-// of blends, float64 -- and of starlet_source.hip -- the float32 passes inside the fit loop.
+// of blends, float64 --, of denoise_batch.hip -- the denoising loop of a ragged list of images,
+// float64 -- and of starlet_source.hip -- the float32 passes inside the fit loop.
 // detect_batch.hip promises every blend the bits of its own starlet.hip chain, and
 // lite.init_blends mixes the two paths by frame size: the promise holds because both files
 // compute with the functions below, not with copies of them.  A kernel of any of the files
@@ -126,6 +127,71 @@ __host__ __device__ inline bool support_converged(double *ss, int planes, double
             thr[k] = K * ss[k];
         }
     return conv;
+}
+
+// ---------------------------------------------------------------------------- one workgroup
+// The whole multiresolution support of one image -- `planes` planes of npix pixels at w0 -- by
+// the workgroup of kSupportT threads that calls this, every thread of it: all iterations,
+// convergence test included (detect_batch.hip, denoise_batch.hip).  starlet.hip's per-image
+// call sums a plane in support_blocks() blocks and adds the partials in a final block; the
+// workgroup walks those blocks one after another, so sigma_j, the iteration count and every
+// mask bit equal that call's whatever the data.  npix <= kSupportMaxPixels (the partials of a
+// plane fit `part`), planes <= kSupportSlots.  Pass 0 of a plane: mean of v = w * ~M; pass 1:
+// sum of (v - mean)^2.  thr_out[planes] receives the final thresholds, *iterations the count.
+constexpr int kSupportSlots = 32;
+constexpr int64_t kSupportMaxPixels = 1 << 16;
+constexpr int kSupportMaxVirtual = kSupportMaxPixels / (8 * kSupportT);
+
+__device__ inline void support_workgroup(const double *w0, int planes, int npix, double sigma0,
+                                         double thresh0, double K, double epsilon, int max_iter,
+                                         double *thr_out, int32_t *iterations) {
+    __shared__ double sh[kSupportT / 64];
+    __shared__ double part[kSupportMaxVirtual];
+    __shared__ double s_thr[kSupportSlots], s_last[kSupportSlots], s_mean[kSupportSlots],
+        s_ss[kSupportSlots];
+    __shared__ int s_done;
+    const int tid = threadIdx.x;
+    const int nb = support_blocks<int>(planes, npix);  // <= kSupportMaxVirtual
+    if (tid < planes) {
+        s_thr[tid] = thresh0;
+        s_last[tid] = sigma0;
+    }
+    __syncthreads();
+    int iters = 0;
+    for (int it = 0; it < max_iter; ++it) {
+        for (int pass = 0; pass < 2; ++pass) {
+            for (int k = 0; k < planes; ++k) {
+                const double *w = w0 + (int64_t)k * npix;
+                const double thr = s_thr[k];
+                const double m = pass ? s_mean[k] : 0.0;
+                for (int vb = 0; vb < nb; ++vb) {  // block vb of the per-image call's grid
+                    const double acc = support_partial<int>(w, vb * kSupportT + tid,
+                                                            nb * kSupportT, npix, thr, pass, m);
+                    const double s = block_sum(acc, sh);
+                    if (tid == 0) part[vb] = s;
+                }
+                __syncthreads();
+                double acc = 0;  // the final block: partials i, i + 256, ...
+                for (int i = tid; i < nb; i += kSupportT) acc += part[i];
+                const double s = block_sum(acc, sh);
+                if (tid == 0) {
+                    if (pass)
+                        s_ss[k] = s;
+                    else
+                        s_mean[k] = s / (double)npix;
+                }
+            }
+            __syncthreads();
+        }
+        iters = it + 1;
+        if (tid == 0)
+            s_done = support_converged(s_ss, planes, (double)npix, K, epsilon, it + 1 == max_iter,
+                                       s_last, s_thr);
+        __syncthreads();
+        if (s_done) break;
+    }
+    if (tid < planes) thr_out[tid] = s_thr[tid];
+    if (tid == 0 && iterations) *iterations = iters;
 }
 
 }  // namespace

@@ -3,7 +3,9 @@
 The transform, its inverse and the multiresolution support run as HIP kernels
 (``csrc/starlet.hip``); the coefficients are the reference's bit for bit (float64, the
 B-spline sums in the reference's order, no FMA).  A user's own ``convolve2D`` callable runs
-on the host in NumPy, with the reference's loop around it.
+on the host in NumPy, with the reference's loop around it.  ``apply_wavelet_denoising`` and its
+list form ``apply_wavelet_denoising_batch`` keep set-up and loop on the device
+(``csrc/denoise_batch.hip``), with the same numbers as the loop over the functions above.
 
 Where the reference crashes this module does what was meant instead:
 
@@ -343,14 +345,280 @@ def get_multiresolution_support(image, starlets, sigma, K=3, epsilon=1e-1, max_i
     return M[:, 0].cpu().numpy().astype(int)
 
 
+# ---------------------------------------------------------------------------
+# wavelet denoising of a ragged list of images (csrc/denoise_batch.hip)
+# ---------------------------------------------------------------------------
+# smi_denoise_task: one image of smi_denoise_*
+DENOISE_TASK = np.dtype([("h", "i4"), ("w", "i4"), ("scales", "i4"), ("reserved", "i4"),
+                         ("image_off", "i8"), ("coeff_off", "i8"), ("plane_off", "i8"),
+                         ("sigma0", "f8"), ("thresh0", "f8")], align=True)
+# stages of smi_denoise_*
+DENOISE_TRANSFORM, DENOISE_SUPPORT, DENOISE_ITERATE = 1, 2, 4
+DENOISE_ALL = DENOISE_TRANSFORM | DENOISE_SUPPORT | DENOISE_ITERATE
+# limits of denoise_batch.hip: pixels of an image one workgroup takes through its support
+# iterations (the limit of detect_batch.hip), tasks of one call; device bytes of one chunk
+DENOISE_BATCH_MAX_PIXELS = DETECT_BATCH_MAX_PIXELS
+DENOISE_BATCH_MAX_TASKS = 65535
+DENOISE_BATCH_BYTES = 1 << 30
+
+
+def denoise_launches(top_scales, max_iter, stages=DENOISE_ALL):
+    """Launches one ``smi_denoise_*`` call enqueues: ``(1 + 4 S) + 2 + (2 S + max_iter *
+    max(6 S, 1))`` for the three stages, ``S = top_scales`` the largest scale count of the
+    table -- whatever the number of images.  Asked of the library; no GPU needed."""
+    n = ctypes.c_int32(0)
+    _lib.check(_lib.load().smi_denoise_launches(int(top_scales), int(max_iter), int(stages),
+                                                ctypes.byref(n)))
+    return n.value
+
+
+def _is_tensor(a):
+    return type(a).__module__.split(".")[0] == "torch"
+
+
+def _denoise_dtype(image):
+    """dtype of the device copy of ``image``: float32, or float64 for everything else."""
+    name = str(image.dtype).replace("torch.", "")
+    return np.dtype(np.float32 if name == "float32" else np.float64)
+
+
+def plan_wavelet_denoising_batch(images, max_iter=20, _max_tasks=None, _max_bytes=None):
+    """``(groups, one_by_one)`` of ``apply_wavelet_denoising_batch``, without touching the GPU.
+    ``groups``: one dict per device call -- ``dtype`` (float32, or float64 for everything else,
+    as ``_upload`` converts), ``images`` (input positions, in input order; at most 65535 and
+    ``DENOISE_BATCH_BYTES`` of device buffers), ``scales`` (the largest scale count among them)
+    and ``launches`` (``denoise_launches(scales, max_iter)``: a function of those two alone).
+    ``one_by_one``: ``(position, reason)`` of the images that do not join a group: more than
+    ``DENOISE_BATCH_MAX_PIXELS`` = 65536 pixels (one workgroup runs all support iterations of an
+    image; such an image keeps the per-image support between the same device-resident stages),
+    fewer than 2 pixels along an axis or not 2-D (the per-image function raises), and every
+    image when ``max_iter < 1`` (the per-image function's own behaviour)."""
+    max_tasks = DENOISE_BATCH_MAX_TASKS if _max_tasks is None else _max_tasks
+    max_bytes = DENOISE_BATCH_BYTES if _max_bytes is None else _max_bytes
+    groups, one_by_one, open_group, used = [], [], {}, {}
+    for i, im in enumerate(images):
+        if not _is_tensor(im):
+            im = np.asarray(im)
+        shape = tuple(im.shape)
+        if max_iter < 1:
+            one_by_one.append((i, "max_iter < 1"))
+            continue
+        if len(shape) != 2:
+            one_by_one.append((i, "not a 2-D image"))
+            continue
+        if min(shape) < 2:
+            one_by_one.append((i, "fewer than 2 pixels along an axis"))
+            continue
+        h, w = shape
+        if h * w > DENOISE_BATCH_MAX_PIXELS:
+            one_by_one.append((i, "more than %d pixels" % DENOISE_BATCH_MAX_PIXELS))
+            continue
+        dtype = _denoise_dtype(im)
+        scales = get_scales(shape)
+        # image, then image_coeffs (float64), M (int32), current coefficients (float64), x, work
+        need = h * w * (dtype.itemsize + (scales + 1) * 20 + 16)
+        g = open_group.get(dtype)
+        if g is None or len(g["images"]) >= max_tasks or used[dtype] + need > max_bytes:
+            g = open_group[dtype] = {"dtype": dtype, "images": [], "scales": 0}
+            groups.append(g)
+            used[dtype] = 0
+        g["images"].append(i)
+        g["scales"] = max(g["scales"], scales)
+        used[dtype] += need
+    for g in groups:
+        g["launches"] = denoise_launches(g["scales"], max_iter)
+    return groups, one_by_one
+
+
+def denoise_task_table(shapes, sigma0, thresh0):
+    """The task table of ``denoise_device`` for images of ``shapes`` ``(H, W)`` packed one after
+    another, each with all its scales: images, coefficient-shaped and plane-shaped buffers in
+    input order.  ``sigma0`` / ``thresh0``: per image, as ``initial_sigma`` rounds them."""
+    table = np.zeros(len(shapes), DENOISE_TASK)
+    plane_off = coeff_off = 0
+    for i, (h, w) in enumerate(shapes):
+        s = _checked_scales((h, w))
+        table[i] = (h, w, s, 0, plane_off, coeff_off, plane_off, sigma0[i], thresh0[i])
+        plane_off += h * w
+        coeff_off += (s + 1) * h * w
+    return table
+
+
+class _DenoiseBuffers:
+    """Device buffers of one ``smi_denoise_*`` table, allocated once before the calls."""
+
+    def __init__(self, torch, table, dev):
+        npix = table["h"].astype(np.int64) * table["w"]
+        n_coeffs = int(((table["scales"] + 1) * npix).sum())
+        n_planes = int(npix.sum())
+        self.n = len(table)
+        self.coeffs = torch.empty(n_coeffs, dtype=torch.float64, device=dev)
+        self.support = torch.empty(n_coeffs, dtype=torch.int32, device=dev)
+        self.current = torch.empty(n_coeffs, dtype=torch.float64, device=dev)
+        self.x = torch.empty(n_planes, dtype=torch.float64, device=dev)
+        self.work = torch.empty(n_planes, dtype=torch.float64, device=dev)
+        self.iterations = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        nbytes = ctypes.c_int64(0)
+        _lib.check(_lib.load().smi_denoise_scratch_bytes(self.n, ctypes.byref(nbytes)))
+        self.scratch = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+        self.table = table
+        self.d_table = torch.from_numpy(table.view(np.uint8)).to(dev)
+
+
+def denoise_device(d_images, buffers, stages, K=3, epsilon=1e-1, max_iter=20, positive=True):
+    """Enqueue the ``stages`` of ``smi_denoise_*`` for the images packed in the flat float32 /
+    float64 device tensor ``d_images`` (``buffers``: ``_DenoiseBuffers`` of their table);
+    ``buffers.x`` holds the result after ``DENOISE_ITERATE``.  Nothing is waited for."""
+    torch = _torch()
+    lib = _lib.load()
+    if d_images.dtype not in (torch.float32, torch.float64) or d_images.dim() != 1:
+        raise ValueError("d_images must be a flat float32 or float64 device tensor")
+    b = buffers
+    fn = lib.smi_denoise_f32 if d_images.dtype == torch.float32 else lib.smi_denoise_f64
+    with torch.cuda.device(d_images.device):
+        _lib.check(fn(b.n, b.table.ctypes.data, _vp(b.d_table), int(stages), float(K),
+                      float(epsilon), int(max_iter), int(bool(positive)), _vp(d_images),
+                      d_images.numel(), _vp(b.coeffs), _vp(b.support), _vp(b.current),
+                      b.coeffs.numel(), _vp(b.x), _vp(b.work), b.x.numel(), _vp(b.iterations),
+                      _vp(b.scratch), b.scratch.numel(), _stream(torch)))
+
+
+def _denoise_device_image(image):
+    """The float32 / float64 device tensor of ``image`` (array or tensor)."""
+    torch = _torch()
+    if not _is_tensor(image):
+        return _upload(image)
+    if image.dtype not in (torch.float32, torch.float64):
+        image = image.to(torch.float64)
+    return image.to("cuda").contiguous()
+
+
+def _denoise_sigma(image, sigma):
+    """``sigma`` of one image: as given, or the host median of the reference."""
+    if sigma is not None:
+        return sigma
+    if _is_tensor(image):
+        image = image.cpu().numpy()
+    return np.median(np.absolute(image - np.median(image)))
+
+
+def _denoise_pack(torch, images):
+    """The images of one group (one device dtype), packed one after another: one copy to the
+    device when they are all host arrays."""
+    if not any(_is_tensor(im) for im in images):
+        packed = np.empty(sum(im.size for im in images), images[0].dtype)
+        at = 0
+        for im in images:
+            packed[at:at + im.size] = im.reshape(-1)
+            at += im.size
+        return torch.from_numpy(packed).to("cuda")
+    return torch.cat([_denoise_device_image(im).reshape(-1) for im in images])
+
+
+def _denoise_tables(images, sigmas, k):
+    """Task table of a group's images with their first thresholds: ``sigma`` (None: the host
+    median) and ``initial_sigma`` in the dtype of the image AS GIVEN -- an int16 or float16 image
+    is transformed in float64, but its ``sigma_j`` start as ``get_multiresolution_support``
+    rounds them for the caller's array."""
+    first = []
+    for im, s in zip(images, sigmas):
+        dtype = _denoise_dtype(im).type if _is_tensor(im) else im.dtype.type
+        first.append(initial_sigma(dtype, 1, _denoise_sigma(im, s), k))
+    return denoise_task_table([tuple(im.shape) for im in images], [s0[0] for s0, _ in first],
+                              [t0[0] for _, t0 in first])
+
+
+def _denoise_one(image, sigma, k, epsilon, max_iter, positive, device):
+    """An image outside the groups.  Beyond the support stage's pixels: the transform and the
+    loop of denoise_batch.hip, resident on the device, around the per-image support.  Anything
+    else: the reference's loop over the public functions, with whatever it raises."""
+    shape = tuple(image.shape)
+    if max_iter < 1 or len(shape) != 2 or min(shape) < 2:
+        if _is_tensor(image):
+            image = image.cpu().numpy()
+        x = _denoise_host_loop(image, sigma, k, epsilon, max_iter, positive)
+        return _upload(x) if device else x
+    torch = _torch()
+    table = _denoise_tables([image], [sigma], k)
+    d_image = _denoise_device_image(image).reshape(-1)
+    buf = _DenoiseBuffers(torch, table, d_image.device)
+    denoise_device(d_image, buf, DENOISE_TRANSFORM, k, epsilon, max_iter, positive)
+    planes = int(table["scales"][0]) + 1
+    M, _, _ = support_device(buf.coeffs.reshape(planes, 1, *shape), table["sigma0"][0],
+                             table["thresh0"][0], k, epsilon, max_iter, masked=False)
+    buf.support.copy_(M.reshape(-1))
+    denoise_device(d_image, buf, DENOISE_ITERATE, k, epsilon, max_iter, positive)
+    x = buf.x.reshape(shape)
+    return x if device else x.cpu().numpy()
+
+
+def apply_wavelet_denoising_batch(images, sigma=None, k=3, epsilon=1e-1, max_iter=20,
+                                  image_type="ground", positive=True, device=False):
+    """``[apply_wavelet_denoising(im, ...) for im in images]`` for 2-D images of any shapes,
+    float32 and float64 mixed (other dtypes become float64), host arrays or device tensors, bit
+    for bit: per group of ``plan_wavelet_denoising_batch`` one packed upload and one device chain
+    (csrc/denoise_batch.hip) that holds set-up and loop and whose number of launches depends on
+    the largest scale count and ``max_iter`` only.  ``sigma``: None (the host median of every
+    image, taken before anything is enqueued), a scalar, or one entry per image.  Returns the
+    list of float64 ``(Ny_i, Nx_i)`` arrays -- with ``device=True`` float64 device tensors,
+    views into their group's buffer, without the copy to the host."""
+    assert image_type in ("ground", "space")
+    if image_type == "space":
+        raise NotImplementedError(
+            "apply_wavelet_denoising(image_type='space'): get_multiresolution_support provides "
+            "only the 'ground' branch (the reference's 'space' branch cannot run)")
+    given = [im if _is_tensor(im) else np.asarray(im) for im in images]
+    images = [im if _is_tensor(im) or im.dtype in (np.float32, np.float64)
+              else im.astype(np.float64) for im in given]
+    if sigma is None or np.ndim(sigma) == 0:
+        sigmas = [sigma] * len(images)
+    else:
+        sigmas = list(sigma)
+        if len(sigmas) != len(images):
+            raise ValueError("sigma must be None, a scalar or one entry per image, got {} for "
+                             "{} images".format(len(sigmas), len(images)))
+    groups, one_by_one = plan_wavelet_denoising_batch(images, max_iter)
+    out = [None] * len(images)
+    runs = []
+    if groups:
+        torch = _torch()
+    for g in groups:
+        ims = [images[i] for i in g["images"]]
+        table = _denoise_tables([given[i] for i in g["images"]],
+                                [sigmas[i] for i in g["images"]], k)
+        d_images = _denoise_pack(torch, ims)
+        buf = _DenoiseBuffers(torch, table, d_images.device)
+        denoise_device(d_images, buf, DENOISE_ALL, k, epsilon, max_iter, positive)
+        # only the result outlives the call: the stream keeps the order, and the caching
+        # allocator hands the other buffers to the next group once the work before is done
+        runs.append((g, buf.x, table))
+        del buf, d_images
+    for g, x, table in runs:
+        flat = x if device else x.cpu().numpy()
+        for i, t in zip(g["images"], table):
+            at, h, w = int(t["plane_off"]), int(t["h"]), int(t["w"])
+            out[i] = flat[at:at + h * w].reshape(h, w)
+    for i, _ in one_by_one:
+        out[i] = _denoise_one(given[i], sigmas[i], k, epsilon, max_iter, positive, device)
+    return out
+
+
 def apply_wavelet_denoising(image, sigma=None, k=3, epsilon=1e-1, max_iter=20,
                             image_type="ground", positive=True):
-    """Wavelet denoising of Starck et al. 2011, section 4.1 (wavelet.py:424-465)."""
+    """Wavelet denoising of Starck et al. 2011, section 4.1 (wavelet.py:424-465): the batch of
+    one image of ``apply_wavelet_denoising_batch``, set-up and loop resident on the device."""
+    return apply_wavelet_denoising_batch([image], None if sigma is None else [sigma], k, epsilon,
+                                         max_iter, image_type, positive)[0]
+
+
+def _denoise_host_loop(image, sigma, k, epsilon, max_iter, positive):
+    """The reference's loop over the public functions, one device call per step: what
+    ``max_iter < 1`` and images without a transform get (it raises as those calls do)."""
     image_coeffs = starlet_transform(image)
     if sigma is None:
         sigma = np.median(np.absolute(image - np.median(image)))
     coeffs = image_coeffs.copy()
-    support = get_multiresolution_support(image, coeffs, sigma, k, epsilon, max_iter, image_type)
+    support = get_multiresolution_support(image, coeffs, sigma, k, epsilon, max_iter, "ground")
     x = starlet_reconstruction(coeffs)
     for _ in range(max_iter):
         coeffs = starlet_transform(x)

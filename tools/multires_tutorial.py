@@ -1,7 +1,11 @@
 """The reference's multi-resolution tutorial (docs/tutorials/multiresolution.ipynb) through
 the facade, from the committed fixture: timings of set-up, initialisation and fit.
 
-    python tools/multires_tutorial.py [iterations]
+    python tools/multires_tutorial.py [iterations] [--detect]
+
+``--detect`` first builds the tutorial's detection image: the low-resolution observation
+sinc-interpolated onto the high-resolution grid with ``interpolate_observation`` (wavelet
+filtered), both observations normalised by their sums and added.
 """
 import os
 import sys
@@ -14,7 +18,9 @@ import scarlet_amd as scarlet  # noqa: E402
 
 g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden",
                          "multires_tutorial.npz"))
-n_iter = int(sys.argv[1]) if len(sys.argv) > 1 else 50
+with_detect = "--detect" in sys.argv
+argv = [a for a in sys.argv[1:] if a != "--detect"]
+n_iter = int(argv[0]) if argv else 50
 
 
 def wcs(tag, n):
@@ -32,6 +38,14 @@ obs_hsc = scarlet.Observation(g["data_hsc"].copy(), wcs=wcs("hsc", 50),
 observations = [obs_hsc, obs_hst]
 frame = scarlet.Frame.from_observations(observations, coverage="intersection",
                                         model_psf=scarlet.GaussianPSF(sigma=0.6))
+if with_detect:
+    # the tutorial's detection image, on the grid of the high-resolution observation
+    td = time.time()
+    interp = scarlet.interpolation.interpolate_observation(obs_hsc, obs_hst, wave_filter=True)
+    hst = np.asarray(obs_hst.data, dtype=np.float64)
+    detect_image = np.sum(interp, axis=0) / np.sum(interp) + np.sum(hst, axis=0) / np.sum(hst)
+    print("detection image %s from interpolate_observation(wave_filter=True): %.3f s"
+          % (tuple(detect_image.shape), time.time() - td))
 t1 = time.time()
 ra_dec = obs_hst.get_sky_coord(g["pixel_hst"])
 sources = [scarlet.ExtendedSource(frame, sky, observations, thresh=0.1) for sky in ra_dec]
