@@ -1228,13 +1228,57 @@ int smi_update_last_fold_plan_test(int64_t plan[8]);
  * resampler, `data` / `weights` are [C][n_a][n_b], `log_norm` is Observation.log_norm of
  * that observation.  From then on every iteration renders the model cube through `r`,
  * adds log_norm + chi^2 / 2 to the loss and the transposed operator applied to
- * w (m - d) to the gradient image.  Every call adds one observation (at most 8).  Batches
- * of one blend only; `r` must outlive `b`. */
+ * w (m - d) to the gradient image.  Every call adds one observation of blend 0 (at most 8 per
+ * blend).  A resampler on the spectral path hands its tables over (a copy: `r` need not
+ * outlive `b`) and the observation joins the pooled chain below; one on the dense path
+ * (smi_resampler_set_path(r, 0), or an operator that is not circulant) needs a batch of one
+ * blend and must outlive `b`. */
 int smi_batch_attach_lowres(smi_batch *b, smi_resampler *r, const int32_t *channels,
                             const float *data, const float *weights, double log_norm);
-/* rendering [C][n_a][n_b] of the index-th attached observation in the last forward /
- * gradient / step call */
+/* The same for blend `blend` of a batch of any size, from the host operators themselves
+ * (A[C][n_a][Fy*Fx], Pt[Fx][Fx*n_b] as for smi_resampler_create; Pt must be circulant, the
+ * dense path is not batched): the batch makes the transforms E[C][n_a][Fy][Kx] and
+ * beta[n_b][Kx], Kx = Fx / 2 + 1, on its own device -- C n_a Fy Kx 8 bytes per observation --
+ * and keeps neither A nor Pt.  Observation i of a blend (the i-th call for it) adds its term
+ * at slot i of that blend: loss_b = log_norm_b + chi2_b / 2 + sum_i term[b][i], i in the
+ * order of the calls.
+ *
+ * The i-th observations of one shape class (C, n_a, n_b, Fy, Fx) are evaluated together,
+ * nine launches per iteration and class whatever the number of blends: padding of the
+ * observed bands, the transforms along x as one batched product over blends x bands,
+ * G and out over (row a, band, blend) with every blend's own E and beta, residual and term by
+ * one workgroup per (blend, observation), Gbar, Mbar, the transform back and the add into that
+ * blend's plane of the gradient image.  A blend gets the bits of its own fit, because every sum
+ * keeps its order: G[k] is sixteen fma chains over y = q (mod 16) in increasing y (terms e.x
+ * m.x, e.y m.y / e.x m.y, -e.y m.x), added q = 0 .. 15; out is sixteen partials over k = part
+ * (mod 16) combined by the xor butterfly 8, 4, 2, 1; Gbar runs over b in increasing order;
+ * Mbar is four chains over a = w (mod 4) combined (0 + 1) + (2 + 3); and the two batched
+ * products take the slices (float32 inside a slice, double across) that smi_gemm_plan gives
+ * the blend's own C bands with its own scratch, whatever the batch.  The terms and renderings
+ * of a blend that has stopped are not written again.  Frame extents
+ * (smi_batch_set_frame_extents) and low-resolution observations do not combine. */
+int smi_batch_attach_lowres_blend(smi_batch *b, int32_t blend, const float *A, const float *Pt,
+                                  int32_t C, int32_t n_a, int32_t n_b, int32_t Fy, int32_t Fx,
+                                  const int32_t *channels, const float *data,
+                                  const float *weights, double log_norm);
+/* rendering [C][n_a][n_b] of the index-th attached observation (of blend 0 / of `blend`) in
+ * the last forward / gradient / step call that evaluated it */
 int smi_batch_get_lowres_rendered(smi_batch *b, int32_t index, float *out);
+int smi_batch_get_lowres_rendered_blend(smi_batch *b, int32_t blend, int32_t index, float *out);
+/* Test entry points (tests/test_gpu_resample_batch.py, tests/test_fit_blends_multires_host.py).
+ * smi_lowres_pool_test: n resamplers of one class (A[n][C][n_a][Fy*Fx], Pt[n][Fx][Fx*n_b])
+ * through the pooled chain on host buffers, models[n][C][Fy][Fx] -> out[n][C][n_a][n_b] and
+ * resid[n][C][n_a][n_b] -> gpad[n][C][Fy][Fx]; 256 guard floats before and after the pooled
+ * out and gpad must come back untouched (*guard_ok = 1).
+ * smi_lowres_gemm_plans_test (host only): {tm, tn, bk, kslice, n_slices} of the transform
+ * along x (adjoint = 1: the one back) of a resampler with C bands by itself (`own`) and of
+ * n_members of them in one launch (`pooled`; more products than the grid's z limit holds are
+ * cut into several launches, `pooled` is the first). */
+int smi_lowres_pool_test(int32_t n, const float *A, const float *Pt, int32_t C, int32_t n_a,
+                         int32_t n_b, int32_t Fy, int32_t Fx, const float *models,
+                         const float *resid, float *out, float *gpad, int32_t *guard_ok);
+int smi_lowres_gemm_plans_test(int32_t C, int32_t Fy, int32_t Fx, int32_t n_members,
+                               int32_t adjoint, int32_t own[5], int32_t pooled[5]);
 
 /* ------------------------------------------------------------------------- *
  * Detection: starlet wavelets (scarlet/wavelet.py) and footprints

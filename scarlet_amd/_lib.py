@@ -292,6 +292,19 @@ SYMBOLS = {
         ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32p, c_f32p, c_f32p, ctypes.c_double]
     ),
     "smi_batch_get_lowres_rendered": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_f32p]),
+    "smi_batch_attach_lowres_blend": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, c_f32p, c_f32p] + [ctypes.c_int32] * 5
+        + [c_i32p, c_f32p, c_f32p, ctypes.c_double],
+    ),
+    "smi_batch_get_lowres_rendered_blend": (
+        ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_f32p]),
+    "smi_lowres_pool_test": (
+        ctypes.c_int,
+        [ctypes.c_int32, c_f32p, c_f32p] + [ctypes.c_int32] * 5
+        + [c_f32p, c_f32p, c_f32p, c_f32p, c_i32p],
+    ),
+    "smi_lowres_gemm_plans_test": (ctypes.c_int, [ctypes.c_int32] * 5 + [c_i32p, c_i32p]),
     "smi_batch_create": (
         ctypes.c_int,
         [ctypes.POINTER(BatchDesc), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)],

@@ -819,27 +819,49 @@ class BlendBatch:
         _lib.check(self._lib.smi_batch_get_sub_ranges(self._h, ctypes.byref(n)))
         return n.value
 
-    def attach_lowres(self, resampler, channels, data, weights, log_norm):
-        """Add a further observation of the (single) blend on a coarser pixel grid as a
-        term of the loss and of the gradient (every call adds one).  ``resampler`` is the handle of a
-        ``ResolutionRenderer``'s device operators (``smi_resampler``), ``channels`` the
-        model channel of each of its bands, ``data`` / ``weights`` (C, n_a, n_b),
-        ``log_norm`` the observation's ``log_norm``."""
+    def attach_lowres(self, resampler, channels, data, weights, log_norm, blend=None):
+        """Add a further observation of a blend on a coarser pixel grid as a term of its loss
+        and of its gradient (every call adds one, at most eight per blend).  ``channels``: the
+        model channel of each of its bands, ``data`` / ``weights`` (C, n_a, n_b), ``log_norm``
+        the observation's ``log_norm``.
+
+        ``blend=None``: blend 0, ``resampler`` is the handle of a ``ResolutionRenderer``'s device
+        operators (``smi_resampler``); on the dense path that needs a batch of one blend.
+        ``blend=i``: blend ``i`` of a batch of any size, ``resampler`` is the renderer's host
+        operators ``(A, Pt, (Fy, Fx))`` (``ResolutionRenderer._operators``); the batch makes the
+        transforms it needs on its own device (``smi_batch_attach_lowres_blend``) and evaluates
+        the observations of one shape class together, whatever their number."""
         channels = np.ascontiguousarray(channels, dtype=np.int32)
         data = np.ascontiguousarray(data, dtype=np.float32)
         weights = np.ascontiguousarray(weights, dtype=np.float32)
         assert data.shape == weights.shape and data.shape[0] == len(channels)
-        self._lowres_shapes = getattr(self, "_lowres_shapes", []) + [data.shape]
-        _lib.check(self._lib.smi_batch_attach_lowres(
-            self._h, resampler, _lib.ptr(channels, ctypes.c_int32),
-            _lib.ptr(data, ctypes.c_float), _lib.ptr(weights, ctypes.c_float), float(log_norm)))
+        if not hasattr(self, "_lowres_shapes"):
+            self._lowres_shapes = {}
+        which = 0 if blend is None else int(blend)
+        if blend is None:
+            _lib.check(self._lib.smi_batch_attach_lowres(
+                self._h, resampler, _lib.ptr(channels, ctypes.c_int32),
+                _lib.ptr(data, ctypes.c_float), _lib.ptr(weights, ctypes.c_float),
+                float(log_norm)))
+        else:
+            A, Pt, (Fy, Fx) = resampler
+            C, n_a, n_b = data.shape
+            A = np.ascontiguousarray(A, dtype=np.float32)
+            Pt = np.ascontiguousarray(Pt, dtype=np.float32)
+            assert A.size == C * n_a * Fy * Fx and Pt.size == Fx * Fx * n_b
+            _lib.check(self._lib.smi_batch_attach_lowres_blend(
+                self._h, which, _lib.ptr(A, ctypes.c_float), _lib.ptr(Pt, ctypes.c_float),
+                C, n_a, n_b, int(Fy), int(Fx), _lib.ptr(channels, ctypes.c_int32),
+                _lib.ptr(data, ctypes.c_float), _lib.ptr(weights, ctypes.c_float),
+                float(log_norm)))
+        self._lowres_shapes.setdefault(which, []).append(data.shape)
 
-    def lowres_rendered(self, index=0):
-        """Rendering of the ``index``-th attached observation in the last forward /
-        gradient / step call."""
-        out = np.empty(self._lowres_shapes[index], dtype=np.float32)
-        _lib.check(self._lib.smi_batch_get_lowres_rendered(self._h, index,
-                                                           _lib.ptr(out, ctypes.c_float)))
+    def lowres_rendered(self, index=0, blend=0):
+        """Rendering of the ``index``-th attached observation of ``blend`` in the last forward /
+        gradient / step call that evaluated it."""
+        out = np.empty(self._lowres_shapes[int(blend)][index], dtype=np.float32)
+        _lib.check(self._lib.smi_batch_get_lowres_rendered_blend(
+            self._h, int(blend), index, _lib.ptr(out, ctypes.c_float)))
         return out
 
     def reset(self):

@@ -268,9 +268,26 @@ struct smi_batch {
     float *scratch = nullptr;  // update-kernel state of boxes too large for the LDS
     int64_t n_morph = 0;
     bool have_components = false, have_obs = false, have_kernel = false;
-    // further observations on coarser grids (one blend) and their loss terms (device)
-    std::vector<smi::LowRes *> lowres;
-    double *extra_terms = nullptr;
+    // Observations on coarser grids, in the order their terms are evaluated and their gradients
+    // added: by the index of the observation within its blend, so that a blend sees its own
+    // in the order they were attached, whatever batch it is in.  A unit is either the pool of
+    // the i-th observations of one shape class (spectral path, any number of blends) or one
+    // observation on the dense path (a batch of one blend).
+    struct LowResUnit {
+        int slot = 0;
+        smi::LowRes *single = nullptr;
+        smi::LowResPool *pool = nullptr;
+    };
+    std::vector<LowResUnit> lowres;
+    // per blend and observation: its unit (pool pointer or single) and member index
+    struct LowResWhere {
+        smi::LowRes *single = nullptr;
+        smi::LowResPool *pool = nullptr;
+        int member = 0;
+    };
+    std::vector<std::vector<LowResWhere>> lowres_of;  // [n_blends][count]
+    double *extra_terms = nullptr;   // [n_blends][kMaxLowRes]
+    int32_t *extra_count = nullptr;  // [n_blends]
     // ranges of blends stepped on streams of their own (blends are independent): the tail
     // of one range's update kernel overlaps the next iteration's convolution of the others
     int n_sub = 0;  // 0 = automatic
@@ -401,7 +418,7 @@ void refresh_view(smi_batch *b) {
     v.c_fista_step = b->c_fista_step;
     v.fista_t = b->fista_t;
     v.extra_term = b->extra_terms;
-    v.n_extra = (int32_t)b->lowres.size();
+    v.extra_count = b->extra_count;
     v.blend0 = 0;
     v.comp0 = 0;
     v.work = b->work_items;
@@ -767,37 +784,148 @@ int smi_update_last_fold_plan_test(int64_t plan[8]) {
     return SMI_OK;
 }
 
-static constexpr int kMaxLowRes = 8;
-
-int smi_batch_attach_lowres(smi_batch *b, smi_resampler *r, const int32_t *channels,
-                            const float *data, const float *weights, double log_norm) {
-    SMI_REQUIRE(b && r && channels && data && weights, "null argument");
-    SMI_REQUIRE(b->d.n_blends == 1, "a low-resolution observation needs a batch of one blend");
+// a low-resolution observation of blend `blend`: from the tables of resampler `r`, or from the
+// host operators A, Pt of shape class (C, n_a, n_b, Fy, Fx)
+static int attach_lowres(smi_batch *b, int32_t blend, smi_resampler *r, bool spectral,
+                         const float *A, const float *Pt, int C, int n_a, int n_b, int Fy, int Fx,
+                         const int32_t *channels, const float *data, const float *weights,
+                         double log_norm) {
+    const int nb = b->d.n_blends;
+    SMI_REQUIRE(blend >= 0 && blend < nb, "no such blend");
     SMI_REQUIRE(!b->frame_hw, "a low-resolution observation does not support frame extents");
-    SMI_REQUIRE(r->impl, "resampler already destroyed");
-    SMI_REQUIRE((int)b->lowres.size() < kMaxLowRes, "too many low-resolution observations");
+    for (int c = 0; c < C; ++c)
+        SMI_REQUIRE(channels[c] >= 0 && channels[c] < b->d.C, "no such model channel");
     SMI_HIP(hipSetDevice(b->device));
     SMI_HIP(hipStreamSynchronize(b->stream));
+    if (b->lowres_of.empty()) b->lowres_of.resize(nb);
+    const int slot = (int)b->lowres_of[blend].size();
+    SMI_REQUIRE(slot < kMaxLowRes, "too many low-resolution observations");
     if (!b->extra_terms) {
-        SMI_HIP(dev_alloc(&b->extra_terms, kMaxLowRes));
-        SMI_HIP(hipMemset(b->extra_terms, 0, kMaxLowRes * sizeof(double)));
+        SMI_HIP(dev_alloc(&b->extra_terms, (size_t)nb * kMaxLowRes));
+        SMI_HIP(hipMemset(b->extra_terms, 0, (size_t)nb * kMaxLowRes * sizeof(double)));
+        SMI_HIP(dev_alloc(&b->extra_count, nb));
+        SMI_HIP(hipMemset(b->extra_count, 0, nb * sizeof(int32_t)));
     }
-    LowRes *l = nullptr;
-    int rc = lowres_create(r->impl, channels, data, weights, log_norm, b->d.H, b->d.W,
-                           b->extra_terms + b->lowres.size(), &l);
-    if (rc) {
-        lowres_destroy(l);
-        return rc;
+    double *term = b->extra_terms + (size_t)blend * kMaxLowRes + slot;
+    // units stay sorted by slot: behind the last unit of this slot
+    auto behind = b->lowres.begin();
+    while (behind != b->lowres.end() && behind->slot <= slot) ++behind;
+    smi_batch::LowResWhere where;
+    if (r && !spectral) {
+        // the dense products: one blend, B alone is Fy Fx Fx n_b floats per band
+        SMI_REQUIRE(nb == 1, "a low-resolution observation on the dense path needs a batch of "
+                             "one blend");
+        LowRes *l = nullptr;
+        const int rc = lowres_create(r->impl, channels, data, weights, log_norm, b->d.H, b->d.W,
+                                     term, &l);
+        if (rc) {
+            lowres_destroy(l);
+            return rc;
+        }
+        smi_batch::LowResUnit u;
+        u.slot = slot;
+        u.single = l;
+        b->lowres.insert(behind, u);
+        where.single = l;
+    } else {
+        LowResPool *pool = nullptr;
+        for (auto &u : b->lowres)
+            if (u.slot == slot && u.pool && lowres_pool_matches(u.pool, C, n_a, n_b, Fy, Fx))
+                pool = u.pool;
+        if (!pool) {
+            const int rc = lowres_pool_create(C, n_a, n_b, Fy, Fx, b->d.H, b->d.W, &pool);
+            if (rc) {
+                lowres_pool_destroy(pool);
+                return rc;
+            }
+            smi_batch::LowResUnit u;
+            u.slot = slot;
+            u.pool = pool;
+            b->lowres.insert(behind, u);
+        }
+        const int rc = lowres_pool_add(pool, A, Pt, r ? r->impl : nullptr, channels, data, weights,
+                                       log_norm, blend, term);
+        if (rc) {
+            if (lowres_pool_size(pool) == 0) {
+                for (auto it = b->lowres.begin(); it != b->lowres.end(); ++it)
+                    if (it->pool == pool) {
+                        b->lowres.erase(it);
+                        break;
+                    }
+                lowres_pool_destroy(pool);
+            }
+            return rc;
+        }
+        where.pool = pool;
+        where.member = lowres_pool_size(pool) - 1;
     }
-    b->lowres.push_back(l);
+    b->lowres_of[blend].push_back(where);
+    const int32_t count = slot + 1;
+    SMI_HIP(hipMemcpy(b->extra_count + blend, &count, sizeof(int32_t), hipMemcpyHostToDevice));
     refresh_view(b);
     return SMI_OK;
 }
 
-int smi_batch_get_lowres_rendered(smi_batch *b, int32_t index, float *out) {
+int smi_batch_attach_lowres(smi_batch *b, smi_resampler *r, const int32_t *channels,
+                            const float *data, const float *weights, double log_norm) {
+    SMI_REQUIRE(b && r && channels && data && weights, "null argument");
+    SMI_REQUIRE(r->impl, "resampler already destroyed");
+    int C, n_a, n_b, Fy, Fx;
+    const bool spectral = resampler_shape(r->impl, &C, &n_a, &n_b, &Fy, &Fx);
+    return attach_lowres(b, 0, r, spectral, nullptr, nullptr, C, n_a, n_b, Fy, Fx, channels, data,
+                         weights, log_norm);
+}
+
+int smi_batch_attach_lowres_blend(smi_batch *b, int32_t blend, const float *A, const float *Pt,
+                                  int32_t C, int32_t n_a, int32_t n_b, int32_t Fy, int32_t Fx,
+                                  const int32_t *channels, const float *data,
+                                  const float *weights, double log_norm) {
+    SMI_REQUIRE(b && A && Pt && channels && data && weights, "null argument");
+    SMI_REQUIRE(C > 0 && n_a > 0 && n_b > 0 && Fy > 0 && Fx > 0, "bad sizes");
+    return attach_lowres(b, blend, nullptr, true, A, Pt, C, n_a, n_b, Fy, Fx, channels, data,
+                         weights, log_norm);
+}
+
+int smi_batch_get_lowres_rendered_blend(smi_batch *b, int32_t blend, int32_t index, float *out) {
     SMI_REQUIRE(b && out, "null argument");
-    SMI_REQUIRE(index >= 0 && index < (int)b->lowres.size(), "no such low-resolution observation");
-    return lowres_get_rendered(b->lowres[index], out, b->stream);
+    SMI_REQUIRE(blend >= 0 && blend < (int)b->lowres_of.size() && index >= 0 &&
+                    index < (int)b->lowres_of[blend].size(),
+                "no such low-resolution observation");
+    const smi_batch::LowResWhere &w = b->lowres_of[blend][index];
+    if (w.single) return lowres_get_rendered(w.single, out, b->stream);
+    return lowres_pool_get_rendered(w.pool, w.member, out, b->stream);
+}
+
+int smi_batch_get_lowres_rendered(smi_batch *b, int32_t index, float *out) {
+    return smi_batch_get_lowres_rendered_blend(b, 0, index, out);
+}
+
+int smi_lowres_pool_test(int32_t n, const float *A, const float *Pt, int32_t C, int32_t n_a,
+                         int32_t n_b, int32_t Fy, int32_t Fx, const float *models,
+                         const float *resid, float *out, float *gpad, int32_t *guard_ok) {
+    SMI_REQUIRE(A && Pt && models && resid && out && gpad && guard_ok, "null argument");
+    SMI_REQUIRE(n > 0 && C > 0 && n_a > 0 && n_b > 0 && Fy > 0 && Fx > 0, "bad sizes");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        set_error("no HIP device available");
+        return SMI_ERR_NO_DEVICE;
+    }
+    return lowres_pool_test(n, A, Pt, C, n_a, n_b, Fy, Fx, models, resid, out, gpad, guard_ok);
+}
+
+int smi_lowres_gemm_plans_test(int32_t C, int32_t Fy, int32_t Fx, int32_t n_members,
+                               int32_t adjoint, int32_t own[5], int32_t pooled[5]) {
+    SMI_REQUIRE(own && pooled, "null argument");
+    GemmPlan a, p;
+    const int rc = lowres_gemm_plans(C, Fy, Fx, n_members, adjoint, &a, &p);
+    if (rc) return rc;
+    const GemmPlan *src[2] = {&a, &p};
+    int32_t *dst[2] = {own, pooled};
+    for (int i = 0; i < 2; ++i) {
+        dst[i][0] = src[i]->tm; dst[i][1] = src[i]->tn; dst[i][2] = src[i]->bk;
+        dst[i][3] = src[i]->kslice; dst[i][4] = src[i]->n_slices;
+    }
+    return SMI_OK;
 }
 
 int smi_resampler_destroy(smi_resampler *r) {
@@ -1010,7 +1138,10 @@ int smi_batch_destroy(smi_batch *b) {
     for (auto e : b->sub_events) (void)hipEventDestroy(e);
     for (auto st : b->sub_streams) (void)hipStreamDestroy(st);
     if (b->h_round) (void)hipHostFree(b->h_round);
-    for (auto *l : b->lowres) lowres_destroy(l);
+    for (auto &u : b->lowres) {
+        lowres_destroy(u.single);
+        lowres_pool_destroy(u.pool);
+    }
     for (auto &l : b->layers)
         for (void *p : {(void *)l.data, (void *)l.weights, (void *)l.Kt, (void *)l.dw})
             if (p) (void)hipFree(p);
@@ -1019,6 +1150,7 @@ int smi_batch_destroy(smi_batch *b) {
     release_kernel_shift(b);
     if (b->Q2) (void)hipFree(b->Q2);
     if (b->extra_terms) (void)hipFree(b->extra_terms);
+    if (b->extra_count) (void)hipFree(b->extra_count);
     delete b;
     return SMI_OK;
 }
@@ -2678,16 +2810,29 @@ int smi_batch_set_stream(smi_batch *b, void *stream) {
 }
 
 // every attached low-resolution observation: rendering, loss term and (backward) gradient
-static int lowres_evaluate_all(smi_batch *b, int backward) {
-    for (auto *l : b->lowres) {
-        const int rc = lowres_evaluate(l, b->P, b->Py, b->Px, backward, b->stream);
+// (`state`: the blends whose terms are evaluated -- a blend that has stopped keeps its term,
+// its rendering and its share of Q as they are)
+static int lowres_evaluate_all(smi_batch *b, const int32_t *state, int backward) {
+    for (auto &u : b->lowres) {
+        const int rc = u.single
+                           ? lowres_evaluate(u.single, b->P, b->Py, b->Px, backward, b->stream)
+                           : lowres_pool_evaluate(u.pool, b->P, b->Py, b->Px, b->d.C, state,
+                                                  backward, b->stream);
         if (rc) return rc;
     }
     return SMI_OK;
 }
 
-static void lowres_add_all(smi_batch *b) {
-    for (auto *l : b->lowres) lowres_add_gradient(l, b->Q, b->Py, b->Px, b->stream);
+static int lowres_add_all(smi_batch *b, const int32_t *state) {
+    for (auto &u : b->lowres) {
+        if (u.single) {
+            lowres_add_gradient(u.single, b->Q, b->Py, b->Px, b->stream);
+            continue;
+        }
+        const int rc = lowres_pool_add_gradient(u.pool, b->Q, b->Py, b->Px, b->d.C, state, b->stream);
+        if (rc) return rc;
+    }
+    return SMI_OK;
 }
 
 int smi_batch_forward(smi_batch *b, float *model, float *rendered, double *logL) {
@@ -2697,7 +2842,7 @@ int smi_batch_forward(smi_batch *b, float *model, float *rendered, double *logL)
     const int nb = v.nb, C = v.C, H = v.H, W = v.W;
     const size_t n_out = (size_t)nb * C * H * W;
     launch_render(v, b->P, b->stream);
-    if ((rc = lowres_evaluate_all(b, 0))) return rc;
+    if ((rc = lowres_evaluate_all(b, v.state, 0))) return rc;
     float *tmp = nullptr;
     if (model || rendered) SMI_HIP(dev_alloc(&tmp, n_out));
     if (model) {
@@ -2727,7 +2872,7 @@ int smi_batch_forward(smi_batch *b, float *model, float *rendered, double *logL)
                                hipMemcpyDeviceToHost, b->stream));
         SMI_HIP(hipMemcpyAsync(ln.data(), b->log_norm, nb * sizeof(double), hipMemcpyDeviceToHost,
                                b->stream));
-        std::vector<double> terms(b->lowres.size(), 0.0);
+        std::vector<double> terms(b->lowres.empty() ? 0 : (size_t)nb * kMaxLowRes, 0.0);
         if (!terms.empty())
             SMI_HIP(hipMemcpyAsync(terms.data(), b->extra_terms, terms.size() * sizeof(double),
                                    hipMemcpyDeviceToHost, b->stream));
@@ -2735,7 +2880,9 @@ int smi_batch_forward(smi_batch *b, float *model, float *rendered, double *logL)
         for (int i = 0; i < nb; ++i) {
             double t = 0.0;
             for (int j = 0; j < v.n_partial; ++j) t += part[(size_t)i * v.n_partial + j];
-            for (double e : terms) t += 2.0 * e;
+            if (!terms.empty())  // (blend i's own terms, in the order they were attached)
+                for (size_t j = 0; j < b->lowres_of[i].size(); ++j)
+                    t += 2.0 * terms[(size_t)i * kMaxLowRes + j];
             logL[i] = -(ln[i] + 0.5 * t);
         }
     }
@@ -2749,7 +2896,7 @@ int smi_batch_gradient(smi_batch *b, float *g_sed, float *g_morph) {
     const BatchView v = unmasked_view(b);
     if (b->fused) {
         launch_render(v, b->P, b->stream);
-        if ((rc = lowres_evaluate_all(b, 1))) return rc;
+        if ((rc = lowres_evaluate_all(b, v.state, 1))) return rc;
         if (b->ks.stamp && (rc = kernel_shift_backward(b, v, 0, 1))) return rc;
         if ((rc = launch_fused_conv(v, b->Fy, b->Fx, b->P, b->Kt, b->d.kernel_bands,
                                     b->d.kernel_per_blend, b->Q, 0, b->dbg, b->stream)))
@@ -2757,12 +2904,12 @@ int smi_batch_gradient(smi_batch *b, float *g_sed, float *g_morph) {
         if ((rc = layers_evaluate(b, v, 1, b->stream))) return rc;
     } else {
         launch_render(v, b->P, b->stream);
-        if ((rc = lowres_evaluate_all(b, 1))) return rc;
+        if ((rc = lowres_evaluate_all(b, v.state, 1))) return rc;
         if ((rc = convolve(b, v, 0))) return rc;
         launch_residual(v, b->Q, b->P, b->stream);
         if ((rc = convolve(b, v, 1))) return rc;
     }
-    lowres_add_all(b);
+    if ((rc = lowres_add_all(b, v.state))) return rc;
     if ((rc = launch_update(v, b->Q, 0, 0.f, 0, b->g_sed, b->g_morph, 1, b->stream))) return rc;
     if ((rc = launch_point_sources(v, b->Q, 0, 0.f, 0, b->g_sed, b->g_center, 1, b->stream)))
         return rc;
@@ -2971,7 +3118,7 @@ int smi_batch_step(smi_batch *b, int32_t it0, int32_t n_iter, float e_rel, int32
         if (ev) SMI_HIP(hipEventRecord(ev[0], b->stream));
         if (b->fused) {
             if (!no_cube) launch_render(v, b->P, b->stream);
-            if ((rc = lowres_evaluate_all(b, 1))) return rc;
+            if ((rc = lowres_evaluate_all(b, v.state, 1))) return rc;
             if (b->ks.stamp && (rc = kernel_shift_backward(b, v, it, 0))) return rc;
             // conv + residual/loss + conv^T in one LDS-resident kernel
             if (ev) SMI_HIP(hipEventRecord(ev[1], b->stream));
@@ -2985,7 +3132,7 @@ int smi_batch_step(smi_batch *b, int32_t it0, int32_t n_iter, float e_rel, int32
             if (ev) SMI_HIP(hipEventRecord(ev[4], b->stream));
         } else {
             launch_render(v, b->P, b->stream);
-            if ((rc = lowres_evaluate_all(b, 1))) return rc;
+            if ((rc = lowres_evaluate_all(b, v.state, 1))) return rc;
             if (ev) SMI_HIP(hipEventRecord(ev[1], b->stream));
             if ((rc = convolve(b, v, 0))) return rc;
             if (ev) SMI_HIP(hipEventRecord(ev[2], b->stream));
@@ -2995,7 +3142,7 @@ int smi_batch_step(smi_batch *b, int32_t it0, int32_t n_iter, float e_rel, int32
             if ((rc = convolve(b, v, 1))) return rc;
             if (ev) SMI_HIP(hipEventRecord(ev[4], b->stream));
         }
-        lowres_add_all(b);
+        if ((rc = lowres_add_all(b, v.state))) return rc;
         if ((rc = launch_shift_backward(v, b->Q, it, nullptr, 0, b->stream))) return rc;
         // (before the spectra move: the coefficient gradient belongs to this iteration's spectrum)
         b->star.b1 = b->b1_f64;

@@ -287,9 +287,10 @@ struct BatchView {
     int32_t scheme;              // SMI_SCHEME_*; FISTA keeps z in m_sed / m_morph
     const float *c_fista_step;
     double *fista_t;             // [n_comp][2]
-    // further observations of blend 0 (resample.hip): log_norm + chi^2 / 2 of each
+    // low-resolution observations (resample.hip): log_norm + chi^2 / 2 of observation i of
+    // blend b at extra_term[b * kMaxLowRes + i], i < extra_count[b] (both nullptr: none)
     const double *extra_term;
-    int32_t n_extra;
+    const int32_t *extra_count;
     // sub-range launches (one stream per range of blends): the grids cover `nb` blends /
     // `n_comp` components starting at these offsets; all arrays stay whole-batch
     int32_t blend0, comp0;
@@ -490,6 +491,46 @@ int gemm_plan(int M, int N, int K, int n_batch, size_t scratch_elems, GemmPlan *
 int gemm_test(const float *A, int64_t strideA, const float *B, int64_t strideB, float *C,
               int64_t strideC, int n_batch, int M, int N, int K, size_t scratch_elems,
               GemmPlan *plan, int32_t *guard_ok);
+int gemm_plan_sliced(int M, int N, int K, int n_batch, int kslice, int n_slices, GemmPlan *p);
+// the two transforms of the spectral path of a resampler with C bands (adjoint: the one back):
+// `own`, the plan the resampler's own launch gets, and `pooled`, that of n_members such
+// resamplers in one launch -- the same slices (host only; test entry)
+int lowres_gemm_plans(int C, int Fy, int Fx, int n_members, int adjoint, GemmPlan *own,
+                      GemmPlan *pooled);
+constexpr int kMaxLowRes = 8;  // low-resolution observations per blend
+// one observation of a LowResPool, as the kernels read it (device table)
+struct LowResMember {
+    const float2 *E, *beta;       // its operators: [C][n_a][Fy][Kx], [n_b][Kx]
+    const float *data, *weights;  // [C][n_a][n_b]
+    const int32_t *channels;      // [C] model channels of its bands
+    double *term;                 // its slot of the batch's extra loss terms
+    double log_norm;
+    int32_t blend, unused;
+};
+// The observations of one shape class (C, n_a, n_b, Fy, Fx) attached to blends of one batch,
+// evaluated together on the spectral path: a fixed number of launches whatever their number.
+struct LowResPool;
+int lowres_pool_create(int C, int n_a, int n_b, int Fy, int Fx, int H, int W, LowResPool **out);
+void lowres_pool_destroy(LowResPool *p);
+bool lowres_pool_matches(const LowResPool *p, int C, int n_a, int n_b, int Fy, int Fx);
+int lowres_pool_size(const LowResPool *p);
+// a member from host operators A [C][n_a][Fy Fx] and Pt [Fx][Fx n_b] (must be circulant), or
+// from the tables of a resampler on the spectral path (A == nullptr)
+int lowres_pool_add(LowResPool *p, const float *A, const float *Pt, const Resampler *from,
+                    const int32_t *channels, const float *data, const float *weights,
+                    double log_norm, int blend, double *term_slot);
+int lowres_pool_evaluate(LowResPool *p, const float *P, int Py, int Px, int Cm,
+                         const int32_t *state, int backward, hipStream_t s);
+int lowres_pool_add_gradient(LowResPool *p, float *Q, int Py, int Px, int Cm,
+                             const int32_t *state, hipStream_t s);
+int lowres_pool_get_rendered(LowResPool *p, int member, float *out, hipStream_t s);
+// (test entry) n resamplers of one class through the pooled chain on host buffers: models
+// [n][C][Fy][Fx] -> out [n][C][n_a][n_b], resid [n][C][n_a][n_b] -> gpad [n][C][Fy][Fx];
+// *guard_ok: the guard bands around the pooled outputs came back untouched
+int lowres_pool_test(int n, const float *A, const float *Pt, int C, int n_a, int n_b, int Fy,
+                     int Fx, const float *models, const float *resid, float *out, float *gpad,
+                     int32_t *guard_ok);
+bool resampler_shape(const Resampler *r, int *C, int *n_a, int *n_b, int *Fy, int *Fx);
 struct LowRes;
 int lowres_create(Resampler *r, const int32_t *channels, const float *data, const float *weights,
                   double log_norm, int H, int W, double *term_slot, LowRes **out);

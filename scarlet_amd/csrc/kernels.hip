@@ -234,7 +234,8 @@ __device__ __forceinline__ void finalize_blend(const BatchView &v, int b, int it
     t = wave_sum(t);
     if (lane == 0) {
         double loss = v.log_norm[b] + 0.5 * t;
-        for (int i = 0; i < v.n_extra; ++i) loss += v.extra_term[i];
+        if (v.extra_count)  // blend b's own low-resolution terms, in the order of attachment
+            for (int i = 0; i < v.extra_count[b]; ++i) loss += v.extra_term[b * kMaxLowRes + i];
         const int n = v.n_loss[b];
         const double prev = v.last_loss[b];
         if (n < v.hist_cap) v.loss_hist[(int64_t)b * v.hist_cap + n] = loss;

@@ -243,14 +243,37 @@ int gemm_plan(int M, int N, int K, int n_batch, size_t scratch_elems, GemmPlan *
     return SMI_OK;
 }
 
+// gemm_plan with the slicing given: the tile variant and the k depth follow the number of
+// products in the launch -- neither changes the order in which the terms of an output are
+// added -- while the slices, which do (float32 inside, double across), are the caller's: those
+// gemm_plan gives ONE member of the launch by itself.
+int gemm_plan_sliced(int M, int N, int K, int n_batch, int kslice, int n_slices, GemmPlan *p) {
+    SMI_REQUIRE(M > 0 && N > 0 && K > 0 && n_batch > 0 && p, "gemm: bad sizes");
+    SMI_REQUIRE(kslice > 0 && kslice % kBK == 0 && n_slices == (K + kslice - 1) / kslice,
+                "gemm: the slices do not cover K");
+    int tm = M <= 96 ? 1 : 2, tn = N <= 96 ? 1 : 2;
+    auto n_tiles = [&](int a, int b) {
+        return (int64_t)((M + 64 * a - 1) / (64 * a)) * ((N + 64 * b - 1) / (64 * b)) * n_batch;
+    };
+    const bool few = n_tiles(tm, tn) * n_slices < 200;
+    if (few) tm = tn = 1;
+    p->tm = tm;
+    p->tn = tn;
+    p->bk = few ? 2 * kBK : kBK;
+    p->kslice = kslice;
+    p->n_slices = n_slices;
+    SMI_REQUIRE((int64_t)n_slices * n_batch <= 65535,
+                "gemm: slices x batch exceed the grid's z limit");
+    return SMI_OK;
+}
+
 namespace {
 
-int gemm(const float *A, int64_t strideA, const float *B, int64_t strideB, float *C,
-         int64_t strideC, int n_batch, double *scratch, size_t scratch_elems, int M, int N, int K,
-         hipStream_t s) {
-    GemmPlan p;
-    const int rc = gemm_plan(M, N, K, n_batch, scratch_elems, &p);
-    if (rc) return rc;
+// the launch of a plan: n_batch products, partials of the slices in `scratch` (n_slices x
+// n_batch x M x N doubles when n_slices > 1)
+int gemm_launch(const GemmPlan &p, const float *A, int64_t strideA, const float *B,
+                int64_t strideB, float *C, int64_t strideC, int n_batch, double *scratch, int M,
+                int N, int K, hipStream_t s) {
     const int bm = 64 * p.tm, bn = 64 * p.tn, kslice = p.kslice, n_slices = p.n_slices;
     const size_t MN = (size_t)M * N;
     const dim3 grid((N + bn - 1) / bn, (M + bm - 1) / bm, n_slices * n_batch);
@@ -267,6 +290,38 @@ int gemm(const float *A, int64_t strideA, const float *B, int64_t strideB, float
     if (n_slices > 1)
         hipLaunchKernelGGL(reduce_slices_kernel, dim3((unsigned)((MN + 63) / 64), n_batch),
                            dim3(1024), 0, s, scratch, C, strideC, (int64_t)MN, n_slices);
+    return SMI_OK;
+}
+
+int gemm(const float *A, int64_t strideA, const float *B, int64_t strideB, float *C,
+         int64_t strideC, int n_batch, double *scratch, size_t scratch_elems, int M, int N, int K,
+         hipStream_t s) {
+    GemmPlan p;
+    const int rc = gemm_plan(M, N, K, n_batch, scratch_elems, &p);
+    if (rc) return rc;
+    return gemm_launch(p, A, strideA, B, strideB, C, strideC, n_batch, scratch, M, N, K, s);
+}
+
+// products of one launch of gemm_pooled: slices x products within the grid's z limit (and the
+// reduction's y limit)
+int gemm_pooled_chunk(int n_slices) { return std::max(1, 65535 / n_slices); }
+
+// n_batch products whose slicing is given (gemm_plan_sliced): cut into launches of at most
+// gemm_pooled_chunk products, which share `scratch` (n_slices x chunk x M x N doubles) one
+// after the other on the stream.  Needs strideB == 0 or whole products per batch entry.
+int gemm_pooled(int kslice, int n_slices, const float *A, int64_t strideA, const float *B,
+                float *C, int64_t strideC, int n_batch, double *scratch, int M, int N, int K,
+                hipStream_t s) {
+    const int chunk = gemm_pooled_chunk(n_slices);
+    for (int b0 = 0; b0 < n_batch; b0 += chunk) {
+        const int nb = std::min(chunk, n_batch - b0);
+        GemmPlan p;
+        int rc = gemm_plan_sliced(M, N, K, nb, kslice, n_slices, &p);
+        if (rc) return rc;
+        rc = gemm_launch(p, A + b0 * strideA, strideA, B, 0, C + b0 * strideC, strideC, nb,
+                         scratch, M, N, K, s);
+        if (rc) return rc;
+    }
     return SMI_OK;
 }
 
@@ -346,6 +401,14 @@ __global__ __launch_bounds__(256) void row_dft_kernel(const float *in, const dou
     }
 }
 
+// The kernels of the spectral path and of the low-resolution term take a blend dimension: with
+// a member table `tab` (LowResMember, common.h) blockIdx.z -- blockIdx.x / y where noted -- is
+// the member m of a pool of observations of one shape class; its operators E and beta come
+// from the table, its work arrays are slice m of the pooled ones, and a member whose blend has
+// stopped (state >= 2) is skipped: nothing of it is written again.  Without a table the
+// kernels serve one resampler as before.  The order in which every sum is formed is the same
+// in both uses, so a member gets the bits of its own resampler.
+
 // One workgroup per (low-resolution row a, band c): G[k] = sum_y conj(E[c][a][y][k]) Mh[c][y][k]
 // (wavefront w takes the rows y = w, w + 16, ..., four loads of E in flight per lane; lanes
 // along k, so a wavefront reads 512 contiguous bytes of E per row), the sixteen partial sums
@@ -353,8 +416,18 @@ __global__ __launch_bounds__(256) void row_dft_kernel(const float *in, const dou
 // per column b.  E is read exactly once per rendering.
 __global__ __launch_bounds__(1024) void spectral_forward_kernel(const float2 *E, const float2 *Mh,
                                                                 const float2 *beta, float *out,
-                                                                int n_a, int n_b, int Fy, int Kx) {
+                                                                int n_a, int n_b, int Fy, int Kx,
+                                                                const LowResMember *tab,
+                                                                const int32_t *state) {
     extern __shared__ double2 fwd_sm[];
+    if (tab) {
+        const LowResMember mb = tab[blockIdx.z];
+        if (state[mb.blend] >= 2) return;
+        E = mb.E;
+        beta = mb.beta;
+        Mh += (int64_t)blockIdx.z * gridDim.y * Fy * Kx;
+        out += (int64_t)blockIdx.z * gridDim.y * n_a * n_b;
+    }
     double2 *red = fwd_sm;         // [16][64]
     double2 *G = fwd_sm + 16 * 64;  // [Kx]
     const int a = blockIdx.x, c = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -412,10 +485,20 @@ __global__ __launch_bounds__(1024) void spectral_forward_kernel(const float2 *E,
     }
 }
 
-// Gbar[ca][k] = sum_b resid[ca][b] conj(beta[b][k]); one workgroup per (band, row a)
+// Gbar[ca][k] = sum_b resid[ca][b] conj(beta[b][k]); one workgroup per (band, row a) and
+// member (blockIdx.y)
 __global__ __launch_bounds__(256) void spectral_gbar_kernel(const float *resid, const float2 *beta,
-                                                            float2 *Gbar, int n_b, int Kx) {
+                                                            float2 *Gbar, int n_b, int Kx,
+                                                            const LowResMember *tab,
+                                                            const int32_t *state) {
     extern __shared__ float gbar_sm[];
+    if (tab) {
+        const LowResMember mb = tab[blockIdx.y];
+        if (state[mb.blend] >= 2) return;
+        beta = mb.beta;
+        resid += (int64_t)blockIdx.y * gridDim.x * n_b;
+        Gbar += (int64_t)blockIdx.y * gridDim.x * Kx;
+    }
     const int64_t ca = blockIdx.x;
     for (int b = threadIdx.x; b < n_b; b += 256) gbar_sm[b] = resid[ca * n_b + b];
     __syncthreads();
@@ -435,8 +518,16 @@ __global__ __launch_bounds__(256) void spectral_gbar_kernel(const float *resid, 
 // (model row y, band c), wavefront w takes a = w, w + 4, ...
 __global__ __launch_bounds__(256) void spectral_adjoint_kernel(const float2 *E, const float2 *Gbar,
                                                                float2 *Mbar, int n_a, int Fy,
-                                                               int Kx) {
+                                                               int Kx, const LowResMember *tab,
+                                                               const int32_t *state) {
     __shared__ double2 red[4][64];
+    if (tab) {
+        const LowResMember mb = tab[blockIdx.z];
+        if (state[mb.blend] >= 2) return;
+        E = mb.E;
+        Gbar += (int64_t)blockIdx.z * gridDim.y * n_a * Kx;
+        Mbar += (int64_t)blockIdx.z * gridDim.y * Fy * Kx;
+    }
     const int y = blockIdx.x, c = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const float2 *Ec = E + ((int64_t)c * n_a * Fy + y) * Kx;
     const float2 *Gc = Gbar + (int64_t)c * n_a * Kx;
@@ -546,19 +637,37 @@ int build_dense(Resampler *r) {
     return SMI_OK;
 }
 
+// doubles for the slice partials of the two transforms of a resampler with C bands
+size_t spectral_scratch_elems(int C, int Fy, int Fx) {
+    const int Kx = Fx / 2 + 1;
+    const size_t slices = (size_t)(std::max(Fx, 2 * Kx) + kSliceTerms - 1) / kSliceTerms + 1;
+    return (size_t)C * Fy * std::max(Fx, 2 * Kx) * slices;
+}
+
+// the transform tables of a row of Fx pixels: twiddles (float64) and the two transforms along
+// x as matrices, Wx [Fx][2 Kx] (cos, -sin interleaved) and its transpose
+void transform_tables(int Fx, std::vector<double2> *tw, std::vector<float> *Wx,
+                      std::vector<float> *WxT) {
+    const int Kx = Fx / 2 + 1;
+    const double step = 2.0 * 3.14159265358979323846 / (double)Fx;
+    tw->resize(Fx);
+    for (int j = 0; j < Fx; ++j) (*tw)[j] = make_double2(std::cos(step * j), -std::sin(step * j));
+    Wx->resize((size_t)Fx * 2 * Kx);
+    WxT->resize((size_t)2 * Kx * Fx);
+    for (int x = 0; x < Fx; ++x)
+        for (int k = 0; k < Kx; ++k) {
+            const double2 w = (*tw)[(int)(((int64_t)k * x) % Fx)];
+            (*Wx)[(size_t)x * 2 * Kx + 2 * k] = (*WxT)[(size_t)(2 * k) * Fx + x] = (float)w.x;
+            (*Wx)[(size_t)x * 2 * Kx + 2 * k + 1] = (*WxT)[(size_t)(2 * k + 1) * Fx + x] = (float)w.y;
+        }
+}
+
 int build_spectral(Resampler *r, const float *Pt_host) {
     const int Fx = r->Fx, Fy = r->Fy, Kx = Fx / 2 + 1, n_a = r->n_a, n_b = r->n_b, C = r->C;
     r->Kx = Kx;
-    const double step = 2.0 * 3.14159265358979323846 / (double)Fx;
-    std::vector<double2> tw(Fx);
-    for (int j = 0; j < Fx; ++j) tw[j] = make_double2(std::cos(step * j), -std::sin(step * j));
-    std::vector<float> Wx((size_t)Fx * 2 * Kx), WxT((size_t)2 * Kx * Fx), S((size_t)n_b * Fx);
-    for (int x = 0; x < Fx; ++x)
-        for (int k = 0; k < Kx; ++k) {
-            const double2 w = tw[(int)(((int64_t)k * x) % Fx)];
-            Wx[(size_t)x * 2 * Kx + 2 * k] = WxT[(size_t)(2 * k) * Fx + x] = (float)w.x;
-            Wx[(size_t)x * 2 * Kx + 2 * k + 1] = WxT[(size_t)(2 * k + 1) * Fx + x] = (float)w.y;
-        }
+    std::vector<double2> tw;
+    std::vector<float> Wx, WxT, S((size_t)n_b * Fx);
+    transform_tables(Fx, &tw, &Wx, &WxT);
     for (int b = 0; b < n_b; ++b)  // s_b[x] = P[x' = 0][x][b]
         for (int x = 0; x < Fx; ++x) S[(size_t)b * Fx + x] = Pt_host[(size_t)x * n_b + b];
     double2 *d_tw = nullptr;
@@ -571,8 +680,7 @@ int build_spectral(Resampler *r, const float *Pt_host) {
     SMI_HIP(hipMalloc((void **)&r->WxT, WxT.size() * sizeof(float)));
     SMI_HIP(hipMalloc((void **)&r->Mh, (size_t)C * Fy * Kx * sizeof(float2)));
     SMI_HIP(hipMalloc((void **)&r->Gbar, (size_t)C * n_a * Kx * sizeof(float2)));
-    const size_t slices = (size_t)(std::max(Fx, 2 * Kx) + kSliceTerms - 1) / kSliceTerms + 1;
-    r->sscratch_elems = (size_t)C * Fy * std::max(Fx, 2 * Kx) * slices;
+    r->sscratch_elems = spectral_scratch_elems(C, Fy, Fx);
     SMI_HIP(hipMalloc((void **)&r->sscratch, r->sscratch_elems * sizeof(double)));
     SMI_HIP(hipMemcpy(d_tw, tw.data(), Fx * sizeof(double2), hipMemcpyHostToDevice));
     SMI_HIP(hipMemcpy(d_S, S.data(), S.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -650,7 +758,7 @@ static int resampler_forward(Resampler *r, hipStream_t s) {
         if (rc) return rc;
         const size_t lds = (size_t)(16 * 64 + Kx) * sizeof(double2);
         hipLaunchKernelGGL(spectral_forward_kernel, dim3(r->n_a, r->C), dim3(1024), lds, s, r->E,
-                           r->Mh, r->beta, r->out, r->n_a, r->n_b, r->Fy, Kx);
+                           r->Mh, r->beta, r->out, r->n_a, r->n_b, r->Fy, Kx, nullptr, nullptr);
         return SMI_OK;
     }
     int rc = gemm(r->model, plane, r->Pt, 0, r->B, plane * r->n_b, r->C, r->scratch,
@@ -667,9 +775,10 @@ static int resampler_adjoint(Resampler *r, const float *resid, float *gpad, hipS
     if (r->path == 1) {
         const int Kx = r->Kx;
         hipLaunchKernelGGL(spectral_gbar_kernel, dim3(r->C * r->n_a), dim3(256),
-                           r->n_b * sizeof(float), s, resid, r->beta, r->Gbar, r->n_b, Kx);
+                           r->n_b * sizeof(float), s, resid, r->beta, r->Gbar, r->n_b, Kx, nullptr,
+                           nullptr);
         hipLaunchKernelGGL(spectral_adjoint_kernel, dim3(r->Fy, r->C), dim3(256), 0, s, r->E,
-                           r->Gbar, r->Mh, r->n_a, r->Fy, Kx);
+                           r->Gbar, r->Mh, r->n_a, r->Fy, Kx, nullptr, nullptr);
         return gemm(reinterpret_cast<float *>(r->Mh), (int64_t)r->Fy * 2 * Kx, r->WxT, 0, gpad,
                     plane, r->C, r->sscratch, r->sscratch_elems, r->Fy, r->Fx, 2 * Kx, s);
     }
@@ -807,13 +916,23 @@ int resampler_time(Resampler *r, int n_rep, double *ms_per_render) {
 //   T[(y, x), b] = sum_a A[a, (y, x)] r[a, b]           (F_y F_x x n_a) . (n_a x n_b)
 //   g[y, x']     = sum_{(x, b)} T[y, (x, b)] P[(x, b), x']   (F_y x F_x n_b) . (F_x n_b x F_x)
 //
-// One blend only: every blend of a batch would need its own operators.
+// LowRes is the term of a batch of one blend on either path of its resampler; LowResPool
+// (below) holds the observations of one shape class of a batch of any size, each with its own
+// operators, on the spectral path.
 // ---------------------------------------------------------------------------------------
 namespace {
 
 // centred zero padding of the observed bands of the model cube (fft._pad, fft.py:82-113)
 __global__ void lowres_pad_kernel(const float *P, int Py, int Px, const int32_t *channels, int H,
-                                  int W, int y0, int x0, float *padded, int Fy, int Fx) {
+                                  int W, int y0, int x0, float *padded, int Fy, int Fx,
+                                  const LowResMember *tab, const int32_t *state, int Cm) {
+    if (tab) {  // member blockIdx.z: the cube of its blend, slice m of the padded pool
+        const LowResMember mb = tab[blockIdx.z];
+        if (state[mb.blend] >= 2) return;
+        P += (int64_t)mb.blend * Cm * Py * Px;
+        channels = mb.channels;
+        padded += (int64_t)blockIdx.z * gridDim.y * Fy * Fx;
+    }
     const int c = blockIdx.y;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Fy * Fx) return;
@@ -827,8 +946,20 @@ __global__ __launch_bounds__(1024) void lowres_residual_kernel(const float *rend
                                                                const float *data,
                                                                const float *weights, float *resid,
                                                                int n, double log_norm,
-                                                               double *term) {
+                                                               double *term,
+                                                               const LowResMember *tab,
+                                                               const int32_t *state) {
     __shared__ double part[16];
+    if (tab) {  // one workgroup per member: the slot of its blend's term
+        const LowResMember mb = tab[blockIdx.x];
+        if (state[mb.blend] >= 2) return;
+        rendered += (int64_t)blockIdx.x * n;
+        resid += (int64_t)blockIdx.x * n;
+        data = mb.data;
+        weights = mb.weights;
+        log_norm = mb.log_norm;
+        term = mb.term;
+    }
     double t = 0.0;
     for (int i = threadIdx.x; i < n; i += 1024) {
         const float d = rendered[i] - data[i], w = weights[i];
@@ -847,7 +978,15 @@ __global__ __launch_bounds__(1024) void lowres_residual_kernel(const float *rend
 
 __global__ void lowres_add_kernel(const float *gpad, int Fy, int Fx, int y0, int x0,
                                   const int32_t *channels, int H, int W, float *Q, int Py,
-                                  int Px) {
+                                  int Px, const LowResMember *tab, const int32_t *state,
+                                  int Cm) {
+    if (tab) {
+        const LowResMember mb = tab[blockIdx.z];
+        if (state[mb.blend] >= 2) return;
+        Q += (int64_t)mb.blend * Cm * Py * Px;
+        channels = mb.channels;
+        gpad += (int64_t)blockIdx.z * gridDim.y * Fy * Fx;
+    }
     const int c = blockIdx.y;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= H * W) return;
@@ -903,11 +1042,12 @@ int lowres_evaluate(LowRes *l, const float *P, int Py, int Px, int backward, hip
     Resampler *r = l->r;
     const int plane = r->Fy * r->Fx, n = r->C * r->n_a * r->n_b;
     hipLaunchKernelGGL(lowres_pad_kernel, dim3((plane + 255) / 256, r->C), dim3(256), 0, s, P, Py,
-                       Px, l->channels, l->H, l->W, l->y0, l->x0, r->model, r->Fy, r->Fx);
+                       Px, l->channels, l->H, l->W, l->y0, l->x0, r->model, r->Fy, r->Fx, nullptr,
+                       nullptr, 0);
     int rc = resampler_forward(r, s);
     if (rc) return rc;
     hipLaunchKernelGGL(lowres_residual_kernel, dim3(1), dim3(1024), 0, s, r->out, l->data,
-                       l->weights, l->resid, n, l->log_norm, l->term);
+                       l->weights, l->resid, n, l->log_norm, l->term, nullptr, nullptr);
     if (!backward) return SMI_OK;
     return resampler_adjoint(r, l->resid, l->gpad, s);
 }
@@ -915,7 +1055,8 @@ int lowres_evaluate(LowRes *l, const float *P, int Py, int Px, int backward, hip
 void lowres_add_gradient(LowRes *l, float *Q, int Py, int Px, hipStream_t s) {
     Resampler *r = l->r;
     hipLaunchKernelGGL(lowres_add_kernel, dim3((l->H * l->W + 255) / 256, r->C), dim3(256), 0, s,
-                       l->gpad, r->Fy, r->Fx, l->y0, l->x0, l->channels, l->H, l->W, Q, Py, Px);
+                       l->gpad, r->Fy, r->Fx, l->y0, l->x0, l->channels, l->H, l->W, Q, Py, Px,
+                       nullptr, nullptr, 0);
 }
 
 int lowres_get_rendered(LowRes *l, float *out, hipStream_t s) {
@@ -924,6 +1065,332 @@ int lowres_get_rendered(LowRes *l, float *out, hipStream_t s) {
                            hipMemcpyDeviceToHost, s));
     SMI_HIP(hipStreamSynchronize(s));
     return SMI_OK;
+}
+
+bool resampler_shape(const Resampler *r, int *C, int *n_a, int *n_b, int *Fy, int *Fx) {
+    *C = r->C; *n_a = r->n_a; *n_b = r->n_b; *Fy = r->Fy; *Fx = r->Fx;
+    return r->path == 1;
+}
+
+// ---------------------------------------------------------------------------------------
+// The low-resolution terms of a batch of blends.  Observations of one shape class (C, n_a,
+// n_b, Fy, Fx) form a pool: every member owns its operators E and beta (a device table of
+// pointers, LowResMember) and slice m of the pooled work arrays, and the chain above runs
+// once for all of them -- pad, transform (one batched product over members x bands),
+// spectral_forward over (a, band, member), one residual workgroup per member, gbar, adjoint,
+// the transform back and the add into the member's blend of Q: nine launches per iteration
+// whatever the number of blends.  The two batched products take the slices the member's own
+// resampler gets (gemm_plan for its C bands and its own scratch), so every sum is formed in
+// the order of the single fit.  A member holds neither A nor Pt on the device: E and beta are
+// made from the host operators when it is added.
+// ---------------------------------------------------------------------------------------
+constexpr size_t kPoolGuard = 256;  // guard floats around the pooled outputs (lowres_pool_test)
+
+struct LowResPool {
+    int C = 0, n_a = 0, n_b = 0, Fy = 0, Fx = 0, Kx = 0;
+    int H = 0, W = 0, y0 = 0, x0 = 0;
+    int kslice_f = 0, nsl_f = 0, kslice_b = 0, nsl_b = 0;  // the member's own slicing
+    struct Owned {
+        float2 *E = nullptr, *beta = nullptr;
+        float *data = nullptr, *weights = nullptr;
+        int32_t *channels = nullptr;
+    };
+    std::vector<Owned> owned;
+    std::vector<LowResMember> members;  // host copy of the table
+    double2 *tw = nullptr;
+    float *Wx = nullptr, *WxT = nullptr;
+    // pooled work arrays of `cap` members (made by lowres_pool_ready)
+    int cap = 0;
+    bool dirty = true;
+    LowResMember *table = nullptr;
+    float *model = nullptr;   // [n][C][Fy][Fx]
+    float *out = nullptr;     // kPoolGuard + [n][C][n_a][n_b] + kPoolGuard
+    float *resid = nullptr;   // [n][C][n_a][n_b]
+    float *gpad = nullptr;    // kPoolGuard + [n][C][Fy][Fx] + kPoolGuard
+    float2 *Mh = nullptr;     // [n][C][Fy][Kx]
+    float2 *Gbar = nullptr;   // [n][C][n_a][Kx]
+    double *scratch = nullptr;
+};
+
+int lowres_gemm_plans(int C, int Fy, int Fx, int n_members, int adjoint, GemmPlan *own,
+                      GemmPlan *pooled) {
+    SMI_REQUIRE(C > 0 && Fy > 0 && Fx > 0 && n_members > 0 && own && pooled, "bad argument");
+    const int Kx = Fx / 2 + 1;
+    const int N = adjoint ? Fx : 2 * Kx, K = adjoint ? 2 * Kx : Fx;
+    int rc = gemm_plan(Fy, N, K, C, spectral_scratch_elems(C, Fy, Fx), own);
+    if (rc) return rc;
+    const int64_t chunk = gemm_pooled_chunk(own->n_slices);
+    return gemm_plan_sliced(Fy, N, K, (int)std::min<int64_t>(chunk, (int64_t)n_members * C),
+                            own->kslice, own->n_slices, pooled);
+}
+
+int lowres_pool_create(int C, int n_a, int n_b, int Fy, int Fx, int H, int W, LowResPool **out) {
+    SMI_REQUIRE(C > 0 && n_a > 0 && n_b > 0 && Fy > 0 && Fx > 0, "bad sizes");
+    SMI_REQUIRE(Fy >= H && Fx >= W, "resampler FFT shape smaller than the model frame");
+    SMI_REQUIRE(Fx <= 2048, "rows too long for the transform tables");
+    auto *p = new LowResPool;
+    *out = p;
+    p->C = C; p->n_a = n_a; p->n_b = n_b; p->Fy = Fy; p->Fx = Fx; p->Kx = Fx / 2 + 1;
+    p->H = H; p->W = W;
+    p->y0 = (Fy - H + 1) / 2;
+    p->x0 = (Fx - W + 1) / 2;
+    GemmPlan own, pooled;
+    int rc = lowres_gemm_plans(C, Fy, Fx, 1, 0, &own, &pooled);
+    if (rc) return rc;
+    p->kslice_f = own.kslice; p->nsl_f = own.n_slices;
+    if ((rc = lowres_gemm_plans(C, Fy, Fx, 1, 1, &own, &pooled))) return rc;
+    p->kslice_b = own.kslice; p->nsl_b = own.n_slices;
+    std::vector<double2> tw;
+    std::vector<float> Wx, WxT;
+    transform_tables(Fx, &tw, &Wx, &WxT);
+    SMI_HIP(hipMalloc((void **)&p->tw, Fx * sizeof(double2)));
+    SMI_HIP(hipMalloc((void **)&p->Wx, Wx.size() * sizeof(float)));
+    SMI_HIP(hipMalloc((void **)&p->WxT, WxT.size() * sizeof(float)));
+    SMI_HIP(hipMemcpy(p->tw, tw.data(), Fx * sizeof(double2), hipMemcpyHostToDevice));
+    SMI_HIP(hipMemcpy(p->Wx, Wx.data(), Wx.size() * sizeof(float), hipMemcpyHostToDevice));
+    SMI_HIP(hipMemcpy(p->WxT, WxT.data(), WxT.size() * sizeof(float), hipMemcpyHostToDevice));
+    return SMI_OK;
+}
+
+static void pool_free_work(LowResPool *p) {
+    for (void *q : {(void *)p->table, (void *)p->model, (void *)p->out, (void *)p->resid,
+                    (void *)p->gpad, (void *)p->Mh, (void *)p->Gbar, (void *)p->scratch})
+        if (q) (void)hipFree(q);
+    p->table = nullptr; p->model = p->out = p->resid = p->gpad = nullptr;
+    p->Mh = p->Gbar = nullptr; p->scratch = nullptr;
+    p->cap = 0;
+}
+
+void lowres_pool_destroy(LowResPool *p) {
+    if (!p) return;
+    pool_free_work(p);
+    for (auto &o : p->owned)
+        for (void *q : {(void *)o.E, (void *)o.beta, (void *)o.data, (void *)o.weights,
+                        (void *)o.channels})
+            if (q) (void)hipFree(q);
+    for (void *q : {(void *)p->tw, (void *)p->Wx, (void *)p->WxT})
+        if (q) (void)hipFree(q);
+    delete p;
+}
+
+bool lowres_pool_matches(const LowResPool *p, int C, int n_a, int n_b, int Fy, int Fx) {
+    return p->C == C && p->n_a == n_a && p->n_b == n_b && p->Fy == Fy && p->Fx == Fx;
+}
+
+int lowres_pool_size(const LowResPool *p) { return (int)p->members.size(); }
+
+int lowres_pool_add(LowResPool *p, const float *A, const float *Pt, const Resampler *from,
+                    const int32_t *channels, const float *data, const float *weights,
+                    double log_norm, int blend, double *term_slot) {
+    const int C = p->C, n_a = p->n_a, n_b = p->n_b, Fy = p->Fy, Fx = p->Fx, Kx = p->Kx;
+    SMI_REQUIRE((A && Pt) || from, "no operators");
+    SMI_REQUIRE(p->members.size() < 65535, "too many observations of one class");
+    const size_t nE = (size_t)C * n_a * Fy * Kx, nB = (size_t)n_b * Kx;
+    const size_t n = (size_t)C * n_a * n_b;
+    p->owned.emplace_back();
+    LowResPool::Owned &o = p->owned.back();
+    float *d_A = nullptr, *d_S = nullptr;
+    auto run = [&]() -> int {
+        SMI_HIP(hipMalloc((void **)&o.E, nE * sizeof(float2)));
+        SMI_HIP(hipMalloc((void **)&o.beta, nB * sizeof(float2)));
+        if (A) {
+            SMI_REQUIRE(circulant_along_x(Pt, Fx, n_b),
+                        "the shift operator is not circulant: a low-resolution observation on "
+                        "the dense path is fitted in a batch of its own");
+            std::vector<float> S((size_t)n_b * Fx);
+            for (int b = 0; b < n_b; ++b)  // s_b[x] = P[x' = 0][x][b]
+                for (int x = 0; x < Fx; ++x) S[(size_t)b * Fx + x] = Pt[(size_t)x * n_b + b];
+            const size_t nA = (size_t)C * n_a * Fy * Fx;
+            SMI_HIP(hipMalloc((void **)&d_A, nA * sizeof(float)));
+            SMI_HIP(hipMalloc((void **)&d_S, S.size() * sizeof(float)));
+            SMI_HIP(hipMemcpy(d_A, A, nA * sizeof(float), hipMemcpyHostToDevice));
+            SMI_HIP(hipMemcpy(d_S, S.data(), S.size() * sizeof(float), hipMemcpyHostToDevice));
+            const size_t lds = (size_t)((Fx + 1) & ~1) * sizeof(double) + (size_t)Fx * sizeof(double2);
+            hipLaunchKernelGGL(row_dft_kernel, dim3((unsigned)((size_t)C * n_a * Fy)), dim3(256),
+                               lds, nullptr, d_A, p->tw, o.E, Fx, Kx, 0);
+            hipLaunchKernelGGL(row_dft_kernel, dim3(n_b), dim3(256), lds, nullptr, d_S, p->tw,
+                               o.beta, Fx, Kx, 1);
+            SMI_HIP(hipGetLastError());
+            SMI_HIP(hipDeviceSynchronize());
+        } else {
+            SMI_REQUIRE(from->spectral && lowres_pool_matches(p, from->C, from->n_a, from->n_b,
+                                                              from->Fy, from->Fx),
+                        "the resampler has no spectral tables of this class");
+            SMI_HIP(hipMemcpy(o.E, from->E, nE * sizeof(float2), hipMemcpyDefault));
+            SMI_HIP(hipMemcpy(o.beta, from->beta, nB * sizeof(float2), hipMemcpyDefault));
+        }
+        if (data) {
+            SMI_HIP(hipMalloc((void **)&o.channels, C * sizeof(int32_t)));
+            SMI_HIP(hipMalloc((void **)&o.data, n * sizeof(float)));
+            SMI_HIP(hipMalloc((void **)&o.weights, n * sizeof(float)));
+            SMI_HIP(hipMemcpy(o.channels, channels, C * sizeof(int32_t), hipMemcpyHostToDevice));
+            SMI_HIP(hipMemcpy(o.data, data, n * sizeof(float), hipMemcpyHostToDevice));
+            SMI_HIP(hipMemcpy(o.weights, weights, n * sizeof(float), hipMemcpyHostToDevice));
+        }
+        if (term_slot) SMI_HIP(hipMemset(term_slot, 0, sizeof(double)));
+        return SMI_OK;
+    };
+    const int rc = run();
+    if (d_A) (void)hipFree(d_A);
+    if (d_S) (void)hipFree(d_S);
+    if (rc) {
+        for (void *q : {(void *)o.E, (void *)o.beta, (void *)o.data, (void *)o.weights,
+                        (void *)o.channels})
+            if (q) (void)hipFree(q);
+        p->owned.pop_back();
+        return rc;
+    }
+    LowResMember m;
+    m.E = o.E; m.beta = o.beta; m.data = o.data; m.weights = o.weights; m.channels = o.channels;
+    m.term = term_slot; m.log_norm = log_norm; m.blend = blend; m.unused = 0;
+    p->members.push_back(m);
+    p->dirty = true;
+    return SMI_OK;
+}
+
+// the table and the pooled work arrays for the members there are now
+static int lowres_pool_ready(LowResPool *p) {
+    if (!p->dirty) return SMI_OK;
+    const int n = (int)p->members.size();
+    SMI_REQUIRE(n > 0, "an empty pool of low-resolution observations");
+    if (n > p->cap) {
+        pool_free_work(p);
+        const size_t plane = (size_t)p->Fy * p->Fx, nc = (size_t)n * p->C;
+        const size_t n_out = nc * p->n_a * p->n_b, n_pad = nc * plane;
+        SMI_HIP(hipMalloc((void **)&p->table, n * sizeof(LowResMember)));
+        SMI_HIP(hipMalloc((void **)&p->model, n_pad * sizeof(float)));
+        SMI_HIP(hipMalloc((void **)&p->out, (n_out + 2 * kPoolGuard) * sizeof(float)));
+        SMI_HIP(hipMalloc((void **)&p->resid, n_out * sizeof(float)));
+        SMI_HIP(hipMalloc((void **)&p->gpad, (n_pad + 2 * kPoolGuard) * sizeof(float)));
+        SMI_HIP(hipMalloc((void **)&p->Mh, nc * p->Fy * p->Kx * sizeof(float2)));
+        SMI_HIP(hipMalloc((void **)&p->Gbar, nc * p->n_a * p->Kx * sizeof(float2)));
+        // (0xa5 bytes: the guard pattern; the work arrays themselves are written before read)
+        SMI_HIP(hipMemset(p->out, 0xa5, (n_out + 2 * kPoolGuard) * sizeof(float)));
+        SMI_HIP(hipMemset(p->gpad, 0xa5, (n_pad + 2 * kPoolGuard) * sizeof(float)));
+        SMI_HIP(hipMemset(p->model, 0, n_pad * sizeof(float)));
+        SMI_HIP(hipMemset(p->resid, 0, n_out * sizeof(float)));
+        const int nsl = std::max(p->nsl_f, p->nsl_b);
+        if (nsl > 1) {
+            const size_t in_launch = std::min<size_t>(nc, (size_t)gemm_pooled_chunk(nsl));
+            const size_t MN = (size_t)p->Fy * std::max(p->Fx, 2 * p->Kx);
+            SMI_HIP(hipMalloc((void **)&p->scratch, (size_t)nsl * in_launch * MN * sizeof(double)));
+        }
+        p->cap = n;
+    }
+    SMI_HIP(hipMemcpy(p->table, p->members.data(), n * sizeof(LowResMember),
+                      hipMemcpyHostToDevice));
+    p->dirty = false;
+    return SMI_OK;
+}
+
+// p->model (padded, all members) -> p->out + kPoolGuard
+static int lowres_pool_forward(LowResPool *p, const int32_t *state, hipStream_t s) {
+    const int n = (int)p->members.size(), Kx = p->Kx;
+    const int64_t plane = (int64_t)p->Fy * p->Fx;
+    int rc = gemm_pooled(p->kslice_f, p->nsl_f, p->model, plane, p->Wx,
+                         reinterpret_cast<float *>(p->Mh), (int64_t)p->Fy * 2 * Kx, n * p->C,
+                         p->scratch, p->Fy, 2 * Kx, p->Fx, s);
+    if (rc) return rc;
+    const size_t lds = (size_t)(16 * 64 + Kx) * sizeof(double2);
+    hipLaunchKernelGGL(spectral_forward_kernel, dim3(p->n_a, p->C, n), dim3(1024), lds, s, nullptr,
+                       p->Mh, nullptr, p->out + kPoolGuard, p->n_a, p->n_b, p->Fy, Kx, p->table,
+                       state);
+    return SMI_OK;
+}
+
+// p->resid -> p->gpad + kPoolGuard
+static int lowres_pool_adjoint(LowResPool *p, const int32_t *state, hipStream_t s) {
+    const int n = (int)p->members.size(), Kx = p->Kx;
+    hipLaunchKernelGGL(spectral_gbar_kernel, dim3(p->C * p->n_a, n), dim3(256),
+                       p->n_b * sizeof(float), s, p->resid, nullptr, p->Gbar, p->n_b, Kx, p->table,
+                       state);
+    hipLaunchKernelGGL(spectral_adjoint_kernel, dim3(p->Fy, p->C, n), dim3(256), 0, s, nullptr,
+                       p->Gbar, p->Mh, p->n_a, p->Fy, Kx, p->table, state);
+    return gemm_pooled(p->kslice_b, p->nsl_b, reinterpret_cast<float *>(p->Mh),
+                       (int64_t)p->Fy * 2 * Kx, p->WxT, p->gpad + kPoolGuard,
+                       (int64_t)p->Fy * p->Fx, n * p->C, p->scratch, p->Fy, p->Fx, 2 * Kx, s);
+}
+
+int lowres_pool_evaluate(LowResPool *p, const float *P, int Py, int Px, int Cm,
+                         const int32_t *state, int backward, hipStream_t s) {
+    int rc = lowres_pool_ready(p);
+    if (rc) return rc;
+    const int n = (int)p->members.size(), plane = p->Fy * p->Fx;
+    hipLaunchKernelGGL(lowres_pad_kernel, dim3((plane + 255) / 256, p->C, n), dim3(256), 0, s, P,
+                       Py, Px, nullptr, p->H, p->W, p->y0, p->x0, p->model, p->Fy, p->Fx, p->table,
+                       state, Cm);
+    if ((rc = lowres_pool_forward(p, state, s))) return rc;
+    hipLaunchKernelGGL(lowres_residual_kernel, dim3(n), dim3(1024), 0, s, p->out + kPoolGuard,
+                       nullptr, nullptr, p->resid, p->C * p->n_a * p->n_b, 0.0, nullptr, p->table,
+                       state);
+    if (!backward) return SMI_OK;
+    return lowres_pool_adjoint(p, state, s);
+}
+
+int lowres_pool_add_gradient(LowResPool *p, float *Q, int Py, int Px, int Cm,
+                             const int32_t *state, hipStream_t s) {
+    const int rc = lowres_pool_ready(p);
+    if (rc) return rc;
+    const int n = (int)p->members.size();
+    hipLaunchKernelGGL(lowres_add_kernel, dim3((p->H * p->W + 255) / 256, p->C, n), dim3(256), 0,
+                       s, p->gpad + kPoolGuard, p->Fy, p->Fx, p->y0, p->x0, nullptr, p->H, p->W, Q,
+                       Py, Px, p->table, state, Cm);
+    return SMI_OK;
+}
+
+int lowres_pool_get_rendered(LowResPool *p, int member, float *out, hipStream_t s) {
+    SMI_REQUIRE(member >= 0 && member < (int)p->members.size() && !p->dirty && p->out,
+                "no rendering of this observation yet");
+    const size_t n = (size_t)p->C * p->n_a * p->n_b;
+    SMI_HIP(hipMemcpyAsync(out, p->out + kPoolGuard + member * n, n * sizeof(float),
+                           hipMemcpyDeviceToHost, s));
+    SMI_HIP(hipStreamSynchronize(s));
+    return SMI_OK;
+}
+
+int lowres_pool_test(int n, const float *A, const float *Pt, int C, int n_a, int n_b, int Fy,
+                     int Fx, const float *models, const float *resid, float *out, float *gpad,
+                     int32_t *guard_ok) {
+    LowResPool *p = nullptr;
+    int32_t *state = nullptr;
+    auto run = [&]() -> int {
+        int rc = lowres_pool_create(C, n_a, n_b, Fy, Fx, Fy, Fx, &p);
+        if (rc) return rc;
+        const size_t nA = (size_t)C * n_a * Fy * Fx, nP = (size_t)Fx * Fx * n_b;
+        for (int m = 0; m < n; ++m)
+            if ((rc = lowres_pool_add(p, A + m * nA, Pt + m * nP, nullptr, nullptr, nullptr,
+                                      nullptr, 0.0, m, nullptr)))
+                return rc;
+        if ((rc = lowres_pool_ready(p))) return rc;
+        const size_t n_pad = (size_t)n * C * Fy * Fx, n_out = (size_t)n * C * n_a * n_b;
+        SMI_HIP(hipMalloc((void **)&state, n * sizeof(int32_t)));
+        SMI_HIP(hipMemset(state, 0, n * sizeof(int32_t)));
+        SMI_HIP(hipMemcpy(p->model, models, n_pad * sizeof(float), hipMemcpyHostToDevice));
+        SMI_HIP(hipMemcpy(p->resid, resid, n_out * sizeof(float), hipMemcpyHostToDevice));
+        if ((rc = lowres_pool_forward(p, state, nullptr))) return rc;
+        if ((rc = lowres_pool_adjoint(p, state, nullptr))) return rc;
+        SMI_HIP(hipGetLastError());
+        SMI_HIP(hipDeviceSynchronize());
+        std::vector<float> h_out(n_out + 2 * kPoolGuard), h_g(n_pad + 2 * kPoolGuard);
+        SMI_HIP(hipMemcpy(h_out.data(), p->out, h_out.size() * sizeof(float), hipMemcpyDeviceToHost));
+        SMI_HIP(hipMemcpy(h_g.data(), p->gpad, h_g.size() * sizeof(float), hipMemcpyDeviceToHost));
+        const uint32_t gbits = 0xa5a5a5a5u;
+        bool ok = true;
+        for (size_t i = 0; i < kPoolGuard; ++i) {
+            ok = ok && memcmp(&h_out[i], &gbits, 4) == 0 &&
+                 memcmp(&h_out[kPoolGuard + n_out + i], &gbits, 4) == 0;
+            ok = ok && memcmp(&h_g[i], &gbits, 4) == 0 &&
+                 memcmp(&h_g[kPoolGuard + n_pad + i], &gbits, 4) == 0;
+        }
+        *guard_ok = ok ? 1 : 0;
+        memcpy(out, h_out.data() + kPoolGuard, n_out * sizeof(float));
+        memcpy(gpad, h_g.data() + kPoolGuard, n_pad * sizeof(float));
+        return SMI_OK;
+    };
+    const int rc = run();
+    if (state) (void)hipFree(state);
+    lowres_pool_destroy(p);
+    return rc;
 }
 
 }  // namespace smi

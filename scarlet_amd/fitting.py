@@ -104,7 +104,11 @@ def fit_blends(blends, max_iter=200, e_rel=1e-3, min_iter=1, devices=None, _repo
     convolution path; frames too large for it go through rocFFT, where the loss is summed in
     blocks of the padded plane and a padded blend's losses are those of its own fit to the
     rounding of that float64 sum.  Blends without a convolution
-    (``NullRenderer``) share a batch when their frames are equal.  The box-resizing hook
+    (``NullRenderer``) share a batch when their frames are equal.  Blends with observations on a
+    coarser pixel grid (``ResolutionRenderer`` on the spectral path) share a batch when they also
+    agree in their exact frame and in the shape classes of these observations; every launch of
+    the low-resolution chain then works on all of them, each with its own operators, and every
+    blend keeps the bits of its own ``Blend.fit`` (``plan_fit_blends``).  The box-resizing hook
     and the restart it triggers (blend.py:196-198, 284-292) stay per blend: after every
     round the blends are regrouped by their own iteration counter.
 
@@ -127,7 +131,7 @@ def fit_blends(blends, max_iter=200, e_rel=1e-3, min_iter=1, devices=None, _repo
     blends = list(blends)
     kw = dict(max_iter=max_iter, e_rel=e_rel, min_iter=min_iter, **alg_kwargs)
     fit_blends.errors = []
-    report = dict(groups=[], alone={}, batches=0)
+    report = dict(groups=[], alone={}, batches=0, operator_bytes=[])
     if _report is not None:
         _report.clear()
         _report.update(report)
@@ -223,11 +227,13 @@ fit_blends.errors = []
 def _merge_report(report, part, lo):
     """The report of the shard that starts at blend ``lo`` into the report of the call."""
     report["groups"].extend((key, [lo + i for i in idx]) for key, idx in part.get("groups", []))
+    report.setdefault("operator_bytes", []).extend(part.get("operator_bytes", []))
     report["alone"].update((lo + i, why) for i, why in part.get("alone", {}).items())
     report["batches"] += part.get("batches", 0)
 
 
-def plan_fit_blends(blends, max_iter=200, e_rel=1e-3, min_iter=1, devices=None, **alg_kwargs):
+def plan_fit_blends(blends, max_iter=200, e_rel=1e-3, min_iter=1, devices=None, details=False,
+                    **alg_kwargs):
     """``(groups, alone)`` of ``fit_blends(blends, ...)`` with the same arguments, without a
     GPU: ``groups``, a list of ``(key, positions)`` -- the blends of every device batch, in the
     order the batches are opened and in list order inside a group -- and ``alone``,
@@ -235,6 +241,13 @@ def plan_fit_blends(blends, max_iter=200, e_rel=1e-3, min_iter=1, devices=None, 
     ``key = (bands, kernel cube shape, (conv_path, Fy, Fx, zb))``: the convolution plan is
     that of the blend's own frame (``_conv_plan``), so the frames of a group may differ;
     without a kernel (``NullRenderer``) the plan is ``(None, h, w, 0)``, the frame itself.
+    A blend with observations on coarser grids (``ResolutionRenderer``, all on the spectral
+    path) has three more entries in its key: its exact frame ``(h, w)`` -- such a group is never
+    padded --, the shape classes ``(C, n_a, n_b, Fy, Fx)`` of these observations in order and
+    their number.  Such a group is cut so that the transformed operators of one batch stay
+    within ``LOWRES_OPERATOR_CAP`` bytes: every part is an entry of ``groups`` (a batch) under
+    the same key.  ``details=True`` returns a third item, the bytes of these operators per
+    entry of ``groups`` (0 without such observations).
     With a list of ``devices`` every shard (``dist.shard_range``) has groups of its own.
     Like the fit, the call prepares the blends' device descriptions and drops what an earlier
     ``fit`` left of its scheme on them."""
@@ -254,11 +267,13 @@ def plan_fit_blends(blends, max_iter=200, e_rel=1e-3, min_iter=1, devices=None, 
         from .dist import shard_range
 
         cuts = [shard_range(len(blends), i, len(devices)) for i in range(len(devices))]
-    report = dict(groups=[], alone={}, batches=0)
+    report = dict(groups=[], alone={}, batches=0, operator_bytes=[])
     for lo, hi in cuts:
         part = {}
         _sort_blends(blends[lo:hi], dict(alg_kwargs), part)
         _merge_report(report, part, lo)
+    if details:
+        return report["groups"], report["alone"], report["operator_bytes"]
     return report["groups"], report["alone"]
 
 
@@ -312,6 +327,12 @@ def _open_batch(runs, specs, flat, capacity, device, opt, report=None):
     if report is not None:
         report["batches"] = report.get("batches", 0) + 1
     try:
+        # observations on coarser pixel grids: terms of their own blend, evaluated together per
+        # shape class (the group shares frame and classes: _group_key)
+        for i, r in enumerate(runs):
+            for obs, idx in r.lowres:
+                batch.attach_lowres(obs.renderer._operators(), idx, obs.data, obs.weights,
+                                    obs.log_norm, blend=i)
         if any(r.blend._loss_constant for r in runs):
             batch.add_loss_constant([r.blend._loss_constant for r in runs])
         Blend._upload_state(batch, flat)
@@ -687,10 +708,12 @@ class _Run:
     """A blend in a device batch: its observation cubes, the device description of its
     components, and where its fit stands."""
 
-    def __init__(self, blend, obs, specs):
+    def __init__(self, blend, obs, specs, lowres=()):
         # `base + local` is the reference's `it`: 0 at the start of fit(), the length
         # of the whole loss history after a restart (blend.py:101, 198)
         self.blend, self.obs, self.specs = blend, obs, specs
+        # (observation, model channels of its bands) of every ResolutionRenderer observation
+        self.lowres = tuple(lowres)
         self.base, self.local, self.result = 0, 0, None
 
     @property
@@ -709,14 +732,17 @@ def _classify(blend):
            for obs in blend.observations):
         return "a user-defined renderer: Blend.fit's host-rendered mode", None
     obs = blend._observation()  # (built once: the data, weight and kernel cubes)
-    if blend._lowres or blend._extra_layers:
-        # a ResolutionRenderer observation / several observations of one channel are terms of
-        # ONE blend's loss on the device (smi_batch_attach_lowres, smi_batch_add_observation)
-        return "several terms in its loss", None
+    if blend._extra_layers:
+        # further cubes on the model's grid are terms of ONE blend's loss on the device
+        # (smi_batch_add_observation)
+        return "several observations of one channel", None
+    if any(not o.renderer.on_spectral_path() for o, _ in blend._lowres):
+        # the dense products keep Fy Fx Fx n_b floats per band: a batch of one blend
+        return "a low-resolution observation on the dense path", None
     specs = blend._specs(_flatten(blend.sources))  # (once: 15 us per component)
     if blend._host:  # (hoststep.py: one iteration per device call)
         return "parameters the host updates", None
-    return None, _Run(blend, obs, specs)
+    return None, _Run(blend, obs, specs, blend._lowres)
 
 
 def _group_key(run):
@@ -726,7 +752,15 @@ def _group_key(run):
     to a batch mate's frame never changes the convolution a blend sees.  Without a kernel
     (``NullRenderer``) the plan is the frame shape itself."""
     data, _, kernel = run.obs
-    return _key_of(data.shape, None if kernel is None else kernel.shape)
+    key = _key_of(data.shape, None if kernel is None else kernel.shape)
+    if run.lowres:
+        # Observations on coarser grids (ResolutionRenderer) are terms of their blend's loss
+        # that the device evaluates per shape class, and they do not combine with frame
+        # extents: such a group shares the exact frame (it is never padded), the number of
+        # these observations and, one by one, their classes (C, n_a, n_b, Fy, Fx).
+        key += (tuple(int(n) for n in data.shape[1:]),
+                tuple(obs.renderer.shape_class() for obs, _ in run.lowres), len(run.lowres))
+    return key
 
 
 @functools.lru_cache(maxsize=4096)
@@ -742,7 +776,7 @@ def _sort_blends(blends, alg_kwargs, report):
     groups)`` -- the adaprox options parsed from ``alg_kwargs`` (which is emptied),
     ``_classify`` of every blend and ``[(key, positions)]`` in order of first appearance.
     ``report`` receives ``groups`` and ``alone`` (``plan_fit_blends``)."""
-    report.update(groups=[], alone={}, batches=0)
+    report.update(groups=[], alone={}, batches=0, operator_bytes=[])
     if alg_kwargs.get("callback") is not None or alg_kwargs.get("scheme", "amsgrad") != "amsgrad":
         why = ("a callback" if alg_kwargs.get("callback") is not None else
                "scheme {!r}".format(alg_kwargs.get("scheme"))) + ": Blend.fit's host-stepped mode"
@@ -758,8 +792,41 @@ def _sort_blends(blends, alg_kwargs, report):
             report["alone"][i] = why
         else:
             groups.setdefault(_group_key(run), []).append(i)
-    report["groups"] = list(groups.items())
+    # a group with low-resolution observations is cut into batches whose pooled operators stay
+    # under the cap; a blend has the same bits on either side of a cut
+    report["groups"], report["operator_bytes"] = [], []
+    for key, idx in groups.items():
+        each = [sum(obs.renderer.operator_bytes() for obs, _ in sorted_out[i][1].lowres)
+                for i in idx]
+        for lo, hi in _cut_by_bytes(each, LOWRES_OPERATOR_CAP):
+            report["groups"].append((key, idx[lo:hi]))
+            report["operator_bytes"].append(int(sum(each[lo:hi])))
     return prox_max_iter, opt, sorted_out, report["groups"]
+
+
+# Device memory the transformed operators E of ONE batch may take (bytes): per low-resolution
+# observation C n_a Fy Kx complex float32 (ResolutionRenderer.operator_bytes; 0.3 MB for an
+# 11 x 11 observation of two bands on a 54 x 60 grid, 10.5 MB for 36 x 36 pixels of five bands
+# on 120 x 120).  An MI355X has 288 GB of HBM; a fit that shards over threads or shares its card
+# with other jobs should not take more than a sixteenth of it, 18 GB, of which the batch's
+# other arrays (cubes, the work arrays of the pool: about a tenth of E), the upload buffers and
+# the runtime need their part -- 12 GiB for E: 1 200 tutorial-sized blends or 40 000
+# catalogue-sized ones in one batch, far beyond where a larger batch still gains anything.
+LOWRES_OPERATOR_CAP = 12 << 30
+
+
+def _cut_by_bytes(each, cap):
+    """``[(lo, hi)]``: consecutive runs of a list of sizes ``each`` whose sums stay within
+    ``cap`` (a single entry beyond the cap is a run of its own)."""
+    cuts, lo, total = [], 0, 0
+    for i, n in enumerate(each):
+        if i > lo and total + n > cap:
+            cuts.append((lo, i))
+            lo, total = i, 0
+        total += n
+    if len(each) > lo:
+        cuts.append((lo, len(each)))
+    return cuts
 
 
 def _fit_alone(blend, device, *args, **kwargs):

@@ -246,6 +246,41 @@ class ResolutionRenderer(Renderer):
         shifted = spectrum[:, :, :, np.newaxis] * phase[np.newaxis, np.newaxis, :, :]
         return np.fft.fftshift(np.fft.irfft(shifted, F, axis=2), axes=2)
 
+    def _operators(self):
+        """``(A, Pt, (Fy, Fx))``: the two host operators as the device takes them, float32 --
+        ``A`` (C, n_a, Fy Fx), the kernel shifted to every low-resolution row, and ``Pt``
+        (Fx, Fx n_b), which shifts one padded row to every low-resolution column (kept: it is
+        small, and a catalogue fit asks for it once per batch the blend is in)."""
+        if getattr(self, "_host_ops", None) is None:
+            Fy, Fx = self._fft_shape
+            n_b = self.other_shifts.shape[1]
+            # operator that shifts one padded row to every low-resolution column: the
+            # reference's pipeline applied to the identity (row x' -> P[x, b, x'])
+            eye = np.eye(Fx, dtype=np.float64)[np.newaxis]  # (1, Fx rows, Fx)
+            P = self._shift_along(eye, -self.other_shifts[1], axis=2)[0]  # (x', x, b)
+            self._host_ops = np.ascontiguousarray(P.reshape(Fx, Fx * n_b), dtype=np.float32)
+        A = np.ascontiguousarray(self._resconv_op, dtype=np.float32)
+        return A, self._host_ops, tuple(int(n) for n in self._fft_shape)
+
+    def shape_class(self):
+        """``(C, n_a, n_b, Fy, Fx)``: observations that agree in it are evaluated together in
+        a device batch (``smi_batch_attach_lowres_blend``)."""
+        C, n_a, _ = self._resconv_op.shape
+        return (int(C), int(n_a), int(self.other_shifts.shape[1])) + tuple(
+            int(n) for n in self._fft_shape)
+
+    def operator_bytes(self):
+        """Device memory of the transformed operator ``E`` of this renderer in a batch:
+        ``C n_a Fy Kx`` complex float32, ``Kx = Fx / 2 + 1``."""
+        C, n_a, _, Fy, Fx = self.shape_class()
+        return C * n_a * Fy * (Fx // 2 + 1) * 8
+
+    def on_spectral_path(self):
+        """True unless the dense products were asked for (``device_path(0)``) or the rows are
+        too long for the device's transform tables; needs no device.  (The shift operator this
+        class builds is circulant by construction; the device checks what it is handed.)"""
+        return not getattr(self, "_dense", False) and self._fft_shape[1] <= 2048
+
     def _resampler(self):
         """Device handle holding the two operators (built on first use)."""
         if self._device is None:
@@ -254,15 +289,8 @@ class ResolutionRenderer(Renderer):
             from . import _lib
 
             lib = _lib.load()
-            C, n_a, _ = self._resconv_op.shape
-            Fy, Fx = self._fft_shape
-            n_b = self.other_shifts.shape[1]
-            # operator that shifts one padded row to every low-resolution column: the
-            # reference's pipeline applied to the identity (row x' -> P[x, b, x'])
-            eye = np.eye(Fx, dtype=np.float64)[np.newaxis]  # (1, Fx rows, Fx)
-            P = self._shift_along(eye, -self.other_shifts[1], axis=2)[0]  # (x', x, b)
-            Pt = np.ascontiguousarray(P.reshape(Fx, Fx * n_b), dtype=np.float32)
-            A = np.ascontiguousarray(self._resconv_op, dtype=np.float32)
+            C, n_a, n_b, Fy, Fx = self.shape_class()
+            A, Pt, _ = self._operators()
             handle = ctypes.c_void_p()
             _lib.check(lib.smi_resampler_create(
                 _lib.ptr(A, ctypes.c_float), _lib.ptr(Pt, ctypes.c_float), C, n_a, n_b, Fy, Fx,
@@ -283,6 +311,7 @@ class ResolutionRenderer(Renderer):
             _lib.check(lib.smi_resampler_set_path(handle, int(path)))
         now = ctypes.c_int32(-1)
         _lib.check(lib.smi_resampler_get_path(handle, ctypes.byref(now)))
+        self._dense = now.value == 0
         return now.value
 
     def get_model(self, *parameters):
