@@ -1156,16 +1156,49 @@ int smi_fft_shape_for(int32_t H, int32_t W, int32_t kernel_h, int32_t kernel_w, 
  * s_b[(x - x') mod Fx].  smi_resampler_create checks that, and then evaluates the same map
  * through transforms along x of the model rows, the operator rows (made once, on the
  * device, in float64) and s_b -- path 1, "spectral": 1/25 of the arithmetic and 1/5 of the
- * HBM traffic of the two dense products (path 0), which stay for any other Pt. */
+ * HBM traffic of the two dense products (path 0), which stay for any other Pt.
+ *
+ * Between ROTATED pixel grids (renderer.py:319-363, 498-524) the reference Fourier-shifts the
+ * padded difference kernel in 2-D to shifts[:, a] for every low-resolution row a (times h^2:
+ * the operator) and, per call, the padded model by -other_shifts[:, b] for every column b, and
+ * contracts the two over the padded grid.  smi_resampler_create_rotated takes what that needs
+ * -- kernel[C][Fy][Fx], scale = h^2, shifts[2][n_a], other_shifts[2][n_b] (y row, then x row) --
+ * and evaluates the same map in Fourier space, path 2:
+ *
+ *   out[c][a][b] = sum_{ky, kx} Re( E[c][a][ky][kx] conj( Mh[c][ky][kx] beta[b][ky][kx] ) )
+ *
+ * with E[c][a] = scale rfftn(kernel[c]) alpha'[a] and beta[b] = w_kx / (Fy Fx) beta'[b] made once
+ * on the device in float64 and kept as float32 complex (C n_a Fy Kx and n_b Fy Kx of them,
+ * Kx = Fx / 2 + 1; w = 1 for kx = 0 and the x-Nyquist term, else 2), Mh = rfftn(model) per
+ * rendering.  alpha'[a] and beta'[b] are the tables exp(-2 pi i (f_y s_y + f_x s_x)), f_y =
+ * fftfreq(Fy), f_x = rfftfreq(Fx), of s = shifts[:, a] and s = -other_shifts[:, b] with the
+ * edge-column rule: the inverse real transform of the reference keeps only the Hermitian part
+ * along y on the self-conjugate columns kx = 0 and (even Fx) kx = Fx / 2, so there t'[ky] =
+ * (t[ky] + conj(t[-ky mod Fy])) / 2.  Sum order: K = Fy Kx is cut into slices of 64 terms
+ * (longer where that would give more than 256 slices; a multiple of 32); inside a slice every
+ * output adds e.x s.x, -e.y s.y with s = conj(Mh beta) for k ascending in one float64 fma
+ * chain (s formed in float64 from the float32 operands and rounded to float32 once), the slices
+ * are added in ascending order.  The transpose: Mbar[c][k] = sum_a E[c][a][k]
+ * (sum_b resid[c][a][b] conj(beta[b][k])) with b ascending in chunks of 64, a = w (mod 4) per
+ * wavefront w and the four sums combined (0 + 1) + (2 + 3), then the inverse transform along
+ * y and along x.  Fx <= 2048 (a row and its twiddles live in LDS); Fy, n_a, n_b <= 65535.
+ * smi_resampler_set_path refuses to move a rotated resampler to path 0 or 1 and any other to
+ * path 2. */
 typedef struct smi_resampler smi_resampler;
 int smi_resampler_create(const float *A, const float *Pt, int32_t C, int32_t n_a, int32_t n_b,
                          int32_t Fy, int32_t Fx, smi_resampler **out);
+int smi_resampler_create_rotated(const float *kernel, double scale, const double *shifts,
+                                 const double *other_shifts, int32_t C, int32_t n_a, int32_t n_b,
+                                 int32_t Fy, int32_t Fx, smi_resampler **out);
 int smi_resampler_render(smi_resampler *r, const float *model, float *out);
 /* mean device time (ms) of one rendering of the model last passed to smi_resampler_render,
  * over n_rep repetitions without host transfers (benchmark of BASELINE config 5) */
 int smi_resampler_time(smi_resampler *r, int32_t n_rep, double *ms_per_render);
+/* the same for the transposed map (smi_resampler_adjoint) of a zero residual */
+int smi_resampler_time_adjoint(smi_resampler *r, int32_t n_rep, double *ms_per_call);
 int smi_resampler_destroy(smi_resampler *r);
-/* which evaluation the resampler uses: 0 = two dense products per band, 1 = spectral.
+/* which evaluation the resampler uses: 0 = two dense products per band, 1 = spectral, 2 = the
+ * Fourier-space contraction between rotated grids.
  * smi_resampler_set_path(r, 0) switches a spectral resampler to the dense products (the
  * parity tests compare the two); path 1 is refused for an operator that is not circulant. */
 int smi_resampler_get_path(smi_resampler *r, int32_t *path);
@@ -1192,6 +1225,19 @@ int smi_gemm_test(const float *A, int64_t strideA, const float *B, int64_t strid
                   int64_t strideC, int32_t n_batch, int32_t M, int32_t N, int32_t K,
                   int64_t scratch_elems, int32_t plan[5], int32_t *guard_ok);
 int smi_resampler_adjoint(smi_resampler *r, const float *resid, float *gpad);
+/* Test entry point (tests/test_gpu_resolution_rot.py): rendering of model[C][Fy][Fx] and
+ * transpose of resid[C][n_a][n_b] by a rotated resampler, into out[C][n_a][n_b] and
+ * gpad[C][Fy][Fx] (host pointers).  Both device outputs are filled with NaNs before the
+ * launches and lie between 256 guard floats; every work array of the rotated map (the two
+ * transforms, Mbar, the slice partials) is followed by 256 guard elements.  *guard_ok = 1 if
+ * all guards came back untouched.  The work arrays are refilled with NaNs on every call. */
+int smi_resampler_rotated_test(smi_resampler *r, const float *model, const float *resid,
+                               float *out, float *gpad, int32_t *guard_ok);
+/* Test entry point (host only, no GPU): what a rotated resampler of these shapes launches --
+ * plan = {ti, tj, tiles along a, tiles along b, terms per slice, slices of K = Fy Kx, chunks of
+ * 64 columns b in the transpose}; the contraction's block tile is 16 ti x 16 tj outputs
+ * (ti, tj <= 4). */
+int smi_resampler_rotated_plan(int32_t n_a, int32_t n_b, int32_t Fy, int32_t Fx, int32_t plan[7]);
 
 /* Test entry point (tests/test_gpu_update_step.py): y[i] = the square root the AMSGrad pass of
  * the update kernels takes when the batch's eps is at least 2^-96 -- the hardware root plus
@@ -1231,8 +1277,8 @@ int smi_update_last_fold_plan_test(int64_t plan[8]);
  * w (m - d) to the gradient image.  Every call adds one observation of blend 0 (at most 8 per
  * blend).  A resampler on the spectral path hands its tables over (a copy: `r` need not
  * outlive `b`) and the observation joins the pooled chain below; one on the dense path
- * (smi_resampler_set_path(r, 0), or an operator that is not circulant) needs a batch of one
- * blend and must outlive `b`. */
+ * (smi_resampler_set_path(r, 0), or an operator that is not circulant) or between rotated
+ * grids (path 2) needs a batch of one blend and must outlive `b`. */
 int smi_batch_attach_lowres(smi_batch *b, smi_resampler *r, const int32_t *channels,
                             const float *data, const float *weights, double log_norm);
 /* The same for blend `blend` of a batch of any size, from the host operators themselves

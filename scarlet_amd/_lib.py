@@ -268,9 +268,19 @@ SYMBOLS = {
         [c_f32p, c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
          ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)],
     ),
+    "smi_resampler_create_rotated": (
+        ctypes.c_int,
+        [c_f32p, ctypes.c_double, c_f64p, c_f64p] + [ctypes.c_int32] * 5
+        + [ctypes.POINTER(ctypes.c_void_p)],
+    ),
+    "smi_resampler_rotated_test": (
+        ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p]),
+    "smi_resampler_rotated_plan": (ctypes.c_int, [ctypes.c_int32] * 4 + [c_i32p]),
     "smi_resampler_render": (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p]),
     "smi_resampler_time": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32,
                                           ctypes.POINTER(ctypes.c_double)]),
+    "smi_resampler_time_adjoint": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32,
+                                                  ctypes.POINTER(ctypes.c_double)]),
     "smi_resampler_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "smi_resampler_get_path": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     "smi_resampler_set_path": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),

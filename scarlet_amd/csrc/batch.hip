@@ -694,6 +694,40 @@ int smi_resampler_create(const float *A, const float *Pt, int32_t C, int32_t n_a
     return SMI_OK;
 }
 
+int smi_resampler_create_rotated(const float *kernel, double scale, const double *shifts,
+                                 const double *other_shifts, int32_t C, int32_t n_a, int32_t n_b,
+                                 int32_t Fy, int32_t Fx, smi_resampler **out) {
+    SMI_REQUIRE(kernel && shifts && other_shifts && out, "null argument");
+    SMI_REQUIRE(C > 0 && n_a > 0 && n_b > 0 && Fy > 0 && Fx > 0, "bad sizes");
+    if (int rc = have_device()) return rc;
+    auto *h = new smi_resampler;
+    const int rc = resampler_create_rotated(kernel, scale, shifts, other_shifts, C, n_a, n_b, Fy,
+                                            Fx, &h->impl);
+    if (rc) {
+        resampler_destroy(h->impl);
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return SMI_OK;
+}
+
+int smi_resampler_rotated_test(smi_resampler *r, const float *model, const float *resid,
+                               float *out, float *gpad, int32_t *guard_ok) {
+    SMI_REQUIRE(r && r->impl && model && resid && out && gpad && guard_ok, "null argument");
+    *guard_ok = 0;
+    return resampler_rotated_test(r->impl, model, resid, out, gpad, guard_ok);
+}
+
+int smi_resampler_rotated_plan(int32_t n_a, int32_t n_b, int32_t Fy, int32_t Fx,
+                               int32_t plan[7]) {
+    SMI_REQUIRE(plan && n_a > 0 && n_b > 0 && Fy > 0 && Fx > 0, "bad argument");
+    const RotPlan p = rot_plan(n_a, n_b, Fy, Fx);
+    plan[0] = p.ti; plan[1] = p.tj; plan[2] = p.tiles_a; plan[3] = p.tiles_b;
+    plan[4] = p.kslice; plan[5] = p.n_slices; plan[6] = p.b_chunks;
+    return SMI_OK;
+}
+
 int smi_resampler_render(smi_resampler *r, const float *model, float *out) {
     SMI_REQUIRE(r && r->impl && model && out, "null argument");
     return resampler_render(r->impl, model, out);
@@ -702,6 +736,11 @@ int smi_resampler_render(smi_resampler *r, const float *model, float *out) {
 int smi_resampler_time(smi_resampler *r, int32_t n_rep, double *ms_per_render) {
     SMI_REQUIRE(r && r->impl && ms_per_render && n_rep > 0, "bad argument");
     return resampler_time(r->impl, n_rep, ms_per_render);
+}
+
+int smi_resampler_time_adjoint(smi_resampler *r, int32_t n_rep, double *ms_per_call) {
+    SMI_REQUIRE(r && r->impl && ms_per_call && n_rep > 0, "bad argument");
+    return resampler_time_adjoint(r->impl, n_rep, ms_per_call);
 }
 
 int smi_resampler_get_path(smi_resampler *r, int32_t *path) {
@@ -812,7 +851,11 @@ static int attach_lowres(smi_batch *b, int32_t blend, smi_resampler *r, bool spe
     while (behind != b->lowres.end() && behind->slot <= slot) ++behind;
     smi_batch::LowResWhere where;
     if (r && !spectral) {
-        // the dense products: one blend, B alone is Fy Fx Fx n_b floats per band
+        // the dense products: one blend, B alone is Fy Fx Fx n_b floats per band; a resampler
+        // between rotated grids keeps its operators itself and is not pooled either
+        if (resampler_get_path(r->impl) == 2)
+            SMI_REQUIRE(nb == 1, "a low-resolution observation on a rotated grid needs a batch "
+                                 "of one blend");
         SMI_REQUIRE(nb == 1, "a low-resolution observation on the dense path needs a batch of "
                              "one blend");
         LowRes *l = nullptr;

@@ -476,8 +476,34 @@ int mask_interpolate_host_buffers(const int32_t *row_idx, const int32_t *col_idx
 struct Resampler;
 int resampler_create(const float *A, const float *Pt, int C, int n_a, int n_b, int Fy, int Fx,
                      Resampler **out);
+// between rotated pixel grids (path 2): the padded kernel [C][Fy][Fx], scale = h^2 and the two
+// shift tables [2][n_a], [2][n_b]; the operator is made on the device (resample_rot.hip)
+int resampler_create_rotated(const float *kernel, double scale, const double *shifts,
+                             const double *other_shifts, int C, int n_a, int n_b, int Fy, int Fx,
+                             Resampler **out);
+// (test entry) rendering and transpose of a rotated resampler on host buffers, into arrays
+// filled with NaNs between guard bands; *guard_ok: those and the guards behind the work arrays
+// came back untouched
+int resampler_rotated_test(Resampler *r, const float *model, const float *resid, float *out,
+                           float *gpad, int32_t *guard_ok);
+// the rotated map itself (resample_rot.hip); model, out, resid and gpad are device pointers
+struct RotResampler;
+int rot_create(const float *kernel, double scale, const double *shifts, const double *other_shifts,
+               int C, int n_a, int n_b, int Fy, int Fx, RotResampler **out);
+void rot_destroy(RotResampler *r);
+int rot_forward(RotResampler *r, const float *model, float *out, hipStream_t s);
+int rot_adjoint(RotResampler *r, const float *resid, float *gpad, hipStream_t s);
+int rot_guards_ok(RotResampler *r, bool *ok);
+int rot_fill_work(RotResampler *r);  // NaNs in the work arrays, the guard pattern behind them
+// what a rotated resampler of these shapes launches (host only): contraction tile 16 ti x 16 tj,
+// tiles along a and b, terms per slice and slices of K = Fy Kx, 64-column chunks of the transpose
+struct RotPlan {
+    int32_t ti = 0, tj = 0, tiles_a = 0, tiles_b = 0, kslice = 0, n_slices = 0, b_chunks = 0;
+};
+RotPlan rot_plan(int n_a, int n_b, int Fy, int Fx);
 int resampler_render(Resampler *r, const float *model, float *out);
 int resampler_time(Resampler *r, int n_rep, double *ms_per_render);
+int resampler_time_adjoint(Resampler *r, int n_rep, double *ms_per_call);
 int resampler_get_path(const Resampler *r);
 int resampler_set_path(Resampler *r, int path);
 void resampler_destroy(Resampler *r);

@@ -19,6 +19,11 @@
 // tiles are summed in double by a second kernel -- that keeps the renderings within
 // ~1e-7 of the reference's float64 evaluation and gives a small output enough workgroups
 // to fill the chip.  The bands of an observation are one batched launch.
+//
+// Between rotated grids the reference shifts kernel and model in 2-D instead; a resampler made
+// by resampler_create_rotated evaluates that map in Fourier space (path 2, resample_rot.hip:
+// the map, its sum order and the edge-column rule are described there and above
+// smi_resampler_create in include/scarlet_amd.h) and holds neither A nor Pt.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -580,7 +585,8 @@ struct Resampler {
     float *At = nullptr;   // [C][Fy * Fx][n_a]: A transposed (left operand of the adjoint)
     float *P = nullptr;    // [Fx * n_b][Fx]
     // spectral path
-    int path = 0;          // 0: dense products, 1: spectral
+    int path = 0;          // 0: dense products, 1: spectral, 2: rotated grids
+    RotResampler *rot = nullptr;  // path 2 (resample_rot.hip): neither A nor Pt exist
     bool spectral = false; // Pt is circulant and the tables below exist
     int Kx = 0;            // Fx / 2 + 1
     float2 *E = nullptr;    // [C][n_a][Fy][Kx]: transforms along x of the operator rows
@@ -723,9 +729,26 @@ int resampler_create(const float *A, const float *Pt, int C, int n_a, int n_b, i
     return build_dense(r);
 }
 
+int resampler_create_rotated(const float *kernel, double scale, const double *shifts,
+                             const double *other_shifts, int C, int n_a, int n_b, int Fy, int Fx,
+                             Resampler **out) {
+    auto *r = new Resampler;
+    r->C = C; r->n_a = n_a; r->n_b = n_b; r->Fy = Fy; r->Fx = Fx;
+    r->path = 2;
+    *out = r;
+    SMI_HIP(hipMalloc((void **)&r->model, (size_t)C * Fy * Fx * sizeof(float)));
+    SMI_HIP(hipMalloc((void **)&r->out, (size_t)C * n_a * n_b * sizeof(float)));
+    return rot_create(kernel, scale, shifts, other_shifts, C, n_a, n_b, Fy, Fx, &r->rot);
+}
+
 int resampler_get_path(const Resampler *r) { return r->path; }
 
 int resampler_set_path(Resampler *r, int path) {
+    if (r->path == 2) {
+        SMI_REQUIRE(path == 2, "a resampler between rotated grids has no other path");
+        return SMI_OK;
+    }
+    SMI_REQUIRE(path != 2, "path 2 is that of a resampler made by smi_resampler_create_rotated");
     SMI_REQUIRE(path == 0 || path == 1, "path is 0 (dense products) or 1 (spectral)");
     SMI_REQUIRE(path == 0 || r->spectral,
                 "the shift operator of this resampler is not circulant: dense products only");
@@ -744,12 +767,14 @@ void resampler_destroy(Resampler *r) {
                     (void *)r->beta, (void *)r->Wx, (void *)r->WxT, (void *)r->Mh,
                     (void *)r->Gbar, (void *)r->sscratch})
         if (p) (void)hipFree(p);
+    rot_destroy(r->rot);
     delete r;
 }
 
 // r->model (device, padded) -> r->out, on stream s; all bands in one launch per product
 static int resampler_forward(Resampler *r, hipStream_t s) {
     const int64_t plane = (int64_t)r->Fy * r->Fx;
+    if (r->path == 2) return rot_forward(r->rot, r->model, r->out, s);
     if (r->path == 1) {
         const int Kx = r->Kx;
         int rc = gemm(r->model, plane, r->Wx, 0, reinterpret_cast<float *>(r->Mh),
@@ -772,6 +797,7 @@ static int resampler_forward(Resampler *r, hipStream_t s) {
 // gradient of the padded bands from the weighted residual [C][n_a][n_b] (the transposed chain)
 static int resampler_adjoint(Resampler *r, const float *resid, float *gpad, hipStream_t s) {
     const int64_t plane = (int64_t)r->Fy * r->Fx;
+    if (r->path == 2) return rot_adjoint(r->rot, resid, gpad, s);
     if (r->path == 1) {
         const int Kx = r->Kx;
         hipLaunchKernelGGL(spectral_gbar_kernel, dim3(r->C * r->n_a), dim3(256),
@@ -822,6 +848,60 @@ int resampler_adjoint_host(Resampler *r, const float *resid, float *gpad) {
     if (d_resid) (void)hipFree(d_resid);
     if (d_gpad) (void)hipFree(d_gpad);
     return rc;
+}
+
+// Rendering and transpose of a rotated resampler on host buffers, for the tests: out and gpad
+// hold NaNs before the launches, a guard band of kGuard floats lies before and after each, and
+// the work arrays of the rotated map carry guards of their own (rot_guards_ok).
+int resampler_rotated_test(Resampler *r, const float *model, const float *resid, float *out,
+                           float *gpad, int32_t *guard_ok) {
+    SMI_REQUIRE(r->path == 2 && r->rot, "not a resampler between rotated grids");
+    constexpr size_t kGuard = 256;
+    const size_t plane = (size_t)r->C * r->Fy * r->Fx, n = (size_t)r->C * r->n_a * r->n_b;
+    const uint32_t fbits = 0x7fc00000u, gbits = 0xa5a5a5a5u;
+    float fnan, fguard;
+    memcpy(&fnan, &fbits, 4);
+    memcpy(&fguard, &gbits, 4);
+    std::vector<float> h_out(n + 2 * kGuard, fnan), h_g(plane + 2 * kGuard, fnan);
+    for (size_t i = 0; i < kGuard; ++i) {
+        h_out[i] = h_out[kGuard + n + i] = fguard;
+        h_g[i] = h_g[kGuard + plane + i] = fguard;
+    }
+    float *d_out = nullptr, *d_g = nullptr, *d_resid = nullptr;
+    bool work_ok = false;
+    auto run = [&]() -> int {
+        SMI_HIP(hipMalloc((void **)&d_out, h_out.size() * sizeof(float)));
+        SMI_HIP(hipMalloc((void **)&d_g, h_g.size() * sizeof(float)));
+        SMI_HIP(hipMalloc((void **)&d_resid, n * sizeof(float)));
+        SMI_HIP(hipMemcpy(d_out, h_out.data(), h_out.size() * sizeof(float), hipMemcpyHostToDevice));
+        SMI_HIP(hipMemcpy(d_g, h_g.data(), h_g.size() * sizeof(float), hipMemcpyHostToDevice));
+        SMI_HIP(hipMemcpy(d_resid, resid, n * sizeof(float), hipMemcpyHostToDevice));
+        SMI_HIP(hipMemcpy(r->model, model, plane * sizeof(float), hipMemcpyHostToDevice));
+        int rc = rot_fill_work(r->rot);  // whatever ran before: unwritten work elements are NaNs
+        if (rc) return rc;
+        if ((rc = rot_forward(r->rot, r->model, d_out + kGuard, nullptr))) return rc;
+        if ((rc = rot_adjoint(r->rot, d_resid, d_g + kGuard, nullptr))) return rc;
+        SMI_HIP(hipGetLastError());
+        SMI_HIP(hipDeviceSynchronize());
+        SMI_HIP(hipMemcpy(h_out.data(), d_out, h_out.size() * sizeof(float), hipMemcpyDeviceToHost));
+        SMI_HIP(hipMemcpy(h_g.data(), d_g, h_g.size() * sizeof(float), hipMemcpyDeviceToHost));
+        return rot_guards_ok(r->rot, &work_ok);
+    };
+    const int rc = run();
+    for (void *p : {(void *)d_out, (void *)d_g, (void *)d_resid})
+        if (p) (void)hipFree(p);
+    if (rc) return rc;
+    bool ok = work_ok;
+    for (size_t i = 0; i < kGuard; ++i) {
+        ok = ok && memcmp(&h_out[i], &fguard, 4) == 0 &&
+             memcmp(&h_out[kGuard + n + i], &fguard, 4) == 0;
+        ok = ok && memcmp(&h_g[i], &fguard, 4) == 0 &&
+             memcmp(&h_g[kGuard + plane + i], &fguard, 4) == 0;
+    }
+    *guard_ok = ok ? 1 : 0;
+    memcpy(out, h_out.data() + kGuard, n * sizeof(float));
+    memcpy(gpad, h_g.data() + kGuard, plane * sizeof(float));
+    return SMI_OK;
 }
 
 // gemm() on host operands, for the tests: C and the scratch hold NaNs before the launch, a
@@ -906,6 +986,38 @@ int resampler_time(Resampler *r, int n_rep, double *ms_per_render) {
     (void)hipEventDestroy(e1);
     *ms_per_render = (double)ms / n_rep;
     return SMI_OK;
+}
+
+// device time of `n_rep` transposes of a zero residual (no host transfers), on the resampler's
+// current path
+int resampler_time_adjoint(Resampler *r, int n_rep, double *ms_per_call) {
+    const size_t n = (size_t)r->C * r->n_a * r->n_b, plane = (size_t)r->C * r->Fy * r->Fx;
+    float *d_resid = nullptr, *d_gpad = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto run = [&]() -> int {
+        SMI_HIP(hipMalloc((void **)&d_resid, n * sizeof(float)));
+        SMI_HIP(hipMalloc((void **)&d_gpad, plane * sizeof(float)));
+        SMI_HIP(hipMemset(d_resid, 0, n * sizeof(float)));
+        SMI_HIP(hipEventCreate(&e0));
+        SMI_HIP(hipEventCreate(&e1));
+        int rc = resampler_adjoint(r, d_resid, d_gpad, nullptr);  // warm-up
+        if (rc) return rc;
+        SMI_HIP(hipEventRecord(e0, nullptr));
+        for (int i = 0; i < n_rep; ++i)
+            if ((rc = resampler_adjoint(r, d_resid, d_gpad, nullptr))) return rc;
+        SMI_HIP(hipEventRecord(e1, nullptr));
+        SMI_HIP(hipEventSynchronize(e1));
+        float ms = 0.f;
+        SMI_HIP(hipEventElapsedTime(&ms, e0, e1));
+        *ms_per_call = (double)ms / n_rep;
+        return SMI_OK;
+    };
+    const int rc = run();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (d_resid) (void)hipFree(d_resid);
+    if (d_gpad) (void)hipFree(d_gpad);
+    return rc;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -736,6 +736,10 @@ def _classify(blend):
         # further cubes on the model's grid are terms of ONE blend's loss on the device
         # (smi_batch_add_observation)
         return "several observations of one channel", None
+    if any(o.renderer.isrot for o, _ in blend._lowres):
+        # its resampler evaluates the 2-D shifts in Fourier space under the dense path's
+        # contract: a batch of one blend (Blend.fit attaches the renderer's own handle)
+        return "a low-resolution observation on a rotated grid", None
     if any(not o.renderer.on_spectral_path() for o, _ in blend._lowres):
         # the dense products keep Fy Fx Fx n_b floats per band: a batch of one blend
         return "a low-resolution observation on the dense path", None

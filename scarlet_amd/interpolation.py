@@ -18,7 +18,8 @@ Where the reference does something else than was meant, this module does what wa
 - non-square observations: the reference stacks ``arange(Ho)`` and ``arange(Wo)`` into one
   array, which NumPy refuses when ``Ho != Wo``; they work here;
 - rotated grids: the reference passes ``angle=None`` whatever the grids are; here grids
-  rotated against each other raise ``NotImplementedError``, as ``ResolutionRenderer`` does.
+  rotated against each other raise ``NotImplementedError`` (``ResolutionRenderer`` decides
+  rotation the same way, and renders between rotated grids).
 """
 
 import numpy as np

@@ -167,8 +167,15 @@ class ResolutionRenderer(Renderer):
     shifting the padded model along x to every low-resolution column and contracting
     with the operator (renderer.py:478-545) -- is linear in the model; it runs on the
     GPU (``smi_resampler_*``), through transforms along x since the shift operator is
-    circulant, or as two dense products per band (``device_path``).  Rotated grids are not
-    supported."""
+    circulant, or as two dense products per band (``device_path``).
+
+    Between rotated pixel grids (``isrot``; renderer.py:319-350, 498-524) the kernel is
+    Fourier-shifted in 2-D to ``shifts[:, a]`` and the model by ``-other_shifts[:, b]``.  The
+    host computes the two shift tables only; operator and rendering are the device's, in
+    Fourier space (``device_path() == 2``, csrc/resample_rot.hip).  Square observations only,
+    as in the reference, and rows of the FFT shape of at most ``MAX_ROW`` pixels."""
+
+    MAX_ROW = 2048  # the device's transform tables of a row live in LDS, 24 bytes per pixel
 
     def __init__(self, data_frame, model_frame, padding=10):
         from . import interpolation
@@ -176,9 +183,12 @@ class ResolutionRenderer(Renderer):
         super().__init__(data_frame, model_frame)
         self.angle, self.h = interpolation.get_angles(data_frame.wcs, model_frame.wcs)
         self.isrot = (np.abs(self.angle[1]) ** 2) > np.finfo(float).eps
-        if self.isrot:
-            raise NotImplementedError("ResolutionRenderer between rotated pixel grids")
         lr_shape = data_frame.shape[1:]
+        if self.isrot and lr_shape[0] != lr_shape[1]:
+            # (the reference's np.stack below raises for these, renderer.py:274)
+            raise NotImplementedError(
+                "ResolutionRenderer between rotated pixel grids needs a square observation, "
+                "this one has {} x {} pixels".format(*lr_shape))
         pixels = np.stack((np.arange(lr_shape[0]), np.arange(lr_shape[1])), axis=1)
         coord_hr = data_frame.convert_pixel_to(model_frame, pixel=pixels)
         diff_psf, psf_lr_hr = self.build_diffkernel(data_frame, model_frame)
@@ -191,6 +201,11 @@ class ResolutionRenderer(Renderer):
         assert self.small_axis
         self._fft_shape = fft._get_fft_shape(psf_lr_hr, np.zeros(model_frame.shape), padding=3,
                                              axes=[-2, -1], max=False)
+        if self.isrot and self._fft_shape[1] > self.MAX_ROW:
+            raise NotImplementedError(
+                "ResolutionRenderer between rotated pixel grids: the device's transform tables "
+                "take rows of up to {} pixels, the FFT shape of this one has {}".format(
+                    self.MAX_ROW, int(self._fft_shape[1])))
         if (self._fft_shape[-2] < diff_psf.shape[-2]) or (self._fft_shape[-1] < diff_psf.shape[-1]):
             diff_psf = fft.Fourier(fft._centered(
                 diff_psf.image, np.array([diff_psf.shape[0] + 1, *self._fft_shape]) - 1))
@@ -200,6 +215,21 @@ class ResolutionRenderer(Renderer):
             (model_frame.Ny % 2) == 0)
         center_x = int(Fx / 2.0 - (Fx - model_frame.Nx) / 2.0) - ((Fx % 2) != 0) * (
             (model_frame.Nx % 2) == 0)
+        self._device = None
+        self._class = (int(self.diff_kernel.image.shape[0]), int(lr_shape[0]), int(lr_shape[1]))
+        if self.isrot:
+            # positions of the low-resolution pixels along the observation's own axes, from its
+            # diagonal pixels (renderer.py:319-350): pixel (a, b) lies at shifts[:, a] +
+            # other_shifts[:, b] on the centred, padded model grid
+            cos, sin = self.angle
+            dy, dx = coord_hr[:, 0] - center_y, coord_hr[:, 1] - center_x
+            self.Y_unrot = dy * cos - dx * sin
+            self.X_unrot = dx * cos + dy * sin
+            self.shifts = np.array([self.Y_unrot * cos, -self.Y_unrot * sin])
+            self.other_shifts = np.array([sin * self.X_unrot, cos * self.X_unrot])
+            # (the operator -- the kernel Fourier-shifted in 2-D to every shifts[:, a], times
+            # h^2 -- is made on the device, in Fourier space: smi_resampler_create_rotated)
+            return
         self.shifts = coord_hr.T.copy()
         self.shifts[0] -= center_y
         self.shifts[1] -= center_x
@@ -208,7 +238,6 @@ class ResolutionRenderer(Renderer):
         op = self._shift_along(self.diff_kernel.image, self.shifts[0], axis=1)  # (C, n_a, Fy, Fx)
         self._resconv_op = (np.array(op, dtype=model_frame.dtype) * self.h**2).reshape(
             op.shape[0], op.shape[1], -1)
-        self._device = None
 
     def build_diffkernel(self, data_frame, model_frame):
         """Difference kernel between the observed PSF, interpolated to the model pixels,
@@ -250,7 +279,16 @@ class ResolutionRenderer(Renderer):
         """``(A, Pt, (Fy, Fx))``: the two host operators as the device takes them, float32 --
         ``A`` (C, n_a, Fy Fx), the kernel shifted to every low-resolution row, and ``Pt``
         (Fx, Fx n_b), which shifts one padded row to every low-resolution column (kept: it is
-        small, and a catalogue fit asks for it once per batch the blend is in)."""
+        small, and a catalogue fit asks for it once per batch the blend is in).
+
+        Between rotated grids: ``(kernel, h**2, shifts, other_shifts, (Fy, Fx))`` -- the padded
+        difference kernel (C, Fy, Fx) in float32 and the two shift tables (2, n_a), (2, n_b)
+        in float64; the device makes the operator from them."""
+        if self.isrot:
+            return (np.ascontiguousarray(self.diff_kernel.image, dtype=np.float32),
+                    float(self.h) ** 2, np.ascontiguousarray(self.shifts, dtype=np.float64),
+                    np.ascontiguousarray(self.other_shifts, dtype=np.float64),
+                    tuple(int(n) for n in self._fft_shape))
         if getattr(self, "_host_ops", None) is None:
             Fy, Fx = self._fft_shape
             n_b = self.other_shifts.shape[1]
@@ -265,9 +303,7 @@ class ResolutionRenderer(Renderer):
     def shape_class(self):
         """``(C, n_a, n_b, Fy, Fx)``: observations that agree in it are evaluated together in
         a device batch (``smi_batch_attach_lowres_blend``)."""
-        C, n_a, _ = self._resconv_op.shape
-        return (int(C), int(n_a), int(self.other_shifts.shape[1])) + tuple(
-            int(n) for n in self._fft_shape)
+        return self._class + tuple(int(n) for n in self._fft_shape)
 
     def operator_bytes(self):
         """Device memory of the transformed operator ``E`` of this renderer in a batch:
@@ -278,8 +314,10 @@ class ResolutionRenderer(Renderer):
     def on_spectral_path(self):
         """True unless the dense products were asked for (``device_path(0)``) or the rows are
         too long for the device's transform tables; needs no device.  (The shift operator this
-        class builds is circulant by construction; the device checks what it is handed.)"""
-        return not getattr(self, "_dense", False) and self._fft_shape[1] <= 2048
+        class builds is circulant by construction; the device checks what it is handed.)
+        False between rotated grids: those have a path of their own."""
+        return (not self.isrot and not getattr(self, "_dense", False)
+                and self._fft_shape[1] <= 2048)
 
     def _resampler(self):
         """Device handle holding the two operators (built on first use)."""
@@ -290,18 +328,26 @@ class ResolutionRenderer(Renderer):
 
             lib = _lib.load()
             C, n_a, n_b, Fy, Fx = self.shape_class()
-            A, Pt, _ = self._operators()
             handle = ctypes.c_void_p()
-            _lib.check(lib.smi_resampler_create(
-                _lib.ptr(A, ctypes.c_float), _lib.ptr(Pt, ctypes.c_float), C, n_a, n_b, Fy, Fx,
-                ctypes.byref(handle)))
+            if self.isrot:
+                kernel, scale, shifts, other_shifts, _ = self._operators()
+                _lib.check(lib.smi_resampler_create_rotated(
+                    _lib.ptr(kernel, ctypes.c_float), scale, _lib.ptr(shifts, ctypes.c_double),
+                    _lib.ptr(other_shifts, ctypes.c_double), C, n_a, n_b, Fy, Fx,
+                    ctypes.byref(handle)))
+            else:
+                A, Pt, _ = self._operators()
+                _lib.check(lib.smi_resampler_create(
+                    _lib.ptr(A, ctypes.c_float), _lib.ptr(Pt, ctypes.c_float), C, n_a, n_b, Fy,
+                    Fx, ctypes.byref(handle)))
             self._device = (lib, handle, (C, n_a, n_b))
         return self._device
 
     def device_path(self, path=None):
         """How the device evaluates the operator: 1 = through transforms along x (the shift
-        operator the reference builds is circulant), 0 = two dense products per band.
-        ``device_path(0)`` switches to the dense products (parity checks)."""
+        operator the reference builds is circulant), 0 = two dense products per band, 2 = the
+        2-D Fourier-space contraction between rotated grids.  ``device_path(0)`` switches to
+        the dense products (parity checks); a rotated renderer stays on path 2."""
         import ctypes
 
         from . import _lib
