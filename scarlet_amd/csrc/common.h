@@ -46,6 +46,33 @@ inline bool in_buffer(int64_t off, int64_t need, int64_t size) {
     return off >= 0 && need >= 0 && off <= size && need <= size - off;
 }
 
+// A device allocation that lives as long as its scope (at least one element, so `p` is never
+// null after alloc); upload: alloc, then a blocking copy of `n` host elements.
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t n) {
+        return hipMalloc(reinterpret_cast<void **>(&p), (n ? n : 1) * sizeof(T));
+    }
+    hipError_t upload(const T *h, size_t n) {
+        hipError_t e = alloc(n);
+        if (e != hipSuccess || n == 0) return e;
+        return hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice);
+    }
+};
+
+// The four events around the three launches of a timed entry, destroyed with their scope.
+struct Events {
+    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~Events() {
+        for (hipEvent_t ev : e)
+            if (ev) (void)hipEventDestroy(ev);
+    }
+};
+
 // Raise a kernel's dynamic-LDS limit to `lds` bytes on the CURRENT device.  Function
 // attributes live per device, so one process driving several GPUs (fit_blends(devices=...))
 // has to configure each of them; `configured` is the caller's static per-kernel table.

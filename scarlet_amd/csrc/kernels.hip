@@ -3410,10 +3410,10 @@ static void pool_free(void *p, size_t cap) {
 }
 
 template <typename T>
-struct DevBuf {
+struct PooledDevBuf {
     T *p = nullptr;
     size_t cap = 0;
-    ~DevBuf() {
+    ~PooledDevBuf() {
         if (p) pool_free(p, cap);
     }
     hipError_t alloc(size_t n) {
@@ -3430,8 +3430,8 @@ template <typename T>
 int sweep_host_buffers(T *flat_img, int32_t n_pix, const SweepPlanHost &plan, T min_gradient) {
     const size_t lds = (size_t)n_pix * sizeof(T);
     if (plan.n_entries == 0) return SMI_OK;
-    DevBuf<T> d_img, d_wt;
-    DevBuf<int32_t> d_ls, d_pix, d_cnt, d_nbr;
+    PooledDevBuf<T> d_img, d_wt;
+    PooledDevBuf<int32_t> d_ls, d_pix, d_cnt, d_nbr;
     std::vector<T> wt(plan.wt.size());
     for (size_t i = 0; i < wt.size(); ++i) wt[i] = (T)plan.wt[i];
     SMI_HIP(d_img.upload(flat_img, n_pix));
@@ -3488,9 +3488,9 @@ int sweep_many_host_buffers(T *images, int32_t n_img, int32_t n_pix,
         for (double w : p.wt) wt.push_back((T)w);
     }
     if (pix.empty()) return SMI_OK;
-    DevBuf<T> d_img, d_wt;
-    DevBuf<int32_t> d_ls, d_pix, d_cnt, d_nbr;
-    DevBuf<SweepManyDesc> d_desc;
+    PooledDevBuf<T> d_img, d_wt;
+    PooledDevBuf<int32_t> d_ls, d_pix, d_cnt, d_nbr;
+    PooledDevBuf<SweepManyDesc> d_desc;
     SMI_HIP(d_img.upload(images, (size_t)n_img * n_pix));
     SMI_HIP(d_wt.upload(wt.data(), wt.size()));
     SMI_HIP(d_ls.upload(ls.data(), ls.size()));
@@ -3516,8 +3516,8 @@ template <typename T>
 int apply_filter_host_buffers(const T *image, int32_t H, int32_t W, const T *values,
                               int32_t n_taps, const int32_t *ys, const int32_t *ye,
                               const int32_t *xs, const int32_t *xe, T *result) {
-    DevBuf<T> d_img, d_val, d_out;
-    DevBuf<int32_t> d_ys, d_ye, d_xs, d_xe;
+    PooledDevBuf<T> d_img, d_val, d_out;
+    PooledDevBuf<int32_t> d_ys, d_ye, d_xs, d_xe;
     const size_t n = (size_t)H * W;
     SMI_HIP(d_img.upload(image, n));
     SMI_HIP(d_val.upload(values, n_taps));

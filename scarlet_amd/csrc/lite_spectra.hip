@@ -213,22 +213,6 @@ __global__ __launch_bounds__(kThreads) void spectra_reduce_kernel(const SpectraA
 }
 
 template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) {
-        return hipMalloc(reinterpret_cast<void **>(&p), (n ? n : 1) * sizeof(T));
-    }
-    hipError_t upload(const T *h, size_t n) {
-        hipError_t e = alloc(n);
-        if (e != hipSuccess || n == 0) return e;
-        return hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice);
-    }
-};
-
-template <typename T>
 int lite_spectra(int32_t device, int32_t C, int32_t kh, int32_t kw, int32_t n_blends,
                  const smi_lite_spectra_blend *blends, int32_t n_components,
                  const smi_lite_spectra_component *comps, const T *images, int64_t n_image,

@@ -64,15 +64,6 @@ __global__ __launch_bounds__(kT) void interpolate_kernel(const int32_t *row_idx,
     }
 }
 
-template <typename T>
-struct Buf {
-    T *p = nullptr;
-    ~Buf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void **>(&p), (n ? n : 1) * sizeof(T)); }
-};
-
 }  // namespace
 
 template <typename T>
@@ -80,9 +71,9 @@ int mask_valid_host_buffers(int32_t i, int32_t j, const T *image, int32_t rows, 
                             uint8_t *unchecked, uint8_t *orphans, double variance,
                             int32_t *bounds, double thresh) {
     const size_t N = (size_t)rows * cols;
-    Buf<T> d_img;
-    Buf<uint8_t> d_un, d_or;
-    Buf<int32_t> d_vis, d_b;
+    DevBuf<T> d_img;
+    DevBuf<uint8_t> d_un, d_or;
+    DevBuf<int32_t> d_vis, d_b;
     SMI_HIP(d_img.alloc(N));
     SMI_HIP(d_un.alloc(N));
     SMI_HIP(d_or.alloc(N));
@@ -109,9 +100,9 @@ int mask_interpolate_host_buffers(const int32_t *row_idx, const int32_t *col_idx
                                   uint8_t *orphans, double variance, int32_t recursive,
                                   int32_t *bounds) {
     const size_t N = (size_t)rows * cols;
-    Buf<T> d_model;
-    Buf<uint8_t> d_un, d_or;
-    Buf<int32_t> d_vis, d_b, d_r, d_c;
+    DevBuf<T> d_model;
+    DevBuf<uint8_t> d_un, d_or;
+    DevBuf<int32_t> d_vis, d_b, d_r, d_c;
     SMI_HIP(d_model.alloc(N));
     SMI_HIP(d_un.alloc(N));
     SMI_HIP(d_or.alloc(N));

@@ -319,30 +319,6 @@ int check_plan(const Plan &p, int64_t n_record, int64_t n_rendered, std::vector<
     return SMI_OK;
 }
 
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) {
-        return hipMalloc(reinterpret_cast<void **>(&p), (n ? n : 1) * sizeof(T));
-    }
-    hipError_t upload(const T *h, size_t n) {
-        hipError_t e = alloc(n);
-        if (e != hipSuccess || n == 0) return e;
-        return hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice);
-    }
-};
-
-struct Events {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Events() {
-        for (hipEvent_t ev : e)
-            if (ev) (void)hipEventDestroy(ev);
-    }
-};
-
 // milliseconds the three launches of this host thread's last call took on the device
 thread_local double g_last_launch_ms[3] = {0, 0, 0};
 

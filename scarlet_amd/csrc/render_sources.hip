@@ -376,30 +376,6 @@ int check_plan(const Plan &p, std::vector<int32_t> *scene_work, std::vector<int6
     return SMI_OK;
 }
 
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) {
-        return hipMalloc(reinterpret_cast<void **>(&p), (n ? n : 1) * sizeof(T));
-    }
-    hipError_t upload(const T *h, size_t n) {
-        hipError_t e = alloc(n);
-        if (e != hipSuccess || n == 0) return e;
-        return hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice);
-    }
-};
-
-struct Events {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Events() {
-        for (hipEvent_t ev : e)
-            if (ev) (void)hipEventDestroy(ev);
-    }
-};
-
 int render_sources(const Plan &p, int32_t device, float *rendered, float *residual, double *chi2,
                    float *src_rendered, float *flux, double *launch_ms) {
     const bool want_flux = p.flags & SMI_RENDER_REWEIGHT;

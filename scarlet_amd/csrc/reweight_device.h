@@ -183,22 +183,6 @@ __device__ __forceinline__ void tile_pass(const ReweightArgs<T> &a, unsigned cha
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) {
-        return hipMalloc(reinterpret_cast<void **>(&p), (n ? n : 1) * sizeof(T));
-    }
-    hipError_t upload(const T *h, size_t n) {
-        hipError_t e = alloc(n);
-        if (e != hipSuccess || n == 0) return e;
-        return hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice);
-    }
-};
-
 constexpr int32_t kMaxCoord = 1 << 24;  // |origins| and extents: sums of a few stay in int32
 
 // every component of [comp0, comp0 + n): inside the table, and its rectangle inside its buffers

@@ -207,15 +207,6 @@ int starlet_reconstruction(const double *d_coeffs, int32_t n, int32_t H, int32_t
     return SMI_OK;
 }
 
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void **>(&p), (n ? n : 1) * sizeof(T)); }
-};
-
 int multiresolution_support(const double *d_coeffs, int32_t n, int32_t planes, int32_t H,
                             int32_t W, int64_t plane_stride, int64_t image_stride,
                             const double *sigma0, const double *thresh0, double K,

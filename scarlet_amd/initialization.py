@@ -7,6 +7,7 @@ import logging
 
 import numpy as np
 
+from ._catalog import Launcher, chunks, defaults, offsets
 from .bbox import Box
 from .morphology import get_minimal_boxsize  # noqa: F401  (reference exports it here)
 from .renderer import ConvolutionRenderer, NullRenderer
@@ -458,7 +459,6 @@ NEAR_SEEN = 1e-6
 MAX_SWEEP_PIXELS = (160 * 1024 - 1024) // 8
 MAX_STAMP = 63
 MAX_BOX_SIDE = 1 << 12
-WORKING_SET_BYTES = 1 << 30
 # |snr / min_snr - k| <= NEAR_INTEGER * k: the loop forms the S/N with float32 dots in no fixed
 # order, the device in float64; a count that close to the edge is the loop's to decide
 NEAR_INTEGER = 1e-4
@@ -594,27 +594,6 @@ def _blend_bytes(frame, n_sources, boxsize=None):
             + 8 * (tiles + 1) * C * (K * K + 3 * K))
 
 
-def _chunks(items, budget):
-    """Consecutive runs of ``(position, bytes)`` whose working sets stay within ``budget`` (a
-    blend beyond the budget is a chunk of its own)."""
-    out, run, used = [], [], 0
-    for pos, need in items:
-        if run and used + need > budget:
-            out.append(run)
-            run, used = [], 0
-        run.append(pos)
-        used += need
-    if run:
-        out.append(run)
-    return out
-
-
-def _offsets(sizes):
-    off = np.zeros(len(sizes) + 1, np.int64)
-    np.cumsum(np.asarray(sizes, np.int64), out=off[1:])
-    return off[:-1], int(off[-1])
-
-
 def _detect_cubes(obs):
     """``observations[0]._detect`` as ``build_initialization_image`` makes and keeps it: the
     data and the variance on the model frame."""
@@ -662,53 +641,9 @@ def trim_box(bounds, pixel, boxsize=None):
     return (int(pixel[0]) - half, int(pixel[1]) - half), 2 * half + 1
 
 
-class _Device:
-    """Uploads and launches of one chunk of ``init_blends`` (csrc/init_sources.hip)."""
-
-    def __init__(self, device):
-        import torch
-
-        from . import _lib
-
-        self.torch, self.lib, self.check = torch, _lib.load(), _lib.check
-        self.dev = torch.device("cuda", device)
-        self.keep = []
-        self.launches = []  # entries called, in order
-
-    def up(self, a):
-        return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
-
-    def cat(self, parts, dtype):
-        parts = [np.ascontiguousarray(p, dtype).reshape(-1) for p in parts]
-        return self.up(np.concatenate(parts) if parts else np.zeros(1, dtype))
-
-    def empty(self, n, dtype):
-        return self.torch.empty(max(int(n), 1), dtype=getattr(self.torch, np.dtype(dtype).name),
-                                device=self.dev)
-
-    def call(self, step, table, *args):
-        """One smi_init_sources_<step>_f32 launch on the current stream: ``args`` are tensors
-        (passed as pointer) or integers, after (count, host table, device table)."""
-        import ctypes
-
-        if not len(table):
-            return
-        self.launches.append(step)
-        fn = getattr(self.lib, "smi_init_sources_%s_f32" % step)
-        argv = self.table(table)
-        for a in args:
-            if isinstance(a, np.ndarray):  # (a further table: count, host, device)
-                argv += self.table(a)
-            else:
-                argv.append(ctypes.c_void_p(a.data_ptr()) if hasattr(a, "data_ptr") else a)
-        stream = ctypes.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
-        self.check(fn(*argv, stream))
-
-    def table(self, table):
-        """(count, host pointer, device pointer) of a descriptor table."""
-        d_table = self.up(table.reshape(-1).view(np.uint8) if table.size else np.zeros(8, np.uint8))
-        self.keep += [table, d_table]  # (until the stream has been synchronised)
-        return [len(table), table.ctypes.data, d_table.data_ptr()]
+def _call(dv, step, table, *args):
+    """One smi_init_sources_<step>_f32 launch through the chunk's ``Launcher``."""
+    dv.call("smi_init_sources_%s_f32" % step, table, *args, tag=step)
 
 
 def pack_chunk(blends, opts):
@@ -719,9 +654,9 @@ def pack_chunk(blends, opts):
     that a look at their values sends through ``init_all_sources``, with the reason -- non-finite
     data, or a variance that is not positive."""
     n_pix = [b[0].shape[1] * b[0].shape[2] for b in blends]
-    cube_off, n_cube = _offsets([b[0].C * n for b, n in zip(blends, n_pix)])
+    cube_off, n_cube = offsets([b[0].C * n for b, n in zip(blends, n_pix)])
     psfs = [np.asarray(b[2].psf.get_model(), np.float64) for b in blends]
-    psf_off, n_psf = _offsets([p.size for p in psfs])
+    psf_off, n_psf = offsets([p.size for p in psfs])
     data, var, loop = [], [], {}
     src_blend, src_pixel, src_spec = [], [], []
     for k, (frame, centers, obs) in enumerate(blends):
@@ -740,9 +675,9 @@ def pack_chunk(blends, opts):
             src_pixel.append(tuple(int(p) for p in np.round(frame.get_pixel(center)).astype("int")))
             src_spec.append(get_pixel_spectrum(center, (obs,), concat=False))
     ns = len(src_blend)
-    spec_off, n_spec = _offsets([blends[k][0].C for k in src_blend])
-    snr_off, n_snr = _offsets([3 * blends[k][0].C for k in src_blend])
-    plane_off, n_plane = _offsets([n_pix[k] for k in src_blend])
+    spec_off, n_spec = offsets([blends[k][0].C for k in src_blend])
+    snr_off, n_snr = offsets([3 * blends[k][0].C for k in src_blend])
+    plane_off, n_plane = offsets([n_pix[k] for k in src_blend])
     snr_t, sweep_t = np.zeros(ns, _PSF_SNR_DESC), np.zeros(ns, _SWEEP_DESC)
     spectra = np.zeros(n_spec, np.float64)
     for s, k in enumerate(src_blend):
@@ -948,7 +883,7 @@ def _run_chunk(blends, opts, device, report):
     src_blend, src_pixel = pk["src_blend"], pk["src_pixel"]
     ns = len(src_blend)
     loop = dict(pk["loop"])
-    dv = _Device(device)
+    dv = Launcher(device, pad=1)
     torch = dv.torch
     t1 = time.perf_counter()
     with torch.cuda.device(dv.dev):
@@ -958,10 +893,10 @@ def _run_chunk(blends, opts, device, report):
         d_planes = dv.empty(pk["n_plane"], np.float64)
         d_bounds, d_peaks = dv.empty(4 * ns, np.int32), dv.empty(ns, np.float64)
         if opts["fallback"]:
-            dv.call("psf_snr", pk["psf_snr"], d_data, d_var, pk["n_cube"], d_psfs, pk["n_psf"],
-                    d_snr, pk["n_snr"])
-        dv.call("sweep", pk["sweep"], d_data, d_var, pk["n_cube"], d_spec, len(pk["spectra"]),
-                d_planes, pk["n_plane"], d_bounds, d_peaks, ns)
+            _call(dv, "psf_snr", pk["psf_snr"], d_data, d_var, pk["n_cube"], d_psfs, pk["n_psf"],
+                  d_snr, pk["n_snr"])
+        _call(dv, "sweep", pk["sweep"], d_data, d_var, pk["n_cube"], d_spec, len(pk["spectra"]),
+              d_planes, pk["n_plane"], d_bounds, d_peaks, ns)
         snr = d_snr.cpu().numpy()
         bounds = d_bounds.cpu().numpy()[:4 * ns].reshape(ns, 4)
         t2 = time.perf_counter()
@@ -978,7 +913,7 @@ def _run_chunk(blends, opts, device, report):
             boxes.append(trim_box(bounds[s], src_pixel[s], opts["boxsize"]))
         cropped = [s for s in range(ns) if src_blend[s] not in loop and counts[s] > 0]
         sizes = [counts[s] * boxes[s][1] ** 2 for s in cropped]
-        out_off, n_out = _offsets(sizes)
+        out_off, n_out = offsets(sizes)
         floor_parts, floor_at, n_floor = [], {}, 0
         crop_t = np.zeros(len(cropped), _CROP_DESC)
         for j, s in enumerate(cropped):
@@ -994,8 +929,8 @@ def _run_chunk(blends, opts, device, report):
                          pk["plane_off"][s], floor_at[key], out_off[j], 25.0)
         d_floors = dv.cat(floor_parts, np.float64)
         d_out, d_flags = dv.empty(n_out, np.float64), dv.empty(len(cropped), np.int32)
-        dv.call("crop", crop_t, d_planes, pk["n_plane"], d_floors, n_floor, d_out, n_out, d_flags,
-                len(cropped))
+        _call(dv, "crop", crop_t, d_planes, pk["n_plane"], d_floors, n_floor, d_out, n_out,
+              d_flags, len(cropped))
         morphs = d_out.cpu().numpy()
         flags = d_flags.cpu().numpy()[:len(cropped)]
     t3 = time.perf_counter()
@@ -1044,10 +979,10 @@ def _run_chunk(blends, opts, device, report):
                 d_weights = dv.cat([b[2].weights for b in blends], np.float32)
                 d_morphs, d_stamps = dv.cat(sp["morphs"], np.float64), dv.cat(sp["stamps"], np.float64)
                 d_part, d_sums = dv.empty(sp["n_part"], np.float64), dv.empty(sp["n_out"], np.float64)
-                dv.call("spectra_tiles", sp["blends"], sp["components"], sp["work"], d_data,
-                        d_weights, pk["n_cube"], d_stamps, sp["n_stamp"], d_morphs, sp["n_morph"],
-                        d_part, sp["n_part"], sp["n_out"])
-                dv.call("spectra_reduce", sp["blends"], d_part, sp["n_part"], d_sums, sp["n_out"])
+                _call(dv, "spectra_tiles", sp["blends"], sp["components"], sp["work"], d_data,
+                      d_weights, pk["n_cube"], d_stamps, sp["n_stamp"], d_morphs, sp["n_morph"],
+                      d_part, sp["n_part"], sp["n_out"])
+                _call(dv, "spectra_reduce", sp["blends"], d_part, sp["n_part"], d_sums, sp["n_out"])
                 sums = d_sums.cpu().numpy()
             for k, parameters, C, K, off in sp["taken"]:
                 E = K * K + 3 * K
@@ -1134,12 +1069,11 @@ def init_blends(frames, centers, observations, device=None, _working_set_bytes=N
     opts = _options(options)
     frames, centers, observations = list(frames), [list(c) for c in centers], list(observations)
     groups, fallback = plan_init_blends(frames, centers, observations, **options)
-    budget = WORKING_SET_BYTES if _working_set_bytes is None else _working_set_bytes
-    device = 0 if device is None else int(device)
+    budget, device = defaults(_working_set_bytes, device)
     results = [None] * len(frames)
     for idx in groups.values():
         items = [(i, _blend_bytes(frames[i], len(centers[i]), opts["boxsize"])) for i in idx]
-        for chunk in _chunks(items, budget):
+        for chunk in chunks(items, budget):
             blends = [(frames[i], centers[i], tuple(_as_tuple(observations[i]))[0]) for i in chunk]
             for i, result in zip(chunk, _run_chunk(blends, opts, device, _report)):
                 if isinstance(result, str):

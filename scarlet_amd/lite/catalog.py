@@ -10,6 +10,7 @@ blends it sends to ``weight_sources`` are measured here in NumPy (``records_of``
 
 import numpy as np
 
+from .._catalog import call_args, chunks, defaults
 from ..bbox import overlapped_slices
 from . import measure
 from .utils import insert_image
@@ -169,14 +170,10 @@ def _run_chunk(packed, key, device, keep_flux):
               else (ctypes.c_float, lib.smi_lite_measure_f32))
     out = np.empty(packed["n_out"], dtype) if keep_flux else None
     records = np.zeros((len(packed["sources"]), C, RECORD), np.float64)
-    args = [device, C, kh, kw]
-    for name in ("blends", "sources", "comps"):
-        args += [len(packed[name]), packed[name].ctypes.data]
-    for arr in (packed["images"], packed["stamps"], packed["seds"], packed["morphs"]):
-        args += [_lib.ptr(arr, ct), arr.size]
-    args += [_lib.ptr(out, ct), 0 if out is None else out.size]
-    args += [_lib.ptr(records, ctypes.c_double), records.size]
-    _lib.check(fn(*args))
+    args = call_args([packed[name] for name in ("blends", "sources", "comps")],
+                     [(packed[name], ct) for name in ("images", "stamps", "seds", "morphs")],
+                     [(out, ct), (records, ctypes.c_double)])
+    _lib.check(fn(device, C, kh, kw, *args))
     return records, out
 
 
@@ -233,14 +230,13 @@ def measure_blends(blends, mask_footprint=True, keep_flux=False, device=None,
     they were.  Blends ``plan_measure_blends`` lists as fallback take ``weight_sources`` and
     NumPy.  ``device``: GPU index of the batches (default 0)."""
     blends = list(blends)
-    budget = measure.WORKING_SET_BYTES if _working_set_bytes is None else _working_set_bytes
-    device = 0 if device is None else int(device)
+    budget, device = defaults(_working_set_bytes, device)
     groups, fallback = plan_measure_blends(blends)
     tables = [np.zeros(len(b.sources), table_dtype(b.observation.images.shape[0])) for b in blends]
     for key, idx in groups.items():
         plans = [measure._plan_blend(blends[i]) for i in idx]
         table_of = {id(p): tables[i] for p, i in zip(plans, idx)}
-        for chunk in measure._chunks(plans, key, budget):
+        for chunk in chunks([(p, measure._plan_bytes(p, key)) for p in plans], budget):
             packed = measure._pack(chunk, key, mask_footprint)
             records, out = _run_chunk(packed, key, device, keep_flux)
             _fill_chunk(chunk, [table_of[id(p)] for p in chunk], packed, records)

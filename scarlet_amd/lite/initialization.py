@@ -16,6 +16,7 @@ from functools import partial
 
 import numpy as np
 
+from .._catalog import Launcher, chunks, defaults, offsets
 from ..bbox import Box, overlapped_slices
 from ..detect import get_detect_wavelets, get_detect_wavelets_batch
 from ..initialization import get_minimal_boxsize, trim_morphology
@@ -291,9 +292,6 @@ def parameterize_sources(sources, observation, parameterization):
 # ---------------------------------------------------------------------------
 # init_blends: init_all_sources_wavelets for a catalogue, device batches per group
 # ---------------------------------------------------------------------------
-# Device working set of one chunk (wavelets, coadds, images, variance, the state of the mask
-# tasks): a group whose blends need more is cut into chunks.
-WORKING_SET_BYTES = 1 << 30
 # lite_init.hip: frame sides, pixels of a frame (one workgroup fills a mask), stamp sides,
 # wavelet planes; a blend beyond them takes init_all_sources_wavelets
 _MAX_EXTENT = 1 << 14
@@ -443,28 +441,6 @@ def _init_bytes(obs, n_sources, n_planes, key):
             + stamp * (wdtype.itemsize + 8) + n_sources * 3 * 7 * n)
 
 
-def _init_chunks(items, key, budget):
-    """Consecutive runs of ``(position, bytes)`` whose working sets stay within ``budget``
-    (a blend beyond the budget is a chunk of its own)."""
-    out, run, used = [], [], 0
-    for pos, need in items:
-        if run and used + need > budget:
-            out.append(run)
-            run, used = [], 0
-        run.append(pos)
-        used += need
-    if run:
-        out.append(run)
-    return out
-
-
-def _offsets(sizes):
-    """Start of every item of a packed buffer, and the total."""
-    off = np.zeros(len(sizes) + 1, np.int64)
-    np.cumsum(sizes, out=off[1:])
-    return off[:-1], int(off[-1])
-
-
 def _monotonic_box(bounds, seed_value, center, grow):
     """The box ``init_monotonic_morph(use_mask=True)`` cuts around ``center`` for a mask with
     ``bounds`` whose seed holds ``seed_value``; None when nothing is left.  (The size rule is
@@ -499,48 +475,11 @@ def _solve_pairs(sums, dtype):
     return seds
 
 
-class _Chunk:
-    """Device buffers and launches of one chunk of ``init_blends`` (csrc/lite_init.hip)."""
-
-    def __init__(self, key, device):
-        import torch
-
-        from .. import _lib
-
-        self.torch, self.lib = torch, _lib.load()
-        self.check = _lib.check
-        self.wdtype, self.idtype, self.mdtype, self.C = key
-        self.dev = torch.device("cuda", device)
-
-    def up(self, a):
-        return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
-
-    def cat(self, parts, dtype):
-        parts = [np.ascontiguousarray(p, dtype).reshape(-1) for p in parts]
-        return self.up(np.concatenate(parts) if parts else np.zeros(0, dtype))
-
-    def empty(self, n, dtype):
-        return self.torch.empty(max(int(n), 1), dtype=getattr(self.torch, np.dtype(dtype).name),
-                                device=self.dev)
-
-    def call(self, step, dtype, table, *args):
-        """One smi_lite_init_<step>_<dtype> launch on the current stream: ``args`` are
-        tensors (passed as pointer) or integers, after (count, host table, device table)."""
-        import ctypes
-
-        fn = getattr(self.lib, "smi_lite_init_%s_%s" % (step, "f64" if dtype == np.float64
-                                                       else "f32"))
-        d_table = self.up(table.view(np.uint8)) if len(table) else None
-        argv = []
-        for a in args:
-            argv.append(ctypes.c_void_p(a.data_ptr()) if _is_tensor(a) else a)
-        stream = ctypes.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
-        head = [len(table), table.ctypes.data if len(table) else None,
-                d_table.data_ptr() if d_table is not None else None]
-        if step in ("snr", "taps", "fit"):
-            head = [self.C] + head
-        self.check(fn(*(head + argv + [stream])))
-        return d_table  # (kept alive by the caller until the stream has been synchronised)
+def _call(ch, C, step, dtype, table, *args):
+    """One smi_lite_init_<step>_<dtype> launch through the chunk's ``Launcher``; the entries
+    whose kernels loop over the bands take ``C`` first."""
+    entry = "smi_lite_init_%s_%s" % (step, "f64" if dtype == np.float64 else "f32")
+    ch.call(entry, table, *args, head=(C,) if step in ("snr", "taps", "fit") else (), tag=step)
 
 
 def _run_init_chunk(blends, key, opts, device):
@@ -548,14 +487,14 @@ def _run_init_chunk(blends, key, opts, device):
     ``(observation, centers, wavelets)``; returns the list of their source lists.  Three
     steps: the detection coefficients in one device buffer, the launches with the host
     decisions between them, the assembly of the sources on the host."""
-    ch = _Chunk(key, device)
+    ch = Launcher(device)
     with ch.torch.cuda.device(ch.dev):
-        d_wavelets, n_planes = _chunk_wavelets(ch, blends, opts)
-        state = _chunk_launches(ch, blends, opts, d_wavelets, n_planes)
+        d_wavelets, n_planes = _chunk_wavelets(ch, key, blends, opts)
+        state = _chunk_launches(ch, key, blends, opts, d_wavelets, n_planes)
     return _chunk_assemble(blends, state)
 
 
-def _chunk_wavelets(ch, blends, opts):
+def _chunk_wavelets(ch, key, blends, opts):
     """The detection coefficients of the chunk's blends, one after another in one device
     buffer (those not passed in come from one ``get_detect_wavelets_batch`` call for all of
     them and never visit the host), and the number of planes of every blend.  Passed arrays
@@ -563,8 +502,8 @@ def _chunk_wavelets(ch, blends, opts):
     n_planes = [_n_planes(obs, wav, opts["scales"]) for obs, _, wav in blends]
     sizes = [p * obs.images.shape[1] * obs.images.shape[2]
              for p, (obs, _, _) in zip(n_planes, blends)]
-    off, total = _offsets(sizes)
-    d_wavelets = ch.empty(total, ch.wdtype)
+    off, total = offsets(sizes)
+    d_wavelets = ch.empty(total, key[0])
     missing = [obs for obs, _, wav in blends if wav is None]
     computed = iter(get_detect_wavelets_batch([obs.images for obs in missing],
                                               [obs.variance for obs in missing],
@@ -581,22 +520,21 @@ def _chunk_wavelets(ch, blends, opts):
 _PSF, _ONE, _TWO, _NONE = 0, 1, 2, 3  # component classes; _NONE: neither bulge nor disk
 
 
-def _chunk_launches(ch, blends, opts, d_wavelets, n_planes):
+def _chunk_launches(ch, key, blends, opts, d_wavelets, n_planes):
     """Everything of a chunk that touches the device: packs and uploads the inputs, runs the
     seven (eight with 2 -> 1 fallbacks) launches of lite_init.hip and decides on the host, as
     ``init_wavelet_source`` does, what follows from each.  Returns what the assembly needs,
     all of it in host memory."""
     from types import SimpleNamespace
 
-    C = ch.C
-    wdtype, idtype, mdtype = ch.wdtype, ch.idtype, ch.mdtype
-    keep = []  # descriptor tables on the device, until the chunk is done
+    wdtype, idtype, mdtype, C = key
+    call = partial(_call, ch, C)
     nb = len(blends)
     # ---- the three coadds
     n_pix = np.array([b[0].images.shape[1] * b[0].images.shape[2] for b in blends], np.int64)
-    wav_off, n_wav = _offsets(np.array(n_planes, np.int64) * n_pix)
-    coadd_off, n_coadd = _offsets(3 * n_pix)
-    image_off, n_image = _offsets(C * n_pix)
+    wav_off, n_wav = offsets(np.array(n_planes, np.int64) * n_pix)
+    coadd_off, n_coadd = offsets(3 * n_pix)
+    image_off, n_image = offsets(C * n_pix)
     coadds = np.zeros(nb, _COADD_DESC)
     for b in range(nb):
         sel = [_plane_selection(sl, n_planes[b])
@@ -604,19 +542,19 @@ def _chunk_launches(ch, blends, opts, d_wavelets, n_planes):
         coadds[b] = (n_planes[b], [s[0] for s in sel], [s[1] for s in sel], [s[2] for s in sel],
                      (0, 0), n_pix[b], wav_off[b], coadd_off[b])
     d_coadds = ch.empty(n_coadd, wdtype)
-    keep.append(ch.call("coadd", wdtype, coadds, d_wavelets, n_wav, d_coadds, n_coadd))
+    call("coadd", wdtype, coadds, d_wavelets, n_wav, d_coadds, n_coadd)
     # ---- per source: SNR sums, centre taps; per blend: the spectrum of the model PSF
     d_images = ch.cat([b[0].images for b in blends], idtype)
     d_variance = ch.cat([b[0].variance for b in blends], idtype)
-    psf_off, n_psf = _offsets([b[0].psfs.size for b in blends])
+    psf_off, n_psf = offsets([b[0].psfs.size for b in blends])
     d_psfs = ch.cat([b[0].psfs for b in blends], idtype)
     stamps = [np.broadcast_to(np.asarray(b[0].diff_kernel.image),
                               (C,) + np.shape(b[0].diff_kernel.image)[1:]) for b in blends]
-    stamp_off, n_stamp = _offsets([s.size for s in stamps])
+    stamp_off, n_stamp = offsets([s.size for s in stamps])
     d_stamps_w = ch.cat(stamps, wdtype)
     d_stamps_m = d_stamps_w if mdtype == wdtype else ch.cat(stamps, mdtype)
     model_psfs = [np.asarray(b[0].model_psf)[0] for b in blends]
-    mpsf_off, n_mpsf = _offsets([m.size for m in model_psfs])
+    mpsf_off, n_mpsf = offsets([m.size for m in model_psfs])
     d_model_psfs = ch.cat(model_psfs, mdtype)
 
     src_blend = np.array([b for b in range(nb) for _ in blends[b][1]], np.int64)
@@ -639,12 +577,10 @@ def _chunk_launches(ch, blends, opts, d_wavelets, n_planes):
     d_snr = ch.empty(2 * ns, np.float64)
     d_taps = ch.empty(ns * (C + 1), wdtype)
     d_ptaps = ch.empty(nb * (C + 1), mdtype)
-    keep.append(ch.call("snr", idtype, snr_t, d_images, d_variance, n_image, d_psfs, n_psf,
-                        d_snr, 2 * ns))
-    keep.append(ch.call("taps", wdtype, taps_t, d_coadds, n_coadd, d_stamps_w, n_stamp, d_taps,
-                        ns * (C + 1)))
-    keep.append(ch.call("taps", mdtype, ptaps_t, d_model_psfs, n_mpsf, d_stamps_m, n_stamp,
-                        d_ptaps, nb * (C + 1)))
+    call("snr", idtype, snr_t, d_images, d_variance, n_image, d_psfs, n_psf, d_snr, 2 * ns)
+    call("taps", wdtype, taps_t, d_coadds, n_coadd, d_stamps_w, n_stamp, d_taps, ns * (C + 1))
+    call("taps", mdtype, ptaps_t, d_model_psfs, n_mpsf, d_stamps_m, n_stamp, d_ptaps,
+         nb * (C + 1))
     snr = d_snr.cpu().numpy()[:2 * ns].reshape(ns, 2)
     taps = d_taps.cpu().numpy()[:ns * (C + 1)].reshape(ns, C + 1)
     ptaps = d_ptaps.cpu().numpy()[:nb * (C + 1)].reshape(nb, C + 1)
@@ -678,8 +614,8 @@ def _chunk_launches(ch, blends, opts, d_wavelets, n_planes):
         d_visited, d_unchecked = ch.empty(pix, np.int32), ch.empty(pix, np.uint8)
         d_orphans = ch.empty(pix, np.uint8)
         d_bounds, d_seeds = ch.empty(4 * len(tasks), np.int32), ch.empty(len(tasks), wdtype)
-        keep.append(ch.call("masks", wdtype, table, d_coadds, n_coadd, d_visited, d_unchecked,
-                            d_orphans, pix, d_valid, n_valid, d_bounds, d_seeds, len(tasks)))
+        call("masks", wdtype, table, d_coadds, n_coadd, d_visited, d_unchecked, d_orphans, pix,
+             d_valid, n_valid, d_bounds, d_seeds, len(tasks))
         bounds = d_bounds.cpu().numpy()[:4 * len(tasks)].reshape(-1, 4)
         seeds = d_seeds.cpu().numpy()
         return [(_monotonic_box(bounds[k], seeds[k], src_center[s], grows[plane]),
@@ -712,7 +648,7 @@ def _chunk_launches(ch, blends, opts, d_wavelets, n_planes):
             box, valid_off = found[(s, plane)]
             if box is not None:
                 comps.append((s, plane, box, valid_off))
-    out_off, n_out = _offsets([c[2].shape[0] * c[2].shape[1] for c in comps])
+    out_off, n_out = offsets([c[2].shape[0] * c[2].shape[1] for c in comps])
     crop_t = np.zeros(len(comps), _CROP_DESC)
     comp_at = {}
     for k, (s, plane, box, valid_off) in enumerate(comps):
@@ -722,9 +658,7 @@ def _chunk_launches(ch, blends, opts, d_wavelets, n_planes):
                      coadd_off[b] + plane * n_pix[b], valid_off, out_off[k])
         comp_at[(s, plane)] = k
     d_out = ch.empty(n_out, wdtype)
-    if len(comps):
-        keep.append(ch.call("crop", wdtype, crop_t, d_coadds, n_coadd, d_valid, n_valid, d_out,
-                            n_out))
+    call("crop", wdtype, crop_t, d_coadds, n_coadd, d_valid, n_valid, d_out, n_out)
     pairs = [s for s in range(ns) if kind[s] == _TWO]
     fit_t = np.zeros(len(pairs), _FIT_DESC)
     for k, s in enumerate(pairs):
@@ -741,9 +675,8 @@ def _chunk_launches(ch, blends, opts, d_wavelets, n_planes):
     d_sums = ch.empty(len(pairs) * C * 5, np.float64)
     if len(pairs):
         d_stamps_fit = ch.cat(stamps, np.float64)
-        keep.append(ch.call("fit", wdtype, fit_t, d_out, n_out, d_images,
-                            int(idtype == np.float64), n_image, d_stamps_fit, n_stamp, d_sums,
-                            len(pairs) * C * 5))
+        call("fit", wdtype, fit_t, d_out, n_out, d_images, int(idtype == np.float64), n_image,
+             d_stamps_fit, n_stamp, d_sums, len(pairs) * C * 5)
     morphs = d_out.cpu().numpy()
     sums = d_sums.cpu().numpy()[:len(pairs) * C * 5].reshape(len(pairs), C, 5)
     boxes = {key: comps[k][2] for key, k in comp_at.items()}
@@ -827,8 +760,7 @@ def init_blends(observations, centers, min_snr=50, bulge_grow=5, disk_grow=5, us
     ``parameterize_sources`` before fitting."""
     observations, centers = list(observations), [list(c) for c in centers]
     wavelets = [None] * len(observations) if wavelets is None else list(wavelets)
-    budget = WORKING_SET_BYTES if _working_set_bytes is None else _working_set_bytes
-    device = 0 if device is None else int(device)
+    budget, device = defaults(_working_set_bytes, device)
     groups, fallback = plan_init_blends(observations, centers, wavelets, bulge_slice, disk_slice,
                                         scales)
     opts = dict(min_snr=min_snr, bulge_grow=bulge_grow, disk_grow=disk_grow, use_psf=use_psf,
@@ -842,7 +774,7 @@ def init_blends(observations, centers, min_snr=50, bulge_grow=5, disk_grow=5, us
                 continue
             planes = _n_planes(observations[i], wavelets[i], scales)
             items.append((i, _init_bytes(observations[i], len(centers[i]), planes, key)))
-        for chunk in _init_chunks(items, key, budget):
+        for chunk in chunks(items, budget):
             blends = [(observations[i], centers[i], wavelets[i]) for i in chunk]
             for i, result in zip(chunk, _run_init_chunk(blends, key, opts, device)):
                 sources[i] = result
@@ -1001,41 +933,29 @@ def _trim_box(bounds, center):
                            (center[1] - half, center[1] + half + 1))
 
 
-# launches of the last chunk of init_blends_main, by entry (tools/lite_init_main_time.py)
-_MAIN_LAUNCHES = []
-
-
 def _run_main_chunk(blends, key, opts, device):
     """``init_all_sources_main`` of the blends of one chunk: ``blends`` is a list of
     ``(observation, centers, detect)``; returns the list of their source lists."""
-    idtype, mdtype, C = key
-    ch = _Chunk((idtype, idtype, mdtype, C), device)
+    ch = Launcher(device)
     with ch.torch.cuda.device(ch.dev):
-        state = _main_launches(ch, blends, opts)
+        state = _main_launches(ch, key, blends, opts)
     return _main_assemble(blends, state)
 
 
-def _main_launches(ch, blends, opts):
+def _main_launches(ch, key, blends, opts):
     """Everything of a chunk that touches the device: packs and uploads the inputs, runs the
     (at most) eight launches -- main_coadd, snr, taps twice, main_sweep, then after the host
     has decided class and box of every source crop, main_split and fit -- and returns what the
     assembly needs, all of it in host memory."""
     from types import SimpleNamespace
 
-    C, idtype, mdtype = ch.C, ch.idtype, ch.mdtype
-    keep = []  # descriptor tables on the device, until the chunk is done
-    del _MAIN_LAUNCHES[:]
-
-    def call(step, dtype, table, *args):
-        if len(table):
-            _MAIN_LAUNCHES.append(step)
-        keep.append(ch.call(step, dtype, table, *args))
-
+    idtype, mdtype, C = key
+    call = partial(_call, ch, C)
     nb = len(blends)
     shapes = [b[0].images.shape[1:] for b in blends]
     n_pix = np.array([h * w for h, w in shapes], np.int64)
-    image_off, n_image = _offsets(C * n_pix)
-    detect_off, n_detect = _offsets(n_pix)
+    image_off, n_image = offsets(C * n_pix)
+    detect_off, n_detect = offsets(n_pix)
     d_images = ch.cat([b[0].images for b in blends], idtype)
     d_variance = ch.cat([b[0].variance for b in blends], idtype)
     # ---- the detection images: the passed ones, the coadds of the others
@@ -1053,21 +973,21 @@ def _main_launches(ch, blends, opts):
          n_detect)
     # ---- per source: SNR sums, centre taps of the convolved detection image; per blend: the
     # spectrum of the model PSF
-    psf_off, n_psf = _offsets([b[0].psfs.size for b in blends])
+    psf_off, n_psf = offsets([b[0].psfs.size for b in blends])
     d_psfs = ch.cat([b[0].psfs for b in blends], idtype)
     stamps = [np.broadcast_to(np.asarray(b[0].diff_kernel.image),
                               (C,) + np.shape(b[0].diff_kernel.image)[1:]) for b in blends]
-    stamp_off, n_stamp = _offsets([s.size for s in stamps])
+    stamp_off, n_stamp = offsets([s.size for s in stamps])
     d_stamps_i = ch.cat(stamps, idtype)
     d_stamps_m = d_stamps_i if mdtype == idtype else ch.cat(stamps, mdtype)
     model_psfs = [np.asarray(b[0].model_psf)[0] for b in blends]
-    mpsf_off, n_mpsf = _offsets([m.size for m in model_psfs])
+    mpsf_off, n_mpsf = offsets([m.size for m in model_psfs])
     d_model_psfs = ch.cat(model_psfs, mdtype)
 
     src_blend = np.array([b for b in range(nb) for _ in blends[b][1]], np.int64)
     src_center = [c for b in blends for c in b[1]]
     ns = len(src_center)
-    swept_off, n_swept = _offsets(n_pix[src_blend])
+    swept_off, n_swept = offsets(n_pix[src_blend])
     thresh = [float(np.mean(b[0].noise_rms) * opts["thresh"]) for b in blends]
     snr_t, taps_t = np.zeros(ns, _SNR_DESC), np.zeros(ns, _TAPS_DESC)
     sweep_t = np.zeros(ns, _MAIN_SWEEP_DESC)
@@ -1116,7 +1036,7 @@ def _main_launches(ch, blends, opts):
     # ---- cut-outs divided by their maximum; bulge and disk of the two-component sources
     sizes = [boxes[s].shape[0] * boxes[s].shape[1] * (3 if kind[s] == _TWO else 1)
              for s in boxes]
-    out_off, n_out = _offsets(sizes)
+    out_off, n_out = offsets(sizes)
     offs = dict(zip(boxes, (int(o) for o in out_off)))
     crop_t = np.zeros(len(boxes), _CROP_DESC)
     for k, (s, box) in enumerate(boxes.items()):
@@ -1209,8 +1129,7 @@ def init_blends_main(observations, centers, detect=None, min_snr=50, use_mask=Fa
     result with ``parameterize_sources`` before fitting."""
     observations, centers = list(observations), [list(c) for c in centers]
     detect = [None] * len(observations) if detect is None else list(detect)
-    budget = WORKING_SET_BYTES if _working_set_bytes is None else _working_set_bytes
-    device = 0 if device is None else int(device)
+    budget, device = defaults(_working_set_bytes, device)
     groups, fallback = plan_init_blends_main(observations, centers, detect, use_mask, percentile)
     opts = dict(min_snr=min_snr, percentile=percentile, thresh=thresh)
     sources = [None] * len(observations)
@@ -1221,7 +1140,7 @@ def init_blends_main(observations, centers, detect=None, min_snr=50, use_mask=Fa
                 sources[i] = []
                 continue
             items.append((i, _main_bytes(observations[i], len(centers[i]), key)))
-        for chunk in _init_chunks(items, key, budget):
+        for chunk in chunks(items, budget):
             blends = [(observations[i], centers[i], detect[i]) for i in chunk]
             for i, result in zip(chunk, _run_main_chunk(blends, key, opts, device)):
                 sources[i] = result

@@ -2,6 +2,7 @@
 
 import numpy as np
 
+from .._catalog import call_args, cat, chunks, defaults
 from ..bbox import Box, overlapped_slices
 from .utils import insert_image
 
@@ -47,10 +48,6 @@ def weight_sources(blend, mask_footprint=True):
 # ---------------------------------------------------------------------------
 # weight_blends: weight_sources for a catalogue, one device batch per group
 # ---------------------------------------------------------------------------
-# Device working set of one launch pair (packed inputs + `total` + fluxes): a group whose
-# blends need more is cut into chunks.  Large enough that a catalogue of a few thousand
-# postage-stamp blends is one chunk, small next to the memory of any device.
-WORKING_SET_BYTES = 1 << 30
 # reweight.hip: a workgroup computes a 32 x 32 tile and keeps its halo (odd row pitch) and
 # the band's stamp in at most 64 KiB of LDS; larger stamps take weight_sources
 _TILE = 32
@@ -163,21 +160,11 @@ def _plan_elements(plan):
     return 2 * C * h * w + sum(morphs.values()) + C * len(morphs) + fluxes
 
 
-def _chunks(plans, key, budget):
-    """Consecutive runs of a group's plans whose working sets stay within ``budget`` bytes
-    (a blend beyond the budget is a chunk of its own)."""
+def _plan_bytes(plan, key):
+    """Bytes of the device working set of a planned blend of group ``key`` (packed inputs,
+    ``total`` and fluxes, the stamp)."""
     dtype, C, kh, kw = key
-    out, run, used = [], [], 0
-    for p in plans:
-        need = (_plan_elements(p) + C * kh * kw) * dtype.itemsize
-        if run and used + need > budget:
-            out.append(run)
-            run, used = [], 0
-        run.append(p)
-        used += need
-    if run:
-        out.append(run)
-    return out
+    return (_plan_elements(plan) + C * kh * kw) * dtype.itemsize
 
 
 def _pack(plans, key, mask_footprint):
@@ -221,13 +208,9 @@ def _pack(plans, key, mask_footprint):
             results.append((src, out_off, shape))
             out_off += int(np.prod(shape))
             s_at += 1
-
-    def cat(parts):
-        return np.concatenate(parts) if parts else np.zeros(0, dtype)
-
-    return dict(blends=blends, sources=sources, comps=comps, images=cat(images),
-                stamps=cat(stamps), seds=cat(seds), morphs=cat(morphs), n_out=out_off,
-                results=results)
+    return dict(blends=blends, sources=sources, comps=comps, images=cat(images, dtype),
+                stamps=cat(stamps, dtype), seds=cat(seds, dtype), morphs=cat(morphs, dtype),
+                n_out=out_off, results=results)
 
 
 def _run_chunk(packed, key, device):
@@ -241,12 +224,10 @@ def _run_chunk(packed, key, device):
     ct, fn = ((ctypes.c_double, lib.smi_reweight_f64) if dtype == np.float64
               else (ctypes.c_float, lib.smi_reweight_f32))
     out = np.empty(packed["n_out"], dtype)
-    args = [device, C, kh, kw]
-    for name in ("blends", "sources", "comps"):
-        args += [len(packed[name]), packed[name].ctypes.data]
-    for arr in (packed["images"], packed["stamps"], packed["seds"], packed["morphs"], out):
-        args += [_lib.ptr(arr, ct), arr.size]
-    _lib.check(fn(*args))
+    args = call_args([packed[name] for name in ("blends", "sources", "comps")],
+                     [(packed[name], ct) for name in ("images", "stamps", "seds", "morphs")],
+                     [(out, ct)])
+    _lib.check(fn(device, C, kh, kw, *args))
     return out
 
 
@@ -291,12 +272,11 @@ def weight_blends(blends, mask_footprint=True, device=None, _working_set_bytes=N
     ``weight_sources`` (on the current device).  ``device``: GPU index of the batches
     (default 0).  Returns None."""
     blends = list(blends)
-    budget = WORKING_SET_BYTES if _working_set_bytes is None else _working_set_bytes
-    device = 0 if device is None else int(device)
+    budget, device = defaults(_working_set_bytes, device)
     groups, fallback = plan_blends(blends)
     for key, idx in groups.items():
         plans = [_plan_blend(blends[i]) for i in idx]
-        for chunk in _chunks(plans, key, budget):
+        for chunk in chunks([(p, _plan_bytes(p, key)) for p in plans], budget):
             packed = _pack(chunk, key, mask_footprint)
             out = _run_chunk(packed, key, device)
             _assign(chunk, packed, out)

@@ -9,9 +9,8 @@ chunking and packing follow ``lite/measure.py::weight_blends``."""
 
 import numpy as np
 
-# Device working set of one launch pair (packed inputs, the sums of every tile, the output): a
-# group whose blends need more is cut into chunks.
-WORKING_SET_BYTES = 1 << 30
+from .._catalog import call_args, chunks, defaults
+
 # lite_spectra.hip: side of a tile of the union box (one workgroup, one thread per pixel);
 # stamp sides; components of a blend; components whose box grown by the stamp's half meets one
 # tile (their columns share the LDS of a CU); sides of a union box.  A blend beyond them takes
@@ -209,22 +208,6 @@ def _plan_bytes(plan, key):
             + (C * kh * kw + (tiles + 1) * C * (K * K + K)) * 8)
 
 
-def _chunks(plans, key, budget):
-    """Consecutive runs of a group's plans whose working sets stay within ``budget`` bytes
-    (a blend beyond the budget is a chunk of its own)."""
-    out, run, used = [], [], 0
-    for p in plans:
-        need = _plan_bytes(p, key)
-        if run and used + need > budget:
-            out.append(run)
-            run, used = [], 0
-        run.append(p)
-        used += need
-    if run:
-        out.append(run)
-    return out
-
-
 def _pack(plans, key):
     """Descriptor tables and packed buffers of one chunk (the arguments of
     smi_lite_spectra_*)."""
@@ -263,13 +246,10 @@ def _run_chunk(packed, key, device):
     ct, fn = ((ctypes.c_double, lib.smi_lite_spectra_f64) if dtype == np.float64
               else (ctypes.c_float, lib.smi_lite_spectra_f32))
     out = np.empty(packed["n_out"], np.float64)
-    args = [device, C, kh, kw]
-    for name in ("blends", "comps"):
-        args += [len(packed[name]), packed[name].ctypes.data]
-    for arr, t in ((packed["images"], ct), (packed["stamps"], ctypes.c_double),
-                   (packed["morphs"], ct), (out, ctypes.c_double)):
-        args += [_lib.ptr(arr, t), arr.size]
-    _lib.check(fn(*args))
+    args = call_args([packed["blends"], packed["comps"]],
+                     [(packed["images"], ct), (packed["stamps"], ctypes.c_double),
+                      (packed["morphs"], ct)], [(out, ctypes.c_double)])
+    _lib.check(fn(device, C, kh, kw, *args))
     return out
 
 
@@ -301,12 +281,11 @@ def fit_spectra_blends(blends, clip=False, device=None, _working_set_bytes=None)
     through ``fit_spectra`` after the device groups.  ``device``: GPU index
     of the batches (default 0).  Returns the list of the blends."""
     blends = list(blends)
-    budget = WORKING_SET_BYTES if _working_set_bytes is None else _working_set_bytes
-    device = 0 if device is None else int(device)
+    budget, device = defaults(_working_set_bytes, device)
     groups, fallback = _plan_groups(blends, clip)
     for key, items in groups.items():
         dtype, C = key[:2]
-        for chunk in _chunks([plan for _, plan in items], key, budget):
+        for chunk in chunks([(plan, _plan_bytes(plan, key)) for _, plan in items], budget):
             packed = _pack(chunk, key)
             out = _run_chunk(packed, key, device)
             equations = _normal_equations(packed, out, C)

@@ -5,6 +5,8 @@ scarlet/measure.py:6-149).  The per-source functions are host NumPy on downloade
 
 import numpy as np
 
+from ._catalog import call_args, cat, chunks, defaults
+
 
 def _model_and_origin(component):
     if hasattr(component, "get_model"):
@@ -83,8 +85,6 @@ def moments(component, N=2, centroid=None, weight=None):
 _TILE = 16
 MAX_STAMP = 63
 MAX_BOX_SIDE = 1 << 14
-# Device working set of one call: a group whose blends need more is cut into chunks
-WORKING_SET_BYTES = 1 << 30
 _RECORD = 8    # SMI_MEASURE_SOURCES_RECORD
 _RENDERED = 3  # sum R, sum R^2, sum R^2 / w
 
@@ -160,9 +160,12 @@ def _channels(renderer, C_obs):
     return [int(c) for c in cmap]
 
 
-def _refusal(blend):
+def _refusal(blend, zero_weights=False, null_subset=False, plain_data=False):
     """``(reason, None)`` why the device path of ``measure_blends`` does not take a blend, or
-    ``(None, (C, kh, kw))``: its group.  Host only."""
+    ``(None, (C, kh, kw))``: its group.  ``render_blends`` asks with all three switches on:
+    ``zero_weights`` lets weights be zero (finite and not negative: they enter chi^2 and the
+    mask only), ``null_subset`` takes a ``NullRenderer`` of a subset of the frame's bands, and
+    ``plain_data`` wants the data to be a plain float32 array as well.  Host only."""
     from .renderer import ConvolutionRenderer, NullRenderer
 
     frame = blend.frame
@@ -189,7 +192,7 @@ def _refusal(blend):
         channels = _channels(renderer, obs.shape[0])
         if len(channels) != obs.shape[0] or not all(0 <= c < shape[0] for c in channels):
             return "an observation whose bands are not bands of the frame", None
-        if type(renderer) is NullRenderer and renderer.channel_map is not None:
+        if not null_subset and type(renderer) is NullRenderer and renderer.channel_map is not None:
             # (its rendering is the whole model: measure.snr has no value for it)
             return "a NullRenderer of a subset of the frame's bands", None
         if type(renderer) is ConvolutionRenderer:
@@ -204,11 +207,14 @@ def _refusal(blend):
                 return "ConvolutionRenderers with different stamp shapes", None
             stamp = kshape[1:]
         weights = obs.weights
-        if (type(weights) is not np.ndarray or weights.dtype != np.float32
-                or weights.shape != tuple(obs.shape)):
-            return "weights that are not a plain float32 array", None
-        if not (weights.min() > 0 and np.isfinite(weights.max())):
-            return "a weight that is zero, negative or not finite", None
+        for name, image in (("weights", weights),) + ((("data", obs.data),) if plain_data else ()):
+            if (type(image) is not np.ndarray or image.dtype != np.float32
+                    or image.shape != tuple(obs.shape)):
+                return "{} that are not a plain float32 array".format(name), None
+        low = weights.min()
+        if not ((low >= 0 if zero_weights else low > 0) and np.isfinite(weights.max())):
+            return "a weight that is {}negative or not finite".format(
+                "" if zero_weights else "zero, "), None
     kh, kw = (1, 1) if stamp is None else stamp
     return None, (int(shape[0]), int(kh), int(kw))
 
@@ -273,13 +279,19 @@ def plan_blend(blend, key):
     return dict(sources=sources, bands=bands, shape=tuple(frame.shape))
 
 
-def _region_tiles(rect, frame_hw, kh, kw):
-    """Tiles of the frame pixels a source's rendered model reaches: its box grown by the
-    stamp's half, clipped to the frame."""
+def region_of(rect, frame_hw, kh, kw):
+    """``(y0, x0, h, w)`` of the frame pixels a source's rendered model reaches: its box grown by
+    the stamp's half and clipped to the frame (``region_of`` of csrc/measure_sources.hip)."""
     y0, x0, h, w = rect
     gy0, gx0 = max(y0 - kh // 2, 0), max(x0 - kw // 2, 0)
     gh = max(min(y0 + h + kh // 2, frame_hw[0]) - gy0, 0)
     gw = max(min(x0 + w + kw // 2, frame_hw[1]) - gx0, 0)
+    return gy0, gx0, gh, gw
+
+
+def _region_tiles(rect, frame_hw, kh, kw):
+    """Tiles of the region of a source."""
+    _, _, gh, gw = region_of(rect, frame_hw, kh, kw)
     return -(-gh // _TILE) * -(-gw // _TILE)
 
 
@@ -299,19 +311,42 @@ def _plan_bytes(plan, key):
     return need
 
 
-def _chunks(items, budget):
-    """Consecutive runs of ``(position, bytes)`` whose working sets stay within ``budget`` (a
-    blend beyond the budget is a chunk of its own)."""
-    out, run, used = [], [], 0
-    for pos, need in items:
-        if run and used + need > budget:
-            out.append(run)
-            run, used = [], 0
-        run.append(pos)
-        used += need
-    if run:
-        out.append(run)
-    return out
+class _Tables:
+    """The band and component tables of a chunk with their packed buffers, filled blend by
+    blend: what ``pack`` here and ``rendering.pack`` share."""
+
+    def __init__(self, plans, key, n_comps):
+        self.C, self.kh, self.kw = key
+        self.comps = np.zeros(n_comps, _COMP_DESC)
+        self.bands = np.zeros(sum(len(p["bands"]) for p in plans), _BAND_DESC)
+        self.seds, self.morphs, self.stamps, self.weights = [], [], [], []
+        self.sed_off = self.morph_off = self.weight_off = 0
+        self.k = self.b_at = 0
+
+    def add_bands(self, plan):
+        """The rows of a blend's observed bands."""
+        _, H, W = plan["shape"]
+        for channel, stamp, weight in plan["bands"]:
+            self.bands[self.b_at] = (channel, 0, self.b_at * self.kh * self.kw, self.weight_off)
+            self.stamps.append(np.ascontiguousarray(stamp, np.float32).reshape(-1))
+            self.weights.append(np.ascontiguousarray(weight, np.float32).reshape(-1))
+            self.weight_off += H * W
+            self.b_at += 1
+
+    def add_components(self, parts):
+        """The rows of a source's components."""
+        for crect, sed, image in parts:
+            self.comps[self.k] = crect + (self.sed_off, self.morph_off)
+            self.seds.append(sed)
+            self.morphs.append(image.reshape(-1))
+            self.sed_off += self.C
+            self.morph_off += image.size
+            self.k += 1
+
+    def packed(self):
+        return dict(comps=self.comps, bands=self.bands, seds=cat(self.seds, np.float64),
+                    morphs=cat(self.morphs, np.float64), stamps=cat(self.stamps, np.float32),
+                    weights=cat(self.weights, np.float32))
 
 
 def pack(plans, key):
@@ -319,46 +354,26 @@ def pack(plans, key):
     smi_measure_sources_f32), one array per kind, and ``layout``: per blend ``(rows, live,
     C_obs)`` -- its number of sources, the rows of those with components (the device's sources,
     in order) and its observed bands."""
-    C, kh, kw = key
+    C = key[0]
     live = [(p, s) for p in plans for s in p["sources"] if s[1]]
     sources = np.zeros(len(live), _SOURCE_DESC)
-    comps = np.zeros(sum(len(s[1]) for _, s in live), _COMP_DESC)
-    bands = np.zeros(sum(len(p["bands"]) for p in plans), _BAND_DESC)
-    seds, morphs, stamps, weights, layout = [], [], [], [], []
-    sed_off = morph_off = weight_off = 0
-    k = s_at = b_at = 0
+    t = _Tables(plans, key, sum(len(s[1]) for _, s in live))
+    layout = []
+    s_at = 0
     for p in plans:
         _, H, W = p["shape"]
-        band0 = b_at
-        for channel, stamp, weight in p["bands"]:
-            bands[b_at] = (channel, 0, b_at * kh * kw, weight_off)
-            stamps.append(np.ascontiguousarray(stamp, np.float32).reshape(-1))
-            weights.append(np.ascontiguousarray(weight, np.float32).reshape(-1))
-            weight_off += H * W
-            b_at += 1
+        band0 = t.b_at
+        t.add_bands(p)
         rows = []
         for row, (rect, parts) in enumerate(p["sources"]):
             if not parts:
                 continue
             rows.append(row)
-            sources[s_at] = rect + (H, W, k, len(parts), band0, b_at - band0)
+            sources[s_at] = rect + (H, W, t.k, len(parts), band0, t.b_at - band0)
             s_at += 1
-            for crect, sed, image in parts:
-                comps[k] = crect + (sed_off, morph_off)
-                seds.append(sed)
-                morphs.append(image.reshape(-1))
-                sed_off += C
-                morph_off += image.size
-                k += 1
-        layout.append((len(p["sources"]), np.array(rows, np.int64), b_at - band0))
-
-    def cat(parts, dtype):
-        return np.concatenate(parts) if parts else np.zeros(0, dtype)
-
-    return dict(sources=sources, comps=comps, bands=bands, seds=cat(seds, np.float64),
-                morphs=cat(morphs, np.float64), stamps=cat(stamps, np.float32),
-                weights=cat(weights, np.float32), layout=layout,
-                n_record=len(live) * C * _RECORD,
+            t.add_components(parts)
+        layout.append((len(p["sources"]), np.array(rows, np.int64), t.b_at - band0))
+    return dict(t.packed(), sources=sources, layout=layout, n_record=len(live) * C * _RECORD,
                 n_rendered=int(sources["n_band"].sum()) * _RENDERED)
 
 
@@ -373,15 +388,11 @@ def _run_chunk(packed, key, device):
     lib = _lib.load()
     records = np.empty(packed["n_record"], np.float64)
     rendered = np.empty(packed["n_rendered"], np.float64)
-    args = [device, C, kh, kw]
-    for name in ("sources", "comps", "bands"):
-        args += [len(packed[name]), packed[name].ctypes.data]
-    for name, ct in (("seds", ctypes.c_double), ("morphs", ctypes.c_double),
-                     ("stamps", ctypes.c_float), ("weights", ctypes.c_float)):
-        args += [_lib.ptr(packed[name], ct), packed[name].size]
-    args += [_lib.ptr(records, ctypes.c_double), records.size,
-             _lib.ptr(rendered, ctypes.c_double), rendered.size]
-    _lib.check(lib.smi_measure_sources_f32(*args))
+    f32, f64 = ctypes.c_float, ctypes.c_double
+    args = call_args([packed[name] for name in ("sources", "comps", "bands")],
+                     [(packed["seds"], f64), (packed["morphs"], f64), (packed["stamps"], f32),
+                      (packed["weights"], f32)], [(records, f64), (rendered, f64)])
+    _lib.check(lib.smi_measure_sources_f32(device, C, kh, kw, *args))
     return records.reshape(-1, C, _RECORD), rendered.reshape(-1, _RENDERED)
 
 
@@ -523,8 +534,7 @@ def measure_blends(blends, device=None, _working_set_bytes=None, _report=None):
     import time
 
     blends = list(blends)
-    budget = WORKING_SET_BYTES if _working_set_bytes is None else _working_set_bytes
-    device = 0 if device is None else int(device)
+    budget, device = defaults(_working_set_bytes, device)
     times = dict(plan=0.0, pack=0.0, device=0.0, table=0.0, loop=0.0)
     t0 = time.perf_counter()
     groups, refused = plan_measure_blends(blends)
@@ -541,7 +551,7 @@ def measure_blends(blends, device=None, _working_set_bytes=None, _report=None):
                 fallback.append((i, "at run time: {}".format(why)))
         items = [(i, _plan_bytes(plans[i], key)) for i in idx if i in plans]
         times["plan"] += time.perf_counter() - t0
-        for chunk in _chunks(items, budget):
+        for chunk in chunks(items, budget):
             t0 = time.perf_counter()
             packed = pack([plans[i] for i in chunk], key)
             t1 = time.perf_counter()

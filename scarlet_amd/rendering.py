@@ -6,8 +6,8 @@ csrc/render_sources.hip per chunk.  Nothing here is on the fitting path."""
 
 import numpy as np
 
-from .measure import (_BAND_DESC, _COMP_DESC, MAX_STAMP, WORKING_SET_BYTES, _channels, _chunks,
-                      _covers, _leaves, _rect, _Refused)
+from ._catalog import call_args, cat, chunks, defaults
+from .measure import _BAND_DESC, _COMP_DESC, _rect, _refusal, _Tables, region_of
 from .measure import plan_blend as _measure_plan_blend
 
 _TILE = 16
@@ -20,59 +20,6 @@ _SOURCE_DESC = np.dtype([("y0", "i4"), ("x0", "i4"), ("h", "i4"), ("w", "i4"), (
                          ("out_off", "i8")], align=True)
 
 
-def _refusal(blend):
-    """``(reason, None)`` why the device path of ``render_blends`` does not take a blend, or
-    ``(None, (C, kh, kw))``: its group.  What ``measure._refusal`` takes, with two differences:
-    weights may be zero (finite and not negative: they enter chi^2 and the mask only), and a
-    ``NullRenderer`` of a subset of the frame's bands is taken; and the data must be a plain
-    float32 array.  Host only."""
-    from .renderer import ConvolutionRenderer, NullRenderer
-
-    frame = blend.frame
-    if np.dtype(frame.dtype) != np.float32:
-        return "frame dtype {} is not float32".format(np.dtype(frame.dtype).name), None
-    try:
-        for src in blend.sources:
-            if getattr(src, "frame", None) is not frame:
-                raise _Refused("a source of another frame")
-            _leaves(src)
-    except _Refused as why:
-        return str(why), None
-    shape, stamp = tuple(frame.shape), None
-    for obs in blend.observations:
-        renderer = getattr(obs, "renderer", None)
-        if renderer is None or getattr(obs, "model_frame", None) is not frame:
-            return "an observation that is not matched to the frame", None
-        if type(renderer) not in (NullRenderer, ConvolutionRenderer):
-            return "renderer {} is neither ConvolutionRenderer nor NullRenderer".format(
-                type(renderer).__name__), None
-        if (tuple(obs.shape[1:]) != shape[1:]
-                or not all(_covers(sl[1:], shape[1:]) for sl in renderer.slices)):
-            return "an observation that does not cover exactly the model frame", None
-        channels = _channels(renderer, obs.shape[0])
-        if len(channels) != obs.shape[0] or not all(0 <= c < shape[0] for c in channels):
-            return "an observation whose bands are not bands of the frame", None
-        if type(renderer) is ConvolutionRenderer:
-            kshape = tuple(np.shape(renderer.diff_kernel.image))
-            if len(kshape) != 3 or kshape[0] not in (1, obs.shape[0]):
-                return "a difference kernel that is not one stamp per band", None
-            if kshape[1] % 2 == 0 or kshape[2] % 2 == 0:
-                return "even difference-kernel stamp", None
-            if max(kshape[1:]) > MAX_STAMP:
-                return "difference-kernel stamp beyond {0} x {0}".format(MAX_STAMP), None
-            if stamp is not None and stamp != kshape[1:]:
-                return "ConvolutionRenderers with different stamp shapes", None
-            stamp = kshape[1:]
-        for name, image in (("weights", obs.weights), ("data", obs.data)):
-            if (type(image) is not np.ndarray or image.dtype != np.float32
-                    or image.shape != tuple(obs.shape)):
-                return "{} that are not a plain float32 array".format(name), None
-        if not (obs.weights.min() >= 0 and np.isfinite(obs.weights.max())):
-            return "a weight that is negative or not finite", None
-    kh, kw = (1, 1) if stamp is None else stamp
-    return None, (int(shape[0]), int(kh), int(kw))
-
-
 def plan_render_blends(blends):
     """``(groups, fallback)`` of ``render_blends``, without touching the GPU or the library: the
     positions of the blends of every device group, keyed by ``(C, kh, kw)`` -- model bands and
@@ -80,22 +27,12 @@ def plan_render_blends(blends):
     inside a group, and ``{position: reason}`` of the blends that go through the host loop."""
     groups, fallback = {}, {}
     for i, blend in enumerate(blends):
-        reason, key = _refusal(blend)
+        reason, key = _refusal(blend, zero_weights=True, null_subset=True, plain_data=True)
         if reason is None:
             groups.setdefault(key, []).append(i)
         else:
             fallback[i] = reason
     return groups, fallback
-
-
-def region_of(rect, frame_hw, kh, kw):
-    """``(y0, x0, h, w)`` of the frame pixels a source's rendered model reaches: its box grown by
-    the stamp's half and clipped to the frame (``region_of`` of csrc/measure_sources.hip)."""
-    y0, x0, h, w = rect
-    gy0, gx0 = max(y0 - kh // 2, 0), max(x0 - kw // 2, 0)
-    gh = max(min(y0 + h + kh // 2, frame_hw[0]) - gy0, 0)
-    gw = max(min(x0 + w + kw // 2, frame_hw[1]) - gx0, 0)
-    return gy0, gx0, gh, gw
 
 
 def plan_blend(blend, key):
@@ -149,59 +86,37 @@ def pack(plans, key, flags=0):
     ``n_source_out`` of the per-source cubes; and ``layout``: per blend ``(out_off, regions,
     offsets)`` -- where its cubes start, per source its region and where its cubes start (None
     for a source without components, or when the sources are not rendered)."""
-    C, kh, kw = key
     want_sources = bool(flags & (SOURCES | REWEIGHT))
     blends = np.zeros(len(plans), _BLEND_DESC)
-    live = [(i, s, g) for i, p in enumerate(plans)
-            for s, g in zip(p["sources"], p["regions"]) if s[1]]
+    live = [s for p in plans for s in p["sources"] if s[1]]
     sources = np.zeros(len(live) if want_sources else 0, _SOURCE_DESC)
-    comps = np.zeros(sum(len(s[1]) for _, s, _ in live), _COMP_DESC)
-    bands = np.zeros(sum(len(p["bands"]) for p in plans), _BAND_DESC)
-    seds, morphs, stamps, weights, data, layout = [], [], [], [], [], []
-    sed_off = morph_off = weight_off = out_off = source_off = 0
-    k = s_at = b_at = 0
+    t = _Tables(plans, key, sum(len(s[1]) for s in live))
+    data, layout = [], []
+    out_off = source_off = s_at = 0
     for i, p in enumerate(plans):
         _, H, W = p["shape"]
-        band0, comp0 = b_at, k
-        for (channel, stamp, weight), image in zip(p["bands"], p["data"]):
-            bands[b_at] = (channel, 0, b_at * kh * kw, weight_off)
-            stamps.append(np.ascontiguousarray(stamp, np.float32).reshape(-1))
-            weights.append(np.ascontiguousarray(weight, np.float32).reshape(-1))
-            data.append(np.ascontiguousarray(image, np.float32).reshape(-1))
-            weight_off += H * W
-            b_at += 1
-        n_band = b_at - band0
+        band0, comp0 = t.b_at, t.k
+        t.add_bands(p)
+        data += [np.ascontiguousarray(image, np.float32).reshape(-1) for image in p["data"]]
+        n_band = t.b_at - band0
         offsets = []
         for (rect, parts), region in zip(p["sources"], p["regions"]):
             if not parts:
                 offsets.append(None)
                 continue
             if want_sources:
-                sources[s_at] = rect + (i, k, len(parts), 0, source_off)
+                sources[s_at] = rect + (i, t.k, len(parts), 0, source_off)
                 offsets.append(source_off)
                 source_off += n_band * region[2] * region[3]
                 s_at += 1
             else:
                 offsets.append(None)
-            for crect, sed, image in parts:
-                comps[k] = crect + (sed_off, morph_off)
-                seds.append(sed)
-                morphs.append(image.reshape(-1))
-                sed_off += C
-                morph_off += image.size
-                k += 1
-        blends[i] = (H, W, comp0, k - comp0, band0, n_band, out_off)
+            t.add_components(parts)
+        blends[i] = (H, W, comp0, t.k - comp0, band0, n_band, out_off)
         layout.append((out_off, list(p["regions"]), offsets))
         out_off += n_band * H * W
-
-    def cat(parts, dtype):
-        return np.concatenate(parts) if parts else np.zeros(0, dtype)
-
-    return dict(blends=blends, sources=sources, comps=comps, bands=bands,
-                seds=cat(seds, np.float64), morphs=cat(morphs, np.float64),
-                stamps=cat(stamps, np.float32), data=cat(data, np.float32),
-                weights=cat(weights, np.float32), layout=layout, n_out=out_off,
-                n_source_out=source_off)
+    return dict(t.packed(), blends=blends, sources=sources, data=cat(data, np.float32),
+                layout=layout, n_out=out_off, n_source_out=source_off)
 
 
 def _run_chunk(packed, key, flags, device):
@@ -219,19 +134,15 @@ def _run_chunk(packed, key, flags, device):
                chi2=np.empty(len(packed["bands"]), np.float64),
                source_rendered=np.empty(packed["n_source_out"], np.float32),
                flux=np.empty(packed["n_source_out"], np.float32) if flags & REWEIGHT else None)
-    args = [device, C, kh, kw, flags]
-    for name in ("blends", "sources", "comps", "bands"):
-        args += [len(packed[name]), packed[name].ctypes.data]
-    for name, ct in (("seds", ctypes.c_double), ("morphs", ctypes.c_double),
-                     ("stamps", ctypes.c_float), ("data", ctypes.c_float),
-                     ("weights", ctypes.c_float)):
-        args += [_lib.ptr(packed[name], ct), packed[name].size]
-    for name, ct in (("rendered", ctypes.c_float), ("residual", ctypes.c_float),
-                     ("chi2", ctypes.c_double), ("source_rendered", ctypes.c_float),
-                     ("flux", ctypes.c_float)):
-        args += [_lib.ptr(out[name], ct), 0 if out[name] is None else out[name].size]
+    f32, f64 = ctypes.c_float, ctypes.c_double
+    args = call_args(
+        [packed[name] for name in ("blends", "sources", "comps", "bands")],
+        [(packed["seds"], f64), (packed["morphs"], f64), (packed["stamps"], f32),
+         (packed["data"], f32), (packed["weights"], f32)],
+        [(out["rendered"], f32), (out["residual"], f32), (out["chi2"], f64),
+         (out["source_rendered"], f32), (out["flux"], f32)])
     ms = (ctypes.c_double * 3)()
-    _lib.check(lib.smi_render_sources_f32(*args, ms))
+    _lib.check(lib.smi_render_sources_f32(device, C, kh, kw, flags, *args, ms))
     out["launch_ms"] = tuple(ms)
     return out
 
@@ -413,8 +324,7 @@ def render_blends(blends, sources=False, reweight=False, mask_footprint=True, de
     import time
 
     blends = list(blends)
-    budget = WORKING_SET_BYTES if _working_set_bytes is None else _working_set_bytes
-    device = 0 if device is None else int(device)
+    budget, device = defaults(_working_set_bytes, device)
     flags = ((SOURCES if sources or reweight else 0) | (REWEIGHT if reweight else 0)
              | (MASK if mask_footprint else 0))
     times = dict(plan=0.0, pack=0.0, device=0.0, results=0.0, loop=0.0)
@@ -435,7 +345,7 @@ def render_blends(blends, sources=False, reweight=False, mask_footprint=True, de
                 fallback.append((i, "at run time: {}".format(why)))
         items = [(i, _plan_bytes(plans[i], key, flags)) for i in idx if i in plans]
         times["plan"] += time.perf_counter() - t0
-        for chunk in _chunks(items, budget):
+        for chunk in chunks(items, budget):
             t0 = time.perf_counter()
             packed = pack([plans[i] for i in chunk], key, flags)
             t1 = time.perf_counter()

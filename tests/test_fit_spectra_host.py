@@ -209,13 +209,16 @@ def test_chunks_at_a_middle_budget_and_at_one_byte():
     # output of 2 bands x (4 + 2) sums in float64
     assert need[0] == (800 + 162) * 4 + (18 + 2 * 2 * 6) * 8
 
+    from scarlet_amd import _catalog
+
     def ids(chunks):
         return [[GROUP[plans.index(p)] for p in c] for c in chunks]
 
-    assert ids(sp._chunks(plans, key, sum(need))) == [GROUP]
-    assert ids(sp._chunks(plans, key, 1)) == [[n] for n in GROUP]
+    items = [(p, sp._plan_bytes(p, key)) for p in plans]
+    assert ids(_catalog.chunks(items, sum(need))) == [GROUP]
+    assert ids(_catalog.chunks(items, 1)) == [[n] for n in GROUP]
     middle = need[0] + need[1] + need[2]
-    chunks = sp._chunks(plans, key, middle)
+    chunks = _catalog.chunks(items, middle)
     assert 1 < len(chunks) < len(GROUP) and chunks[0] == plans[:3]
     assert [p for c in chunks for p in c] == plans
     for c, nxt in zip(chunks, chunks[1:] + [None]):

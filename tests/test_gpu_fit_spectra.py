@@ -133,7 +133,7 @@ GROUP = ["union-15", "disjoint", "union-17", "present-32", "components-64"]
 
 
 def test_one_group_in_chunks_and_orders_gives_the_same_bits():
-    from scarlet_amd import lite
+    from scarlet_amd import _catalog, lite
     from scarlet_amd.lite import spectra
 
     key = (np.dtype(np.float32), 2, 3, 3)
@@ -148,7 +148,8 @@ def test_one_group_in_chunks_and_orders_gives_the_same_bits():
 
     plans = [spectra._plan_blend(cases.make_blend(n))[1] for n in GROUP]
     middle = sum(spectra._plan_bytes(p, key) for p in plans[:3])
-    assert 1 < len(spectra._chunks(plans, key, middle)) < len(GROUP)
+    items = [(p, spectra._plan_bytes(p, key)) for p in plans]
+    assert 1 < len(_catalog.chunks(items, middle)) < len(GROUP)
     forward = list(range(len(GROUP)))
     want = run(forward)
     for order, budget, twice in ((forward, middle, False), (forward, 1, False),

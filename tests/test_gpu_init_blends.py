@@ -135,7 +135,7 @@ def test_device_sums_against_longdouble(runs):
     absolute values; asserted at 1e-12 of the largest entry of its kind."""
     import torch
 
-    from scarlet_amd import initialization as init
+    from scarlet_amd import _catalog, initialization as init
 
     cat, got, _, _ = runs("two", False)
     for case, (sources, _) in zip(cat, got):
@@ -143,15 +143,15 @@ def test_device_sums_against_longdouble(runs):
             continue
         frame, obs = case[1], case[3]
         sp = init.pack_spectra([(0, frame, obs, sources)], [0])
-        dv = init._Device(0)
+        dv = _catalog.Launcher(0, pad=1)
         K, C = int(sp["blends"][0]["n_comp"]), frame.C
         d_data, d_weights = dv.cat([obs.data], np.float32), dv.cat([obs.weights], np.float32)
         d_morphs, d_stamps = dv.cat(sp["morphs"], np.float64), dv.cat(sp["stamps"], np.float64)
         d_part, d_sums = dv.empty(sp["n_part"], np.float64), dv.empty(sp["n_out"], np.float64)
-        dv.call("spectra_tiles", sp["blends"], sp["components"], sp["work"], d_data, d_weights,
-                obs.data.size, d_stamps, sp["n_stamp"], d_morphs, sp["n_morph"], d_part,
-                sp["n_part"], sp["n_out"])
-        dv.call("spectra_reduce", sp["blends"], d_part, sp["n_part"], d_sums, sp["n_out"])
+        init._call(dv, "spectra_tiles", sp["blends"], sp["components"], sp["work"], d_data,
+                   d_weights, obs.data.size, d_stamps, sp["n_stamp"], d_morphs, sp["n_morph"],
+                   d_part, sp["n_part"], sp["n_out"])
+        init._call(dv, "spectra_reduce", sp["blends"], d_part, sp["n_part"], d_sums, sp["n_out"])
         torch.cuda.synchronize()
         sums = d_sums.cpu().numpy().reshape(C, K * K + 3 * K)
         want = ic.normal_equations(sp, 0, obs.data, obs.weights, np.longdouble)

@@ -41,7 +41,7 @@ def test_one_group_of_five_blends_in_one_two_and_five_chunks():
     sizes, three, two and one source -- in one chunk: every offset past the first blend's is
     in use.  Equal to the loop and the oracle; a budget that cuts the group into chunks of
     two, two and one blend and a budget of one byte give the same bits."""
-    from scarlet_amd import lite
+    from scarlet_amd import _catalog, lite
     from scarlet_amd.lite import initialization as li
 
     group = [init_cases.make_case(n) for n in init_cases.GROUP]
@@ -53,8 +53,8 @@ def test_one_group_of_five_blends_in_one_two_and_five_chunks():
     assert idx == [0, 1, 2, 3, 4]
     middle = init_cases.group_budget(group, key)
     items = [(i, li._init_bytes(c.obs, len(c.centers), 4, key)) for i, c in enumerate(group)]
-    assert li._init_chunks(items, key, middle) == [[0, 1], [2, 3], [4]]
-    assert li._init_chunks(items, key, li.WORKING_SET_BYTES) == [[0, 1, 2, 3, 4]]
+    assert _catalog.chunks(items, middle) == [[0, 1], [2, 3], [4]]
+    assert _catalog.chunks(items, _catalog.WORKING_SET_BYTES) == [[0, 1, 2, 3, 4]]
 
     batch = lite.init_blends(observations, centers, wavelets=wavelets, **options)
     worst = 0.0

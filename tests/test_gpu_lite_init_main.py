@@ -62,7 +62,7 @@ def test_one_group_of_five_blends_in_one_three_and_five_chunks():
     the first blend's is in use.  Equal to the loop and the oracle; a budget that cuts the
     group into chunks of two, two and one blend, a budget of one byte and another order of the
     blends give the same bits, the spectra of joint fits included."""
-    from scarlet_amd import lite
+    from scarlet_amd import _catalog, lite
     from scarlet_amd.lite import initialization as li
 
     group = [mc.make_case(n) for n in mc.GROUP]
@@ -73,11 +73,11 @@ def test_one_group_of_five_blends_in_one_three_and_five_chunks():
     assert idx == [0, 1, 2, 3, 4] and len({o.images.shape[1:] for o in observations}) == 3
     items = [(i, li._main_bytes(c.obs, len(c.centers), key)) for i, c in enumerate(group)]
     middle = items[0][1] + items[1][1]
-    assert li._init_chunks(items, key, middle) == [[0, 1], [2, 3], [4]]
+    assert _catalog.chunks(items, middle) == [[0, 1], [2, 3], [4]]
 
     batch = mc.run_batch(group)
-    assert li._MAIN_LAUNCHES == ["main_coadd", "snr", "taps", "taps", "main_sweep", "crop",
-                                 "main_split", "fit"]
+    assert _catalog.Launcher.last.launches == ["main_coadd", "snr", "taps", "taps", "main_sweep",
+                                               "crop", "main_split", "fit"]
     worst = max(_check(batch[i], case) for i, case in enumerate(group))
     print("largest |batch - oracle| / max(|loop - oracle|, floor):", worst)
     for budget in (middle, 1):

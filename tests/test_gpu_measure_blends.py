@@ -121,7 +121,7 @@ def test_alone_in_chunks_and_reversed(runs):
     """A blend's table has the same bits alone, in the whole catalogue, in chunks and in the
     reversed list."""
     import scarlet_amd as scarlet
-    from scarlet_amd import measure
+    from scarlet_amd import _catalog, measure
 
     blends, tables = runs["blends"], runs["tables"]
     device = sorted(runs["device"])
@@ -139,7 +139,7 @@ def test_alone_in_chunks_and_reversed(runs):
     need = [measure._plan_bytes(runs["device"][i][1], (3, 5, 5)) for i in group]
     assert len(group) == 3
     budget = need[0] + need[1]
-    assert measure._chunks(list(zip(group, need)), budget) == [group[:2], group[2:]]
+    assert _catalog.chunks(list(zip(group, need)), budget) == [group[:2], group[2:]]
     for i, table in zip(group, scarlet.measure_blends([blends[i] for i in group],
                                                       _working_set_bytes=budget)):
         assert table.tobytes() == tables[i].tobytes(), runs["cat"][i][0]

@@ -298,7 +298,7 @@ def test_alone_in_chunks_and_reversed(runs):
     """A blend's outputs have the same bits alone, in the whole catalogue, with every blend a
     chunk of its own, with two blends to a chunk, and in the reversed list."""
     import scarlet_amd as scarlet
-    from scarlet_amd import measure, rendering
+    from scarlet_amd import _catalog, rendering
 
     blends, results = runs["blends"], runs["results"]
     device = sorted(runs["device"])
@@ -318,7 +318,7 @@ def test_alone_in_chunks_and_reversed(runs):
     need = [rendering._plan_bytes(runs["device"][i][1], key, flags) for i in group]
     assert len(group) == 5
     budget = need[0] + need[1]  # holds the first two blends, not three
-    chunks = measure._chunks(list(zip(group, need)), budget)
+    chunks = _catalog.chunks(list(zip(group, need)), budget)
     assert chunks[0] == group[:2] and sum(chunks, []) == group
     report = {}
     for i, res in zip(group, scarlet.render_blends([blends[i] for i in group], reweight=True,

@@ -192,15 +192,15 @@ def test_packed_tables_stay_inside_their_buffers(cat):
 
 
 def test_small_chunks_pack_a_blend_to_the_same_bytes(cat):
-    from scarlet_amd import initialization as init
+    from scarlet_amd import _catalog, initialization as init
 
     opts = init._options(ic.OPTIONS["two"])
     blends = _device_blends(cat)
     whole = init.pack_chunk(blends, opts)
     items = [(i, init._blend_bytes(b[0], len(b[1]), 21)) for i, b in enumerate(blends)]
-    assert init._chunks(items, 1) == [[i] for i in range(len(blends))]
-    assert init._chunks(items, 1 << 40) == [list(range(len(blends)))]
-    two = init._chunks(items, items[0][1] + items[1][1])
+    assert _catalog.chunks(items, 1) == [[i] for i in range(len(blends))]
+    assert _catalog.chunks(items, 1 << 40) == [list(range(len(blends)))]
+    two = _catalog.chunks(items, items[0][1] + items[1][1])
     assert two[0] == [0, 1] and sum(two, []) == list(range(len(blends)))
     first = 0
     for k, blend in enumerate(blends):

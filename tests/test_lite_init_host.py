@@ -177,6 +177,7 @@ def test_plan_refuses_a_centre_outside_the_frame(cases):
 def test_the_group_of_the_gpu_test_is_one_group(cases):
     """The cases the GPU test batches together share one device group, and the budgets it
     uses cut them into one, several multi-blend and one-blend chunks."""
+    from scarlet_amd import _catalog
     from scarlet_amd import lite
     from scarlet_amd.lite import initialization as li
 
@@ -192,7 +193,7 @@ def test_the_group_of_the_gpu_test_is_one_group(cases):
     assert len({len(c.centers) for c in group}) == 3
     items = [(i, li._init_bytes(c.obs, len(c.centers), 4, key)) for i, c in enumerate(group)]
     middle = init_cases.group_budget(group, key)
-    assert li._init_chunks(items, key, middle) == [[0, 1], [2, 3], [4]]
+    assert _catalog.chunks(items, middle) == [[0, 1], [2, 3], [4]]
 
 
 def test_plan_of_an_empty_catalogue_and_of_a_blend_without_centres(cases):
@@ -207,6 +208,7 @@ def test_plan_of_an_empty_catalogue_and_of_a_blend_without_centres(cases):
 
 
 def test_chunks_follow_the_budget():
+    from scarlet_amd import _catalog
     from scarlet_amd.lite import initialization as li
 
     key = (np.dtype(np.float64), np.dtype(np.float32), np.dtype(np.float32), 2)
@@ -218,15 +220,16 @@ def test_chunks_follow_the_budget():
     assert li._n_planes(obs, np.zeros((4, 10, 10)), 5) == 4
     assert li._n_planes(obs, None, 2) == 3  # what get_detect_wavelets makes
     items = [(i, need) for i in range(5)]
-    assert li._init_chunks(items, key, 2 * need) == [[0, 1], [2, 3], [4]]
-    assert li._init_chunks(items, key, 1) == [[0], [1], [2], [3], [4]]
-    assert li._init_chunks(items, key, 1 << 40) == [[0, 1, 2, 3, 4]]
-    assert li._init_chunks([], key, 1) == []
+    assert _catalog.chunks(items, 2 * need) == [[0, 1], [2, 3], [4]]
+    assert _catalog.chunks(items, 1) == [[0], [1], [2], [3], [4]]
+    assert _catalog.chunks(items, 1 << 40) == [[0, 1, 2, 3, 4]]
+    assert _catalog.chunks([], 1) == []
 
 
 def test_descriptor_layouts_and_offsets():
     """The records are the C structs of include/scarlet_amd.h, and packed buffers follow
     each other without gaps."""
+    from scarlet_amd import _catalog
     from scarlet_amd.lite import initialization as li
 
     sizes = {li._COADD_DESC: 72, li._SNR_DESC: 40, li._TAPS_DESC: 48, li._MASK_DESC: 40,
@@ -234,7 +237,7 @@ def test_descriptor_layouts_and_offsets():
     for desc, size in sizes.items():
         assert desc.itemsize == size
     assert li._COADD_DESC.fields["n_pix"][1] == 48 and li._FIT_DESC.fields["image_off"][1] == 64
-    off, total = li._offsets([6, 0, 10])
+    off, total = _catalog.offsets([6, 0, 10])
     assert list(off) == [0, 6, 6] and total == 16
     assert li._plane_selection(slice(None, -1), 4) == (0, 3, 1)
     assert li._plane_selection(slice(2, -1), 4) == (2, 1, 1)

@@ -307,7 +307,7 @@ def test_plan_refuses_bad_catalogues(cases):
 
 
 def test_chunks_follow_the_working_set(cases):
-    from scarlet_amd import lite
+    from scarlet_amd import _catalog, lite
     from scarlet_amd.lite import initialization as li
 
     group = [cases[n] for n in mc.GROUP]
@@ -319,6 +319,6 @@ def test_chunks_follow_the_working_set(cases):
     # detection image, images, variance, four frames per source, stamps, the cosine table
     assert items[0][1] == ((1 + 4 + 4 * 3) * 120 * 4 + 2 * 9 * (4 + 4 + 8) + 64 * 19 * 23)
     middle = items[0][1] + items[1][1]
-    assert li._init_chunks(items, key, middle) == [[0, 1], [2, 3], [4]]
-    assert li._init_chunks(items, key, li.WORKING_SET_BYTES) == [[0, 1, 2, 3, 4]]
-    assert li._init_chunks(items, key, 1) == [[0], [1], [2], [3], [4]]
+    assert _catalog.chunks(items, middle) == [[0, 1], [2, 3], [4]]
+    assert _catalog.chunks(items, _catalog.WORKING_SET_BYTES) == [[0, 1, 2, 3, 4]]
+    assert _catalog.chunks(items, 1) == [[0], [1], [2], [3], [4]]

@@ -122,7 +122,7 @@ def test_table_dtype():
 def test_packed_tables(planned):
     """Offsets, counts and buffer sizes of two blends of one group packed together; the tile
     counts of hand-worked boxes."""
-    from scarlet_amd import measure
+    from scarlet_amd import _catalog, measure
 
     by_name = {p[0]: p for p in planned}
     key = (3, 5, 5)
@@ -162,7 +162,7 @@ def test_packed_tables(planned):
     assert tiles((-2, -3, 13, 17), (9, 11), 5, 5) == 1     # clipped to the 9 x 11 frame
     assert tiles((40, 40, 3, 3), (9, 11), 5, 5) == 0       # out of reach
     # chunks: runs within the budget, a blend beyond it alone
-    assert measure._chunks([(0, 5), (1, 5), (2, 20), (3, 1)], 10) == [[0, 1], [2], [3]]
+    assert _catalog.chunks([(0, 5), (1, 5), (2, 20), (3, 1)], 10) == [[0, 1], [2], [3]]
 
 
 def test_oracle_model_is_get_model(planned):

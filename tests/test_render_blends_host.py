@@ -99,7 +99,7 @@ def test_packed_tables_bytes_and_chunks(planned):
     """Offsets, counts and buffer sizes of two blends of one group packed together, with and
     without the sources; the regions and tile counts of hand-worked boxes; chunks at a small
     budget."""
-    from scarlet_amd import measure, rendering
+    from scarlet_amd import _catalog, measure, rendering
 
     key = (3, 5, 5)
     plans = [planned["tiny"][2], planned["list map"][2]]
@@ -155,8 +155,8 @@ def test_packed_tables_bytes_and_chunks(planned):
     assert with_flux - with_sources == 4 * cubes + 8 * 2 * 775
     group = [planned[n][2] for n in ("tiny", "list map", "slice map")]
     need = [rendering._plan_bytes(p, key, 0) for p in group]
-    assert measure._chunks(list(enumerate(need)), need[0] + need[1]) == [[0, 1], [2]]
-    assert measure._chunks(list(enumerate(need)), 1) == [[0], [1], [2]]
+    assert _catalog.chunks(list(enumerate(need)), need[0] + need[1]) == [[0, 1], [2]]
+    assert _catalog.chunks(list(enumerate(need)), 1) == [[0], [1], [2]]
 
 
 def test_oracle_rendering_is_the_float64_fft(planned):

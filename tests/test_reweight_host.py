@@ -150,15 +150,17 @@ def test_groups_keep_input_order_and_mixed_dtypes_fall_back():
 
 
 def test_chunks_cover_every_source_once():
+    from scarlet_amd import _catalog
     from scarlet_amd.lite import measure
 
     blends = [cases.make_blend("7x5-3x3", seed=s) for s in range(5)]
     key = measure._group_key(blends[0])
     plans = [measure._plan_blend(b) for b in blends]
-    assert len(measure._chunks(plans, key, measure.WORKING_SET_BYTES)) == 1
+    items = [(p, measure._plan_bytes(p, key)) for p in plans]
+    assert len(_catalog.chunks(items, _catalog.WORKING_SET_BYTES)) == 1
     need = (measure._plan_elements(plans[0]) + 27) * 4
     for budget, n in ((1, 5), (need, 5), (2 * need, 3), (5 * need, 1)):
-        chunks = measure._chunks(plans, key, budget)
+        chunks = _catalog.chunks(items, budget)
         assert len(chunks) == n
         assert [id(p) for c in chunks for p in c] == [id(p) for p in plans]
         seen = []

@@ -46,7 +46,7 @@ def main():
 
     import torch
 
-    from scarlet_amd import lite
+    from scarlet_amd import _catalog, lite
     from scarlet_amd.lite import initialization
 
     assert torch.cuda.is_available(), "needs a GPU"
@@ -81,21 +81,21 @@ def main():
 
     t_batch = timed(batch, args.repeats)
     t_loop = timed(loop, args.repeats)
-    launches = list(initialization._MAIN_LAUNCHES)
+    launches = list(_catalog.Launcher.last.launches)
     # one more batch call with clocks inside: the device steps up to the host's decisions (the
     # sweep's download ends with the device idle), the decisions, the rest of the launches with
     # their download, the assembly
     split = {}
     saved_launches, saved_assemble = initialization._main_launches, initialization._main_assemble
 
-    def clocked_launches(ch, blends_, opts):
+    def clocked_launches(ch, key, blends_, opts):
         real_cpu, real_call = ch.torch.Tensor.cpu, type(ch).call
         marks, crop_at = [], []
 
-        def call(self, step, *a, **k):
-            if step == "crop":
+        def call(self, entry, *a, **k):
+            if k.get("tag") == "crop":
                 crop_at.append(time.perf_counter())
-            return real_call(self, step, *a, **k)
+            return real_call(self, entry, *a, **k)
 
         def cpu(self, *a, **k):
             out = real_cpu(self, *a, **k)
@@ -105,7 +105,7 @@ def main():
         t0 = time.perf_counter()
         ch.torch.Tensor.cpu, type(ch).call = cpu, call
         try:
-            out = saved_launches(ch, blends_, opts)
+            out = saved_launches(ch, key, blends_, opts)
         finally:
             ch.torch.Tensor.cpu, type(ch).call = real_cpu, real_call
         t1 = time.perf_counter()
