@@ -1369,12 +1369,15 @@ static int interleave_observation(smi_batch *b, const float *d_data, const float
     if (!b->fused) return SMI_OK;
     const int H = b->d.H, W = b->d.W;
     const int64_t planes = (int64_t)b->d.n_blends * b->d.C;
-    // (sixteen elements of slack, zero: the kernel's loads of the columns W .. W + 15 of the last
-    // pair, which it multiplies by a weight of 0 -- they have to be finite)
-    const size_t n = (size_t)planes * ((H + 1) / 2) * W;
+    // (Fx elements of slack, zero: the kernel loads the columns W .. 16 NX1 - 1 of the last pair
+    // and multiplies them by a weight of 0 -- they have to be finite.  NX1 = Fx / 16 - ZB blocks,
+    // and ZB is the smaller padding-block count of the two axes (launch_impl), so NX1 can be
+    // more than the blocks the frame's columns need: a 54 x 44 frame under 80 x 80 reads up to
+    // column 63, twenty elements beyond its last row -- sixteen were not enough)
+    const size_t n = (size_t)planes * ((H + 1) / 2) * W, slack = (size_t)b->Fx;
     if (!*dw) {
-        SMI_HIP(dev_alloc(dw, n + 16));
-        SMI_HIP(hipMemset(*dw + n, 0, 16 * sizeof(float4)));
+        SMI_HIP(dev_alloc(dw, n + slack));
+        SMI_HIP(hipMemset(*dw + n, 0, slack * sizeof(float4)));
     }
     if (adopted) SMI_HIP(hipDeviceSynchronize());
     launch_interleave_obs(d_data, d_weights, *dw, planes, H, W, b->stream);

@@ -94,6 +94,33 @@ __device__ __forceinline__ cf cmulc(cf a, cf b) {
         : "v"(a), "v"(b), "v"(t));
     return r;
 }
+// a and b of the lane l <- a and b of the lane l ^ 32, without the LDS (gfx950).
+// v_permlane32_swap vdst, src swaps the lanes 32 .. 63 of vdst with the lanes 0 .. 31 of src
+// and leaves the other two halves alone.  With a = [a.lo, a.hi] (the two half-waves):
+//   swap(a, b):  a = [a.lo, b.lo], b = [a.hi, b.hi]
+//   swap(b, a):  b = [a.hi, a.lo], a = [b.hi, b.lo]
+// i.e. each register now holds the other one's value of the partner half-wave: two swaps
+// for two registers, no copy, no select; the names change places (statically).  The
+// builtin, not inline assembly: the hazard recogniser places the two wait states that the
+// swap needs behind a VALU write of an operand.
+__device__ __forceinline__ void rotate_half_waves(float &a, float &b) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a),
+                                                    __builtin_bit_cast(unsigned, b), false, false);
+    const auto s = __builtin_amdgcn_permlane32_swap(r[1], r[0], false, false);
+    // (copies of the elements first: __builtin_bit_cast of an element of a vector value reads
+    // element 0 whichever is named, with this compiler)
+    const unsigned s0 = s[0], s1 = s[1];
+    a = __builtin_bit_cast(float, s0);
+    b = __builtin_bit_cast(float, s1);
+}
+// (component by component: a complex number stays in its aligned register pair)
+__device__ __forceinline__ void rotate_half_waves(cf &u, cf &v) {
+    float ux = u.x, uy = u.y, vx = v.x, vy = v.y;
+    rotate_half_waves(ux, vx);
+    rotate_half_waves(uy, vy);
+    u = cf{ux, uy};
+    v = cf{vx, vy};
+}
 // b + w d and b - w d with w = -i (forward) or +i (inverse), scaled by s:
 // -i d = (d.y, -d.x), +i d = (-d.y, d.x)
 template <bool INV>

@@ -142,8 +142,41 @@ __device__ __forceinline__ int pos(int k) {
 // sum over the workgroup in two halves around a barrier the caller has anyway: every
 // wavefront leaves its partial sum (wave_partial, before the barrier), one thread adds them
 // up (sum_partials, after it)
+// The xor butterfly 32, 16, 8, 4, 2, 1 of __shfl_xor with the same two operands in every
+// addition (so the sum keeps its bits), but the partner's value comes through the VALU where
+// an instruction moves lanes that way, not through ds_bpermute_b32:
+//   32, 16: v_permlane32_swap / v_permlane16_swap of a register with a copy of itself leave
+//           [lo, lo] and [hi, hi] (half-waves; for 16: [r0, r0, r2, r2] and [r1, r1, r3, r3],
+//           rows of 16 lanes) -- every lane holds its own value in one of them and its
+//           partner's in the other, and the addition commutes;
+//   8: row_ror:8 (lane (i + 8) % 16 of the row = i ^ 8);  2, 1: quad_perm [2,3,0,1], [1,0,3,2];
+//   4: no DPP control is an xor by 4, it stays with __shfl_xor.
+template <int CTRL>
+__device__ __forceinline__ double dpp_move(double v) {
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = (unsigned)b, hi = (unsigned)(b >> 32);
+    const unsigned plo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false);
+    const unsigned phi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false);
+    return __builtin_bit_cast(double, ((unsigned long long)phi << 32) | plo);
+}
+template <bool ROWS>  // partners 16 lanes apart (ROWS) or 32
+__device__ __forceinline__ double add_partner_swap(double v) {
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = (unsigned)b, hi = (unsigned)(b >> 32);
+    const auto l = ROWS ? __builtin_amdgcn_permlane16_swap(lo, lo, false, false)
+                        : __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+    const auto h = ROWS ? __builtin_amdgcn_permlane16_swap(hi, hi, false, false)
+                        : __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    return __builtin_bit_cast(double, ((unsigned long long)h[0] << 32) | l[0]) +
+           __builtin_bit_cast(double, ((unsigned long long)h[1] << 32) | l[1]);
+}
 __device__ __forceinline__ void wave_partial(double v, double *part) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    v = add_partner_swap<false>(v);
+    v = add_partner_swap<true>(v);
+    v += dpp_move<0x128>(v);  // row_ror:8
+    v += __shfl_xor(v, 4, 64);
+    v += dpp_move<0x4e>(v);  // quad_perm:[2,3,0,1]
+    v += dpp_move<0xb1>(v);  // quad_perm:[1,0,3,2]
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
 }
 __device__ __forceinline__ double sum_partials(const double *part) {
@@ -422,8 +455,21 @@ struct Conv {
         if (kGroupsPerTrip >= (C::FY / 2 + 31) / 32) return 1;
         return ((n_pairs + 31) / 32 + kGroupsPerTrip - 1) / kGroupsPerTrip;
     }
-    static __device__ __forceinline__ cf from_partner(cf v) {
-        return cf{__shfl_xor(v.x, 32, 64), __shfl_xor(v.y, 32, 64)};
+    // The lanes l and l ^ 32 exchange u and v: afterwards both hold what the partner lane had
+    // there.  In registers (fftk::rotate_half_waves): v_permlane32_swap takes no trip through
+    // the LDS queue, needs no address and no lgkmcnt wait, where __shfl_xor(., 32) is a
+    // ds_bpermute_b32 per dword -- a third of a block pass's LDS instructions.  The values
+    // the lane had are gone: it needed them only for its partner.
+    // kExchangeInRegisters = false keeps ds_bpermute (an instance that the rotation would
+    // push into scratch memory would take it; none does).
+    static constexpr bool kExchangeInRegisters = true;
+    static __device__ __forceinline__ void exchange(cf &u, cf &v) {
+        if constexpr (kExchangeInRegisters) {
+            fftk::rotate_half_waves(u, v);
+        } else {
+            u = cf{__shfl_xor(u.x, 32, 64), __shfl_xor(u.y, 32, 64)};
+            v = cf{__shfl_xor(v.x, 32, 64), __shfl_xor(v.y, 32, 64)};
+        }
     }
     // Xa = za + conj(zb), Xb = -i (za - conj(zb))   (the 1/2 lives in K^); one packed addition
     // each, the swaps of halves and the signs in the operand modifiers (the compiler builds a
@@ -470,7 +516,9 @@ struct Conv {
             };
             if (b.kind == 0) {  // uniform over the wavefront
 #pragma unroll
-                for (int k2 = 0; k2 < 8; ++k2) sep(va[k2], from_partner(va[15 - k2]), xa[k2], xb[k2]);
+                for (int i = 8; i < kF2; i += 2) exchange(va[i], va[i + 1]);  // the mirror block's
+#pragma unroll
+                for (int k2 = 0; k2 < 8; ++k2) sep(va[k2], va[15 - k2], xa[k2], xb[k2]);
                 store();
             } else if (b.kind == 1) {
                 // (two branches: a select between va[a] and va[b] would be compiled into a
@@ -529,8 +577,10 @@ struct Conv {
 #pragma unroll
                 for (int k2 = 0; k2 < 8; ++k2) {
                     va[k2] = plus(xa[k2], xb[k2]);
-                    va[15 - k2] = from_partner(minus(xa[k2], xb[k2]));
+                    va[15 - k2] = minus(xa[k2], xb[k2]);  // for the mirror block
                 }
+#pragma unroll
+                for (int i = 8; i < kF2; i += 2) exchange(va[i], va[i + 1]);
                 tail();
             } else if (b.kind == 1) {
                 // (slot 0 of the rows: DC term in the real, Nyquist term in the imaginary part)
@@ -799,7 +849,7 @@ __global__ __launch_bounds__(kThreads) void fused_conv_kernel(BatchView v, const
         cf dv[NX1], wv[NX1];
         auto fetch = [&](const Item &s, auto from, auto to) {
             // (a thread without an item of its own reads the last pair; columns beyond W read
-            // what follows the row -- the allocation has sixteen elements of slack -- and are
+            // what follows the row -- the allocation has Fx zeroed elements of slack -- and are
             // discarded below.  One offset register, the column step an immediate.)
             uint32_t o = (uint32_t)(min(s.j, cv.n_pairs - 1) * W + s.n2) * 16u;
             asm volatile("" : "+v"(o));
